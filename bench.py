@@ -18,7 +18,11 @@ M/inference/text_generation/generation.py:123-205).  Context parallelism CP = N 
 total work fixed as N grows ("strong" scaling).  Synthetic data, seeded random bf16 weights of
 the real architecture; inputs are resident in HBM before the timed region.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with these extra objects:
+Prints ONE JSON line on rank 0 (contract in the task statement).  A plain run does only what that line's headline needs: set-up,
+warm-up, the timed steps, the outputs of `--dump-outputs DIR` and the line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`,
+`config`, ...).  `--dump-outputs DIR` writes what the last timed step returned, the next-token logits [b, vocab], as
+DIR/logits.npy (float32); the inputs and weights are seeded, so two builds run with the same arguments can be compared output for
+output.  With `--full` the run also measures and checks the rest and adds these objects to the line:
   roofline      dominant kernel = flash-attention forward: algorithmic FLOPs per launch
                 (4*d*heads*visible (q,k) pairs on this rank) / mean launch time measured live with
                 HIP events on the launch stream, against the 2.5 PFLOP/s dense bf16 MFMA peak;
@@ -29,7 +33,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with these extra
                 gather (HIP events around every wait, mean per layer / total per prefill), the same all-gather timed alone after the
                 timed region (ms, GB/s received per rank), the logits gather;
   cross_rank_check (N > 1) after the timed region: the logits of the 2 N positions the ranks marked (two per rank, sync_output's
-                rows) against the SAME prefill run by rank 0 alone at CP = 1 — rel-L2, max-abs, argmax agreement.
+                rows) against the SAME prefill run by rank 0 alone at CP = 1 — rel-L2, max-abs, argmax agreement;
+  parity_check  (N = 1) after the timed region: one more prefill forced through the context-parallel code path against the plain one.
 """
 from __future__ import annotations
 
@@ -356,10 +361,16 @@ def main():
     ap.add_argument("--layers", type=int, default=48, help="debug only; the metric needs all 48 layers")
     ap.add_argument("--vit-layers", type=int, default=24, help="debug only")
     ap.add_argument("--frames", type=int, default=-1, help="debug only; default fills the sequence (506 @128K)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity-check", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check the rest: roofline, comm, parity / cross-rank checks, CPU baseline (module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
+    ap.add_argument("--no-parity-check", action="store_true", help="with --full: leave out the parity / cross-rank checks")
     ap.add_argument("--dry-run", action="store_true", help="plumbing check: tiny model (2 + 2 layers, seq 4096, 8 frames); NOT a measurement")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     if args.dry_run:
         args.seq, args.layers, args.vit_layers, args.frames, args.no_cpu_baseline = 4096, 2, 2, 8, True
@@ -447,9 +458,10 @@ def main():
         warm_done = 1
     for _ in range(max(args.warmup - warm_done, 0)):
         step()
-    model.attn_events = []
-    if world > 1:
-        model.core_attention.comm_log = []
+    if args.full:                                   # HIP events per attention launch / per K / V wait: roofline and comm only
+        model.attn_events = []
+        if world > 1:
+            model.core_attention.comm_log = []
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -461,6 +473,55 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     assert torch.isfinite(out.float()).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"logits": out})
+
+    ms_per_step = dt / args.steps * 1e3
+    value = seq / (dt / args.steps)
+    fpt = flops_per_token(seq, frames, cfg, vcfg)
+    name = {16384: "Long-VITA-16K", 131072: "Long-VITA-128K", 1048576: "Long-VITA-1M"}.get(seq, f"Long-VITA (seq {seq})")
+    line = {
+        "metric": "prefill tokens/sec/node (ViT+LLM) at seq=128K" if seq == 131072 else f"prefill tokens/sec/node (ViT+LLM) at seq={seq}",
+        "value": value, "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": f"{name} prefill: {frames}-frame synthetic video (InternViT-300M + projector) + "
+                               f"Qwen2.5-14B decoder ({cfg.num_layers} layers), seq {seq}, logits-masked LM head",
+                   "seq_len": seq, "frames": frames, "global_batch": 1, "parallelism": f"cp{world}", "dry_run": bool(args.dry_run),
+                   "weights": "seeded random bf16 (N(0,0.02))",
+                   "algorithmic_gflop_per_token": fpt / 1e9,
+                   "end_to_end_tflops_per_gpu": fpt * value / world / 1e12,
+                   "end_to_end_frac_of_mfma_peak": fpt * value / world / 1e12 / MFMA_BF16_PEAK_TFLOPS,
+                   # measured on rank 0, to set against the byte model of DESIGN.md 6.1 (weights + workspace + frames)
+                   "peak_hbm_gb_rank0": torch.cuda.max_memory_allocated() / 2 ** 30},
+    }
+    if degraded:
+        line["degraded"] = degraded
+    if staged:
+        line["transport"] = "gloo-staged (diagnostic: device tensors through host memory; not a measurement)"
+    if args.full:
+        line.update(full_report(args, model, step, out, cfg, seq, frames, fpt, tokens, ext, world, rank, dev, selftest))
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def dump_outputs(directory: str, arrays: dict) -> None:
+    """--dump-outputs: every array the timed step returned, as DIR/<name>.npy in float32 (the logits row is 152064 values)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    host = {name: t.detach().float().cpu().numpy() for name, t in arrays.items()}
+    assert sum(a.nbytes for a in host.values()) <= 64 << 20, {name: a.shape for name, a in host.items()}
+    for name, a in host.items():
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+
+
+def full_report(args, model, step, out, cfg, seq, frames, fpt, tokens, ext, world, rank, dev, selftest) -> dict:
+    """--full, after the timed region: roofline, comm, the parity / cross-rank checks and the CPU baseline (module docstring).
+    Collective on every rank; only rank 0 measures the CPU baseline."""
+    extra = {}
     comm_log = model.core_attention.comm_log or []
     model.core_attention.comm_log = None
     # diagnostics of the exchange: never allowed to cost the measured line (every rank takes the same path through the collectives)
@@ -511,51 +572,25 @@ def main():
         except (OSError, KeyError, ValueError):
             continue
 
-    ms_per_step = dt / args.steps * 1e3
-    value = seq / (dt / args.steps)
-    fpt = flops_per_token(seq, frames, cfg, vcfg)
-    name = {16384: "Long-VITA-16K", 131072: "Long-VITA-128K", 1048576: "Long-VITA-1M"}.get(seq, f"Long-VITA (seq {seq})")
-    line = {
-        "metric": "prefill tokens/sec/node (ViT+LLM) at seq=128K" if seq == 131072 else f"prefill tokens/sec/node (ViT+LLM) at seq={seq}",
-        "value": value, "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic",
-        "config": {"workload": f"{name} prefill: {frames}-frame synthetic video (InternViT-300M + projector) + "
-                               f"Qwen2.5-14B decoder ({cfg.num_layers} layers), seq {seq}, logits-masked LM head",
-                   "seq_len": seq, "frames": frames, "global_batch": 1, "parallelism": f"cp{world}", "dry_run": bool(args.dry_run),
-                   "weights": "seeded random bf16 (N(0,0.02))",
-                   "algorithmic_gflop_per_token": fpt / 1e9,
-                   "end_to_end_tflops_per_gpu": fpt * value / world / 1e12,
-                   "end_to_end_frac_of_mfma_peak": fpt * value / world / 1e12 / MFMA_BF16_PEAK_TFLOPS,
-                   # measured on rank 0, to set against the byte model of DESIGN.md 6.1 (weights + workspace + frames)
-                   "peak_hbm_gb_rank0": torch.cuda.max_memory_allocated() / 2 ** 30},
-        "roofline": {"bound": "mfma", "kernel": "flash_fwd64_kernel (d = 128, causal; 4 waves x 64 rows)" if os.environ.get("VITA_ATTN64", "1") != "0" else "flash_fwd_kernel<128, causal>", "achieved": achieved,
-                     "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TFLOPS,
-                     "traffic": traffic, "traffic_source": traffic_src, "launches_timed": len(ev_ms), "ms_per_launch": attn_ms,
-                     "flop_per_launch": attn_flops},
-    }
-    if degraded:
-        line["degraded"] = degraded
-    if staged:
-        line["transport"] = "gloo-staged (diagnostic: device tensors through host memory; not a measurement)"
+    extra["roofline"] = {"bound": "mfma", "kernel": "flash_fwd64_kernel (d = 128, causal; 4 waves x 64 rows)" if os.environ.get("VITA_ATTN64", "1") != "0" else "flash_fwd_kernel<128, causal>", "achieved": achieved,
+                         "peak": MFMA_BF16_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / MFMA_BF16_PEAK_TFLOPS,
+                         "traffic": traffic, "traffic_source": traffic_src, "launches_timed": len(ev_ms), "ms_per_launch": attn_ms,
+                         "flop_per_launch": attn_flops}
     if parity is not None:
-        line["parity_check"] = parity
-    line["comm"] = comm
+        extra["parity_check"] = parity
+    extra["comm"] = comm
     if cross is not None:
-        line["cross_rank_check"] = cross
+        extra["cross_rank_check"] = cross
     if rank == 0:
         if not args.no_cpu_baseline:
             try:
-                line["cpu_baseline"] = cpu_baseline(seq, frames, fpt)
+                extra["cpu_baseline"] = cpu_baseline(seq, frames, fpt)
             except Exception as e:  # noqa: BLE001 — a reported baseline must not cost the measured line
-                line["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": torch.get_num_threads(), "kind": "port",
-                                        "sample": f"failed: {type(e).__name__}: {e}"}
+                extra["cpu_baseline"] = {"value": None, "unit": "tokens/s", "cores": torch.get_num_threads(), "kind": "port",
+                                         "sample": f"failed: {type(e).__name__}: {e}"}
         else:
-            line["cpu_baseline"] = None
-        print(json.dumps(line), flush=True)
-    if dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
+            extra["cpu_baseline"] = None
+    return extra
 
 
 if __name__ == "__main__":

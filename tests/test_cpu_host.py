@@ -902,9 +902,9 @@ def test_c_abi_compiles_and_validates_from_plain_c(tmp_path):
 def test_adaptor_stacks_on_top_of_the_references_adaptor():
     """INTEGRATION.md §1's order — `import long_vita_megatron.megatron_adaptor` (the reference patches Megatron through ITS manager),
     then `import long_vita_amd.megatron_adaptor` (this package patches the same dotted names through its own) — on the stand-in
-    Megatron tree (VERDICT r2 "missing" 5: two managers on the same names had no test).  The first manager is the reference's own
-    class when /root/reference is readable (M/patch_utils.py is stdlib-only, loaded from its file), else this package's class under
-    a second module name (pinned equal by patch_manager.pt); its replacements stand in for the reference's (same kinds: a `*_wrapper`
+    Megatron tree (VERDICT r2 "missing" 5: two managers on the same names had no test).  The first manager is this package's class
+    loaded under a second module name, standing in for the reference's M/patch_utils.py (the two are pinned equal by
+    patch_manager.pt, so the test needs nothing outside the repository); its replacements stand in for the reference's (same kinds: a `*_wrapper`
     for DotProductAttention.forward, outright replacements elsewhere, M/megatron_adaptor.py:21-22,81-106).  After the second
     adaptor every patched name resolves to THIS package's object — also in a module that imported the reference's replacement by
     name beforehand (identity propagation) — and the attention wrapper stacked on the reference's wrapper still routes to HIP."""
@@ -916,8 +916,7 @@ def test_adaptor_stacks_on_top_of_the_references_adaptor():
     from long_vita_amd.dot_product_attention import HipDotProductAttention
     from long_vita_amd.language_model_embedding import LanguageModelEmbedding
     from long_vita_amd.patch_utils import MindSpeedPatchesManager as aspm
-    ref_file = "/root/reference/long_vita_megatron/patch_utils.py"
-    src = ref_file if os.path.exists(ref_file) else os.path.join(ROOT, "long_vita_amd", "patch_utils.py")
+    src = os.path.join(ROOT, "long_vita_amd", "patch_utils.py")
     spec = importlib.util.spec_from_file_location("_first_manager_patch_utils", src)
     first = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(first)

@@ -222,7 +222,7 @@ def test_bench_dry_run_goes_through_the_distributed_plumbing():
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--dry-run"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--dry-run", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=500, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0"))
     assert r.returncode == 0, r.stdout + r.stderr
     import json
@@ -234,6 +234,33 @@ def test_bench_dry_run_goes_through_the_distributed_plumbing():
     assert comm["ranks"] == 1 and comm["backend"] == "nccl" and comm["isolated_all_gather_ms"] > 0 and comm["kv_messages_per_layer"] >= 1
 
 
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR` (without --full): the contract line and nothing measured
+    besides it, K timed steps, and the last step's logits in DIR/logits.npy — the same values from a second run with the same
+    arguments (seeded inputs and weights)."""
+    import json
+    import numpy as np
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):         # an earlier test's process group: not this run's
+        env.pop(k, None)
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "0", "--dry-run",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=500, env=env)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        line = json.loads(lines[0])
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["unit"] == "tokens/s" and line["dtype"] == "bf16"
+        assert not {"roofline", "comm", "parity_check", "cross_rank_check", "cpu_baseline"} & set(line), sorted(line)
+        logits = np.load(d / "logits.npy")
+        assert logits.dtype == np.float32 and logits.shape == (1, 152064) and np.isfinite(logits).all()
+        dumps.append(logits)
+    a, b = dumps
+    assert np.linalg.norm(a - b) <= 1e-3 * np.linalg.norm(b)
+
+
 def _bench_self_launched(extra_env):
     """`python bench.py --gpus 1 --dry-run` with NO launcher around it and VITA_BENCH_FORCE_SPAWN=1: the file starts its own rank under
     torch.distributed.run (what `--gpus N`, N > 1, does on a multi-GPU node) and relays the one line."""
@@ -241,7 +268,7 @@ def _bench_self_launched(extra_env):
     env = dict(os.environ, VITA_BENCH_FORCE_SPAWN="1", **extra_env)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--dry-run"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--dry-run", "--full"],
                        capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -282,7 +309,7 @@ def test_bench_n_processes_on_one_gpu_over_staged_gloo(n):
     env = dict(os.environ, VITA_BENCH_BACKEND="gloo-staged")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--dry-run"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "1", "--warmup", "1", "--dry-run", "--full"],
                        capture_output=True, text=True, timeout=1500, env=env)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

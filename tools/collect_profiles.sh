@@ -8,7 +8,7 @@ TAG=${1:-r05}
 OUT=gpurun_out
 mkdir -p $OUT
 export TMPDIR=/tmp
-python bench.py --steps 3 --warmup 1 > $OUT/${TAG}_bench128k_n1.json 2> $OUT/${TAG}_bench128k_n1.err
+python bench.py --full --steps 3 --warmup 1 > $OUT/${TAG}_bench128k_n1.json 2> $OUT/${TAG}_bench128k_n1.err
 tail -c 3000 $OUT/${TAG}_bench128k_n1.json
 rm -rf /tmp/prof_ks; (cd /tmp && rocprofv3 --kernel-trace --stats -d /tmp/prof_ks -o ks -- python $OLDPWD/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-parity-check > $OLDPWD/$OUT/${TAG}_bench128k_under_rocprof.json 2> /tmp/prof_ks.err)
 DB=$(find /tmp/prof_ks -name "*.db" | head -1)
@@ -26,7 +26,7 @@ python tools/microbench.py attn attn_bwd > /dev/null 2>&1; cp $OUT/microbench.js
 VITA_ATTN_BWD_KVP=0 python tools/microbench.py attn_bwd > /dev/null 2>&1; grep attn_bwd $OUT/microbench.jsonl | tail -6 | sed 's/"kind": "attn_bwd"/"kind": "attn_bwd", "VITA_ATTN_BWD_KVP": 0/' >> $OUT/${TAG}_attn_bwd_microbench.jsonl
 rm -f $OUT/microbench.jsonl
 python tools/microbench.py gemm peaks > /dev/null 2>&1; cp $OUT/microbench.jsonl $OUT/${TAG}_gemm.jsonl
-python bench.py --seq 16384 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench16k_n1.json 2> /dev/null; tail -c 600 $OUT/${TAG}_bench16k_n1.json
+python bench.py --full --seq 16384 --steps 5 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench16k_n1.json 2> /dev/null; tail -c 600 $OUT/${TAG}_bench16k_n1.json
 # roctx ranges (VITA_DEBUG): marker + kernel trace of a dry run
 rm -rf /tmp/prof_mk; (cd /tmp && VITA_DEBUG=1 rocprofv3 --marker-trace --kernel-trace --stats -d /tmp/prof_mk -o mk --output-format csv -- python $OLDPWD/bench.py --dry-run --steps 1 --warmup 0 --no-parity-check > /dev/null 2> /tmp/prof_mk.err)
 MK=$(find /tmp/prof_mk -name "*marker_api_trace.csv" | head -1); [ -n "$MK" ] && (head -1 $MK; grep -c . $MK; cut -d, -f1-4 $MK | sed -n 2,12p) > $OUT/${TAG}_roctx_ranges_dry_run.txt; cat $OUT/${TAG}_roctx_ranges_dry_run.txt 2>/dev/null | head -8; [ -z "$MK" ] && (find /tmp/prof_mk | head; tail -5 /tmp/prof_mk.err)
