@@ -29,7 +29,7 @@
 
 namespace {
 
-// developer aid (VITA_ATTN_VARIANT bit 2): per-phase shader-clock totals, [group A|B][top, qk, sm_pv, barrier, n]
+// per-phase shader-clock totals of a TIMING build, [group A|B][top, qk, sm_pv, barrier, n]
 __device__ unsigned long long g_attn_timing[16];
 constexpr int QTILE = 256;   // query rows per workgroup (8 waves x 32)
 constexpr int KVT = 64;      // keys per tile
@@ -74,7 +74,8 @@ struct TileIt {
   int64_t crow;       // first row of chunk c in the K/V buffers
 };
 
-// VARIANT (developer tuning aid, see attn_variant()):
+// VARIANT (libvita_hip.so builds 6: LDS-DMA with QK_AHEAD 3; the others and TIMING are not instantiated.  The parameters stay because
+// folding them out of the source changes the d = 64 instances' register allocation, which needs a same-box A / B of its own):
 //   0 = K/V tiles go HBM/L2 -> LDS directly with the LDS-DMA (global_load_lds_dwordx4); the DMA writes
 //       lane-linear, so the bank swizzles are applied to the per-lane SOURCE address (same involution
 //       on the fragment reads); no staging VGPRs, no ds_write burst behind the barrier;
@@ -468,60 +469,18 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
   }
 }
 
-template <int D, bool CAUSAL, int VARIANT, bool TIMING = false>
-int launch_attn_v(const AttnArgs& a, int64_t nblocks, hipStream_t st) {
+template <int D, bool CAUSAL>
+int launch_attn(const AttnArgs& a, int64_t nblocks, hipStream_t st) {
   constexpr int lds = 2 * 2 * KVT * D * 2;
   static std::atomic<unsigned long long> attr_set{0};
   vita_device_once(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd_kernel<D, CAUSAL, VARIANT, TIMING>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd_kernel<D, CAUSAL, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   });
-  hipLaunchKernelGGL((flash_fwd_kernel<D, CAUSAL, VARIANT, TIMING>), dim3((unsigned)nblocks), dim3(512), lds, st, a);
+  hipLaunchKernelGGL((flash_fwd_kernel<D, CAUSAL, 6>), dim3((unsigned)nblocks), dim3(512), lds, st, a);
   return vita_check_launch();
 }
 
-// VITA_ATTN_VARIANT (developer tuning aid): bits 0-3 = kernel VARIANT (default 6 = LDS-DMA + QK_AHEAD 3), bit 4 = phase timers.
-inline int attn_variant() {
-  static const int v = [] {
-    const char* e = vita_dev_getenv("VITA_ATTN_VARIANT");
-    return e ? atoi(e) : 6;
-  }();
-  return v;
-}
-
-template <int D, bool CAUSAL>
-int launch_attn(const AttnArgs& a, int64_t nblocks, hipStream_t st) {
-  const int v = attn_variant();
-  if constexpr (D == 96) {
-    return launch_attn_v<D, CAUSAL, 6>(a, nblocks, st);                           // LDS-DMA staging only (see the kernel's static_assert)
-  } else {
-    if ((v & 16) && D == 128 && CAUSAL) {
-      switch (v & 15) {
-        case 1: return launch_attn_v<128, true, 1, true>(a, nblocks, st);
-        case 0: return launch_attn_v<128, true, 0, true>(a, nblocks, st);
-        default: return launch_attn_v<128, true, 6, true>(a, nblocks, st);
-      }
-    }
-    switch (v & 15) {
-      case 1: return launch_attn_v<D, CAUSAL, 1>(a, nblocks, st);
-      case 0: return launch_attn_v<D, CAUSAL, 0>(a, nblocks, st);
-      default: return launch_attn_v<D, CAUSAL, 6>(a, nblocks, st);
-    }
-  }
-}
-
 }  // namespace
-
-// developer aid, not part of the public ABI: copy (and optionally clear) the phase timers
-extern "C" int vita_debug_attn_timing(unsigned long long* host_out16, int reset) {
-  if (host_out16 && hipMemcpyFromSymbol(host_out16, HIP_SYMBOL(g_attn_timing), 16 * sizeof(unsigned long long)) != hipSuccess)
-    return VITA_ERR_LAUNCH;
-  if (reset) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(g_attn_timing), z, sizeof(z)) != hipSuccess) return VITA_ERR_LAUNCH;
-  }
-  return VITA_OK;
-}
 
 // ---- merge of two attention partials over disjoint key sets (context parallelism: own chunks first, remote chunks after the gather)
 //   lse = log(exp(lse_a) + exp(lse_b)),  O = O_a exp(lse_a - lse) + O_b exp(lse_b - lse);  a part that saw no key has lse = -inf.

@@ -71,8 +71,8 @@ constexpr SlotMap make_map1() {
 // <= 32 rows (the ViT's 1025th token: one workgroup in five).  Its waves 1 .. 3 own no valid row and wave 0 only its first block; they all
 // take the same path (same barriers, same LDS-DMA shares) with half the MFMAs and half the softmax, and the workgroup leaves its CU in
 // ~55 % of the time.
-// NW = 4: 64 rows per wave (NQB = 2), one wave per SIMD — the shipped form.  NW = 8 (NQB = 1 only; developer switch VITA_ATTN64V=8):
-// eight waves x 32 rows, two waves per SIMD in 252 registers — built to test whether a second wave's issue slots help where a single wave
+// Four waves: 64 rows per wave (NQB = 2), one wave per SIMD.  The r05 alternative of eight waves x 32 rows, two waves per SIMD in 252
+// registers, was built to test whether a second wave's issue slots help where a single wave
 // cannot issue its ~13 instructions per MFMA inside the MFMA's 32 cycles.  They do not: 0.521 vs 0.477 ms.  SQ counters of the 4-wave
 // form at 253 frames (profiles/r05_vit_attn_pmc.txt): 11.1 VALU instructions per MFMA (attn64: 5.7), the wave issues 66 % of its cycles,
 // VALU active 53 %, matrix pipe busy 32 %, s_waitcnt / s_barrier 19.5 % — a deeper DMA ring (four slots, counted vmcnt: kept) did not
@@ -80,7 +80,7 @@ constexpr SlotMap make_map1() {
 // add, half a max3 and half a pack per score) costs more issue time than the 8 MFMAs per 32 x 32 score tile take: the kernel is bound by
 // VALU issue, and 0.85 PFLOP/s of MFMA work is out of reach for an fp32 softmax on this chip (16-lane SIMDs: 4 cycles per VALU
 // instruction; the r01 kernel, the 8-wave form and this one all land within 12 % of each other).
-template <int NQB, int NW>
+template <int NQB>
 __device__ __forceinline__ void fwd64v_body(const AttnArgs& p, const unsigned lds0, const int wave, const int lane, const int b, const int kvh,
                                             const int hq, const int qti) {
   const int hi = lane >> 5, l31 = lane & 31;
@@ -89,6 +89,7 @@ __device__ __forceinline__ void fwd64v_body(const AttnArgs& p, const unsigned ld
   // time — they share that head's K / V through the XCD's L2) ---------------------------------------------------------------------------
   const int G = p.n_q_heads / p.n_kv_heads;
   const int head = kvh * G + hq;
+  constexpr int NW = 4;                             // waves per workgroup
   constexpr int PW = 8 / NW;                        // 1 KiB LDS-DMA pieces of a K (or V) tile per wave
   const int q_off = qti * QTILE + wave * (QTILE / NW);   // this wave's first row
   const int q_last = p.q_valid - 1;
@@ -410,7 +411,6 @@ __device__ __forceinline__ void fwd64v_body(const AttnArgs& p, const unsigned ld
   }
 }
 
-template <int NW>
 __device__ __forceinline__ void fwd64v_entry(const AttnArgs& p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
@@ -423,16 +423,11 @@ __device__ __forceinline__ void fwd64v_entry(const AttnArgs& p) {
   const int n_qt = (p.q_valid + QTILE - 1) / QTILE;   // (one chunk: rows 0 .. q_valid - 1)
   const int qti = bid % n_qt;
   const int b = bid / n_qt;
-  if constexpr (NW == 8) {
-    fwd64v_body<1, 8>(p, lds0, wave, lane, b, kvh, hq, qti);
-  } else {
-    if (p.q_valid - qti * QTILE <= 32) fwd64v_body<1, 4>(p, lds0, wave, lane, b, kvh, hq, qti);
-    else fwd64v_body<2, 4>(p, lds0, wave, lane, b, kvh, hq, qti);
-  }
+  if (p.q_valid - qti * QTILE <= 32) fwd64v_body<1>(p, lds0, wave, lane, b, kvh, hq, qti);
+  else fwd64v_body<2>(p, lds0, wave, lane, b, kvh, hq, qti);
 }
 
-__global__ __launch_bounds__(256, 1) void flash_fwd64v_kernel(AttnArgs p) { fwd64v_entry<4>(p); }
-__global__ __launch_bounds__(512, 2) void flash_fwd64v8_kernel(AttnArgs p) { fwd64v_entry<8>(p); }
+__global__ __launch_bounds__(256, 1) void flash_fwd64v_kernel(AttnArgs p) { fwd64v_entry(p); }
 
 }  // namespace
 
@@ -451,13 +446,10 @@ int vita_attn64v_launch(const AttnArgs& a, hipStream_t st) {
   static std::atomic<unsigned long long> attr_set{0};
   vita_device_once(attr_set, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd64v_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd64v8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_TOTAL);
   });
   const int64_t nblocks = (int64_t)a.batch * a.n_q_heads * ((a.q_valid + QTILE - 1) / QTILE);
   if (nblocks > 0x7fffffff) return VITA_ERR_UNSUPPORTED;
   // measured (64 frames x 1025 tokens, 16 heads, same box): 4 waves x 64 rows 0.477 ms, 8 waves x 32 rows 0.521 ms, r01 kernel 0.543 ms
-  const char* e = vita_dev_getenv("VITA_ATTN64V");                                 // developer A / B switch: 8 = the 8-wave x 32-row form
-  if (e && e[0] == '8') hipLaunchKernelGGL(flash_fwd64v8_kernel, dim3((unsigned)nblocks), dim3(512), LDS_TOTAL, st, a);
-  else hipLaunchKernelGGL(flash_fwd64v_kernel, dim3((unsigned)nblocks), dim3(256), LDS_TOTAL, st, a);
+  hipLaunchKernelGGL(flash_fwd64v_kernel, dim3((unsigned)nblocks), dim3(256), LDS_TOTAL, st, a);
   return vita_check_launch();
 }

@@ -20,7 +20,7 @@
 // per slot — with S only one half ahead A's second group was VALU-bound and B idled at the barrier (5.75 ms at 16K), with two exp2 in
 // every other slot 5.5 ms, one per slot 5.3-5.4 ms.  Every group starts from fragments its predecessor read at slot 12 and the lse / delta of
 // a half are fetched a trip ahead, so no group waits for an LDS round trip before its first MFMA (that alone: +- 0: same-box A/B).
-// Timing-only ablations (KVP_ABL, same box, whole backward 8.84 ms): no barriers 8.90, no exp2 8.38, no softmax / dS arithmetic at all 7.9 —
+// Timing-only ablations (r04 developer builds with wrong results, same box, whole backward 8.84 ms): no barriers 8.90, no exp2 8.38, no softmax / dS arithmetic at all 7.9 —
 // the barriers are free, and what the arithmetic costs it costs in power, not in issue slots: 1.25 PFLOP/s executed without it is the
 // chip's ceiling for an LDS-fed MFMA stream on random data (MI355X_MICROARCH.md, DVFS; the forward runs 1.20-1.24).
 //
@@ -35,7 +35,7 @@
 //     diagonal, block NB - 1 - w from its diagonal UP to the last tile: at global step s every first-phase workgroup of the XCD reads
 //     tile (last - s / G, head s % G) and every second-phase workgroup tile (s / G - 1, head s % G) — two streams per XCD instead of 32.
 // Measured (16K, same box, dK + dV pass alone, best / median of 5): r04 5.20 / 5.45 ms -> 5.13 / 5.29 ms with 0.89 GB fetched per launch
-// (11 x less); the ceiling of ANY locality scheme — timing ablation KVP_ABL = 8, every tile index taken mod 64 so that all reads hit the
+// (11 x less); the ceiling of ANY locality scheme — a timing ablation with every tile index taken mod 64 so that all reads hit the
 // L2 — is 5.00 / 5.10 ms.  The 25 x re-reads of r04 cost 5 % of the pass, not more: the pass is bound by issue and power
 // (MI355X_MICROARCH.md, DVFS: the fifth back-to-back launch of the same kernel runs 11 % slower than the first), as r04 concluded.
 #include "attn_bwd_args.h"
@@ -48,22 +48,6 @@ constexpr int NRING = 4;                                // Q / dO tile images in
 constexpr int LDS_Q = 0, LDS_DO = NRING * TILEB, LDS_ST = 2 * NRING * TILEB, LDS_X = LDS_ST + NRING * 512, LDS_TOTAL = LDS_X + 2 * 2 * 4096;
 constexpr float LOG2E = 1.44269504088896340736f;
 constexpr int PF_NONE = 0, PF_FRAG = 1, PF_TR = 2;
-// timing-only ablations (WRONG results; never in libvita_hip.so): -DKVP_ABL=1 no barrier between the two trips of a tile, 2 no exp2,
-// 3 no barrier at all, 5 no softmax / dS arithmetic at all (MFMAs + LDS traffic only), 6 = 5 + 3, 7 every tile read from the SAME
-// addresses (tile 0 of head 0: every LDS-DMA after the first hits the XCD's L2 — the upper bound of what any re-ordering of the
-// workgroups for L2 locality could give — but also the same operand bits in every MFMA: less switching power, higher clock), 8 every tile
-// read from a 64-tile window of head 0 (tile index mod 64: 2 MB of DISTINCT random data that stays in the XCD's 4 MB L2)
-#ifndef KVP_ABL
-#define KVP_ABL 0
-#endif
-constexpr int ABL = KVP_ABL;
-#ifndef KVP_HAND_SPREAD
-#define KVP_HAND_SPREAD 1          // r06: three of the four hand-over stores of P behind MFMAs of the S group (0: all four in front of the pair barrier)
-#endif
-#ifndef KVP_DMA_SPREAD
-#define KVP_DMA_SPREAD 1
-#endif
-constexpr bool DMA_SPREAD = KVP_DMA_SPREAD != 0;       // (0: the nine pieces of a tile in a burst at the top of the iteration, for A / B builds)
 
 typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
 typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
@@ -148,7 +132,7 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
     if (wave == 1) vita_lds_dma4(vita_make_rsrc_uniform(p.delta + t.stat), (unsigned)(lane * 4), lds0 + LDS_ST + slot3 * 512 + 256);
   };
 
-  // the same tile one piece at a time (r05, KVP_DMA_SPREAD): piece i = 0 .. 3 Q line i, 4 .. 7 dO line i - 4, 8 the lse / delta row of waves
+  // the same tile one piece at a time (r05): piece i = 0 .. 3 Q line i, 4 .. 7 dO line i - 4, 8 the lse / delta row of waves
   // 0 / 1 — issued one per MFMA slot behind the first MFMAs of a trip instead of nine in a burst behind the barrier (attn64.hip r05)
   QTileIt it;                                            // the pipeline's cursor (described with the iteration below)
   int dma_slot3 = 0;
@@ -170,8 +154,8 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
   int64_t q_hstep = 0, do_hstep = 0, q_tstep = 0, do_tstep = 0;
   int st_hstep = 0, st_tstep = 0;
   auto setptr = [&](QTileIt& t) __attribute__((always_inline)) {    // chunk entry only: everything else is increments
-    const int64_t row = ABL == 7 ? 0 : (ABL == 8 ? (int64_t)(t.j & 63) * QT : (int64_t)t.c * p.chunk_len + (int64_t)t.j * QT);
-    const int hq = ABL == 7 || ABL == 8 ? 0 : t.hq;
+    const int64_t row = (int64_t)t.c * p.chunk_len + (int64_t)t.j * QT;
+    const int hq = t.hq;
     const int head = kvh * G + hq;
     t.qp = qbase + ((int64_t)hq * p.q_hs + row * p.q_rs) * 2;
     t.dop = (const char*)p.d_o + ((int64_t)head * p.do_hs + row * p.do_rs) * 2;
@@ -194,14 +178,13 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
   auto advance = [&](QTileIt& t) __attribute__((always_inline)) {
     t.hq += dir;
     if (t.hq >= 0 && t.hq < G) {                          // the next head of the same tile (G - 1 times out of G)
-      if (ABL != 7 && ABL != 8) { t.qp += q_hstep; t.dop += do_hstep; t.stat += st_hstep; }
+      t.qp += q_hstep; t.dop += do_hstep; t.stat += st_hstep;
       return;
     }
     t.hq = dir > 0 ? 0 : G - 1;
     t.j += dir;
     if (t.j >= t.jlo && t.j < q_tiles_per_chunk) {
-      if (ABL == 8) setptr(t);
-      else if (ABL != 7) { t.qp += q_tstep; t.dop += do_tstep; t.stat += st_tstep; }
+      t.qp += q_tstep; t.dop += do_tstep; t.stat += st_tstep;
       return;
     }
     t.c += dir;
@@ -233,7 +216,6 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
   auto load_stat = [&](unsigned st, int qh) __attribute__((always_inline)) { stat_fetch(st, qh); stat_finish(); };
   // A: P of pair e (kb = e >> 3, registers 2 (e & 7), +1) of buffer `par`, in place
   auto exp_pair = [&](int par, int e) __attribute__((always_inline)) {
-    if (ABL == 2 || ABL == 5 || ABL == 6) return;
     const int kb = e >> 3, r = 2 * (e & 7);
     xb[par][kb][r] = __builtin_amdgcn_exp2f(fmaf(xb[par][kb][r], scale_log2e, -rstat[r]));
     xb[par][kb][r + 1] = __builtin_amdgcn_exp2f(fmaf(xb[par][kb][r + 1], scale_log2e, -rstat[r + 1]));
@@ -241,19 +223,16 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
   // A: P of ONE element (el = 16 kb + r) — one transcendental per MFMA slot: two in one slot (r04 first form) took 40 cycles of issue
   // against the MFMA's 32 and left the next slot half empty (timing ablations: the softmax arithmetic cost 17 % of the kernel)
   auto exp_one = [&](int par, int el) __attribute__((always_inline)) {
-    if (ABL == 2 || ABL == 5 || ABL == 6) return;
     const int kb = el >> 4, r = el & 15;
     xb[par][kb][r] = __builtin_amdgcn_exp2f(fmaf(xb[par][kb][r], scale_log2e, -rstat[r]));
   };
   auto pack_pair = [&](int par, int e) __attribute__((always_inline)) {          // A: bf16 pair of P
     const int kb = e >> 3, pr = e & 7, r = 2 * pr;
-    if (ABL == 5 || ABL == 6) { pk[par][kb][pr >> 2][pr & 3] = __builtin_bit_cast(unsigned, xb[par][kb][r]); return; }
     pk[par][kb][pr >> 2][pr & 3] = pack_bf16x2(xb[par][kb][r], xb[par][kb][r + 1]);
     asm volatile("" :: "v"(pk[par][kb][pr >> 2][pr & 3]));                       // computed HERE (no sinking past the phase)
   };
   auto ds_pair = [&](int par, int e) __attribute__((always_inline)) {            // B: dS = P o (dP scale - delta scale), packed
     const int kb = e >> 3, pr = e & 7, r = 2 * pr;
-    if (ABL == 5 || ABL == 6) { pk[par][kb][pr >> 2][pr & 3] = pin[kb][pr >> 2][pr & 3] ^ __builtin_bit_cast(unsigned, xb[par][kb][r]); return; }
     const unsigned w = pin[kb][pr >> 2][pr & 3];
     const float a = bf16lo_to_f32(w) * fmaf(xb[par][kb][r], scale, -rstat[r]);
     const float b = bf16hi_to_f32(w) * fmaf(xb[par][kb][r + 1], scale, -rstat[r + 1]);
@@ -269,7 +248,7 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
         *(lds_u32x4*)(uintptr_t)(xaddr + par * 8192 + (kb * 2 + t2) * 1024) = w;
       }
   };
-  // r06 (KVP_HAND_SPREAD): one of the four 16-byte stores of a hand-over.  Issued back to back in front of the pair barrier, the four stores of
+  // r06: one of the four 16-byte stores of a hand-over.  Issued back to back in front of the pair barrier, the four stores of
   // the two A waves fill the LDS data FIFO (SQ_LDS_DATA_FIFO_FULL 2.4e7 per 16K launch: a ds_write_b128 moves 5 source dwords at 2 cycles each)
   // and the wave stalls with the matrix pipe draining; three of them now go out behind MFMAs of the S group, as soon as their pairs are packed
   auto hand_over_part = [&](int par, int i) __attribute__((always_inline)) {
@@ -323,9 +302,7 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
       const int ds = s >> 1, kb = s & 1;
-      if (KVP_DMA_SPREAD == 1 && dma && s >= 1 && s <= 9) dma_tile_piece(it, s - 1);
-      if (KVP_DMA_SPREAD == 2 && dma && (s & 1)) dma_tile_piece(it, s >> 1);
-      if (KVP_DMA_SPREAD == 2 && dma && s == 14) dma_tile_piece(it, 8);
+      if (dma && s >= 1 && s <= 9) dma_tile_piece(it, s - 1);
       if (kb == 0 && ds + 2 < 8) fr[(ds + 2) & 3] = frag(img, ds + 2, qh_n);
       if (s == 12) { prefetch(pf, pf_img, pf_qh); if (pf_stat) stat_fetch(pf_st, pf_st_qh); }
       if (ds == 0) {
@@ -346,7 +323,7 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
         exp_one(par, 16 + s);
         if (s >= 2 && (s & 1) == 0) pack_pair(par, 8 + ((s - 2) >> 1));
         // pairs 0 .. 7 were packed under the previous group, pairs 8 .. 11 by slot 8
-        if (KVP_HAND_SPREAD && hand) {
+        if (hand) {
           if (s == 1) hand_over_part(par, 0);
           if (s == 5) hand_over_part(par, 1);
           if (s == 11) hand_over_part(par, 2);
@@ -356,7 +333,7 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
     }
     if (!ROLE_B && fill) {
       pack_pair(par, 15);
-      if (KVP_HAND_SPREAD && hand) hand_over_part(par, 3);
+      if (hand) hand_over_part(par, 3);
     }
   };
   // 16 slots: gradient^T += X^T(half qh of the image at `img`, transposed reads) packed(par)   (A: dV^T += dO^T P, B: dK^T += Q^T dS);
@@ -370,9 +347,7 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
       const int i = s >> 1, kb = s & 1, t2 = i >> 2, db = i & 3;
-      if (KVP_DMA_SPREAD == 1 && dma && s >= 1 && s <= 9) dma_tile_piece(it, s - 1);
-      if (KVP_DMA_SPREAD == 2 && dma && (s & 1)) dma_tile_piece(it, s >> 1);
-      if (KVP_DMA_SPREAD == 2 && dma && s == 14) dma_tile_piece(it, 8);
+      if (dma && s >= 1 && s <= 9) dma_tile_piece(it, s - 1);
       if (kb == 0 && i + 2 < 8) tr[(i + 2) & 3] = tr_frag(img, 2 * qh + ((i + 2) >> 2), (i + 2) & 3);
       if (s == 12) { prefetch(pf, pf_img, pf_qh); if (pf_stat) stat_fetch(pf_st, pf_st_qh); }
       const u32x4 pw = {pk[par][kb][t2][0], pk[par][kb][t2][1], pk[par][kb][t2][2], pk[par][kb][t2][3]};
@@ -395,7 +370,6 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
   };
   auto pair_barrier = [&]() __attribute__((always_inline)) {       // LDS hand-over visible to the partner (whole workgroup: one barrier kind)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    if (ABL == 3 || ABL == 6) return;
     __builtin_amdgcn_s_barrier();
   };
 
@@ -415,8 +389,7 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
   // the longer ring is kept for the context-parallel case, where a tile of a remote chunk may come from further away.
   auto iteration = [&](const bool has1, const bool has3) __attribute__((always_inline)) {
     int m_nx3 = -1;
-    if (DMA_SPREAD) dma_slot3 = s3n3;
-    else if (has3) dma_tile(it, s3n3);                   // tile t + 3 -> the slot that held tile t - 1 (last read before the previous tile barrier)
+    dma_slot3 = s3n3;                                    // tile t + 3 -> the slot that held tile t - 1 (last read before the previous tile barrier)
     // the cursor's own step (compares, 64-bit adds, two branches: ~15 scalar instructions, more at a chunk boundary) goes BEHIND the first
     // 16-MFMA group of the trip, where the matrix pipe is still draining: at the top of the trip — straight after the barrier, in all four
     // waves at once — it sat on the critical path of every tile (r05 first form: + 5 % SQ_WAVE_CYCLES)
@@ -447,10 +420,10 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
 #pragma unroll
         for (int e = 8; e < 16; ++e) pack_pair(1, e);
       }
-      if (!(KVP_HAND_SPREAD && has1)) hand_over(1);      // P(u + 1) -> the partner, before the barrier that ends this trip
+      if (!has1) hand_over(1);      // P(u + 1) -> the partner, before the barrier that ends this trip
       if (has1 && m_nx1 >= 0) mask_half(0, m_nx1);                                       // wave-uniform, diagonal tiles only
     }
-    if (ABL != 1) pair_barrier();
+    pair_barrier();
     // ---- trip 1: half u = (tile t, rows 32 ..) in buffers 1; u + 1, u + 2 = the two halves of tile t + 1 if has1 ---------------------------
     if (ROLE_B) {
       take_over(1);
@@ -468,7 +441,6 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
       g_group(1, g_cur, 1, has1, true, has1 ? PF_FRAG : PF_NONE, x_nxt, 1, false, 0, 0);
       if (has1) {
         x_group(0, x_nxt, 1, true, true, PF_TR, g_nxt, 0, true, st_nxt, 1, false, true);         // S(u + 2) -> buffers 1; next: trip 0 of tile t + 1
-        if (!KVP_HAND_SPREAD) hand_over(0);
         if (m_nx1 >= 0) mask_half(1, m_nx1 + 32);
       }
     }
@@ -480,7 +452,7 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    if (ABL != 3 && ABL != 6) __syncthreads();
+    __syncthreads();
     m_cur = m_nx1; m_nx1 = m_nx2; m_nx2 = m_nx3;
     const int tmp = s3; s3 = s3n; s3n = s3nn; s3nn = s3n3; s3n3 = tmp;
   };

@@ -202,7 +202,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& p, f32x16 (&acc)[N
 //   <128,128,2,2>: 4 waves, 64 KiB LDS, 2 workgroups per CU (small / ragged problems)
 //   <256,256,2,4>: 8 waves, 128 KiB LDS, per-wave tile 128 x 64 -> 0.75 LDS fragment reads and
 //                  0.25 KiB of DMA per MFMA instead of 1.0 / 0.5 (the 128^2 tile is LDS-bound)
-template <int EPI, int BM, int BN, int WM, int WN, bool PIN = true>
+template <int EPI, int BM, int BN, int WM, int WN>
 __global__ __launch_bounds__(64 * WM * WN, (BM == 256 && WM * WN == 4) ? 1 : 2) void gemm_bf16_kernel(GemmArgs p) {
   constexpr int NW = WM * WN;
   constexpr int TM = BM / WM, TN = BN / WN;          // per-wave tile
@@ -341,22 +341,20 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 256 && WM * WN == 4) ? 1 : 2) 
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi)
           acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kk][ni], af[kk][mi], acc[ni][mi], 0, 0, 0);
-    if (PIN) {
-      // issue order: fragments of k-step s+1 are read while the MFMAs of k-step s run
-      constexpr int NF = MI + NI, NM = MI * NI;
-      __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
+    // issue order: fragments of k-step s+1 are read while the MFMAs of k-step s run
+    constexpr int NF = MI + NI, NM = MI * NI;
+    __builtin_amdgcn_sched_group_barrier(0x100, NF, 0);
 #pragma unroll
-      for (int kk = 0; kk < 4; ++kk) {
-        if (kk < 3) {
+    for (int kk = 0; kk < 4; ++kk) {
+      if (kk < 3) {
 #pragma unroll
-          for (int i = 0; i < NF; ++i) {
-            if (i < NM) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
-          if (NM > NF) __builtin_amdgcn_sched_group_barrier(0x008, NM - NF, 0);
-        } else {
-          __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
+        for (int i = 0; i < NF; ++i) {
+          if (i < NM) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
+        if (NM > NF) __builtin_amdgcn_sched_group_barrier(0x008, NM - NF, 0);
+      } else {
+        __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -364,180 +362,6 @@ __global__ __launch_bounds__(64 * WM * WN, (BM == 256 && WM * WN == 4) ? 1 : 2) 
   }
 
   gemm_epilogue<EPI, MI, NI, TM, TN>(p, acc, m0, n0, wm, wn, lane);
-}
-
-// ---- 4 waves x (128 x 128): one wave per SIMD, operands HBM/L2 -> VGPR -> LDS ------------------------------------------
-// Per MFMA this geometry moves 0.5 KiB of fragment reads + 0.25 KiB of staging writes through the LDS port (the 8-wave
-// kernel above: 0.75 + 0.25), and the port is what bounds these kernels.  With one wave per SIMD nothing hides a stall,
-// so program order is the issue order (sched_group_barrier pins the MFMAs between the memory instructions):
-// (slot plan above the main loop).
-// MODE (measurement only, EPI 0; results are wrong for MODE > 0): 1 = every K tile re-reads tile 0 (all loads hit L1/L2),
-// 2 = no global loads / LDS writes, 3 = no fragment reads either (MFMA stream only) — the ablation ladder in DESIGN.md §4.2
-template <int EPI, int MODE = 0>
-__global__ __launch_bounds__(256, 1) void gemm4_kernel(GemmArgs p) {
-  constexpr int BM = 256, BN = 256, WN = 2, TM = 128, TN = 128, MI = 4, NI = 4;
-  constexpr int A_BYTES = BM * BK * 2, W_BYTES = BN * BK * 2, STAGE = A_BYTES + W_BYTES;
-  constexpr int QA = 8, QW = 8, NP = QA + QW, NF = MI + NI, NM = MI * NI;
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WN, wn = wave % WN;
-
-  constexpr bool SPLITK = EPI == VITA_EPI_F32_PARTIAL;
-  const int nwg = p.tiles_m * p.tiles_n * (SPLITK ? p.splits : 1);
-  int pid;
-  {
-    const int bid = blockIdx.x, xcd = bid & 7, q = nwg >> 3, r = nwg & 7;
-    pid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  // split-K: the split is the SLOW index, so that the workgroups an XCD runs side by side are tiles of one K range sharing operand panels
-  const int split = SPLITK ? pid / (p.tiles_m * p.tiles_n) : 0;
-  if (SPLITK) pid -= split * (p.tiles_m * p.tiles_n);
-  constexpr int GROUP_M = 4;
-  const int per_group = GROUP_M * p.tiles_n;
-  const int group = pid / per_group;
-  const int first_m = group * GROUP_M;
-  const int gsz = min(p.tiles_m - first_m, GROUP_M);
-  const int in_group = pid - group * per_group;
-  const int tm = first_m + in_group % gsz;
-  const int tn = in_group / gsz;
-  const int64_t m0 = (int64_t)tm * BM;
-  const int64_t n0 = (int64_t)tn * (EPI == VITA_EPI_SWIGLU ? BN / 2 : BN);
-
-  // piece j of a wave = 8 tile rows x 128 B: lane -> (row (wave*8 + j)*8 + lane/8, 16-B slot lane&7), stored swizzled
-  const bf16_t* src[NP];
-  unsigned dst[NP];
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const bool isw = j >= QA;
-    const int lr = (wave * 8 + (isw ? j - QA : j)) * 8 + (lane >> 3);
-    int64_t g;
-    if (!isw) {
-      g = m0 + lr;
-      g = g < p.M ? g : p.M - 1;
-      src[j] = p.A + g * p.lda + (lane & 7) * 8;
-    } else {
-      if (EPI == VITA_EPI_SWIGLU) {
-        const int blk = lr >> 5;
-        int64_t oc = n0 + (blk >> 1) * 32 + (lr & 31);
-        oc = oc < p.N ? oc : p.N - 1;
-        g = ((blk & 1) ? p.N : 0) + oc;
-      } else {
-        g = n0 + lr;
-        g = g < p.N ? g : p.N - 1;
-      }
-      src[j] = p.W + g * p.ldw + (lane & 7) * 8;
-    }
-    dst[j] = (isw ? A_BYTES : 0) + tile_off(lr, lane & 7);
-  }
-  unsigned fa[4], fw[4];
-#pragma unroll
-  for (int kk = 0; kk < 4; ++kk) {
-    fa[kk] = tile_off(wm * TM + (lane & 31), kk * 2 + (lane >> 5));
-    fw[kk] = A_BYTES + tile_off(wn * TN + (lane & 31), kk * 2 + (lane >> 5));
-  }
-  f32x16 acc[NI][MI];
-#pragma unroll
-  for (int i = 0; i < NI; ++i)
-#pragma unroll
-    for (int j = 0; j < MI; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  const int nk = (int)(p.K / BK);
-  u32x4 g[NP];
-  bf16x8 af[2][MI], wf[2][NI];
-  auto read_frag = [&](unsigned base, int kk, int set, int i) __attribute__((always_inline)) {
-    if (i == 0) wf[set][0] = *(lds_bf16x8*)(uintptr_t)(base + fw[kk]);
-    else if (i <= MI) af[set][i - 1] = *(lds_bf16x8*)(uintptr_t)(base + fa[kk] + (i - 1) * 32 * 128);
-    else wf[set][i - MI] = *(lds_bf16x8*)(uintptr_t)(base + fw[kk] + (i - MI) * 32 * 128);
-  };
-  // prologue: tile 0 -> stage 0, tile 1 -> registers, first fragments
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    g[j] = *(const u32x4*)src[j];
-    src[j] += (nk > 1 && MODE == 0) ? BK : 0;
-  }
-#pragma unroll
-  for (int j = 0; j < NP; ++j) *(__attribute__((address_space(3))) u32x4*)(uintptr_t)(lds0 + dst[j]) = g[j];
-  __syncthreads();
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    g[j] = *(const u32x4*)src[j];
-    src[j] += (nk > 2 && MODE == 0) ? BK : 0;
-  }
-#pragma unroll
-  for (int i = 0; i < NF; ++i) read_frag(lds0, 0, 0, i);
-  if (MODE == 3) {
-#pragma unroll
-    for (int i = 0; i < NF; ++i) read_frag(lds0, 1, 1, i);
-  }
-
-  // Every MFMA has exactly one memory instruction behind it (64 + 64 per K tile):
-  //   positions 0..7 of k-steps 0..2 : fragment reads of the next k-step
-  //   positions 8..15 of k-steps 0, 1 : ds_write_b128 of tile t+1 (in registers since the previous iteration) -> other stage
-  //   positions 8..15 of k-step 2, 0..7 of k-step 3 : global_load_dwordx4 of tile t+2
-  //   position 8 of k-step 3        : lgkmcnt(0) + s_barrier (no vmcnt: the loads just issued stay in flight)
-  //   positions 8..15 of k-step 3   : first fragment reads of tile t+1
-  for (int t = 0; t < nk; ++t) {
-    const unsigned cur = lds0 + (t & 1) * STAGE, nxt = lds0 + ((t + 1) & 1) * STAGE;
-    const int adv = (MODE == 0 && t + 3 < nk) ? BK : 0;   // the pointers stop at the last K tile (re-staged, never read)
-#pragma unroll
-    for (int kk = 0; kk < 4; ++kk) {
-#pragma unroll
-      for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi) {
-          const int i = ni * MI + mi;
-          if (kk == 3 && i == NM / 2) {
-            __builtin_amdgcn_sched_barrier(0);
-            asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          acc[ni][mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[kk & 1][ni], af[kk & 1][mi], acc[ni][mi], 0, 0, 0);
-          if (kk == 3 && i >= NM / 2) __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-          else __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          if (MODE < 3 && kk < 3 && i < NF) {
-            read_frag(cur, kk + 1, (kk + 1) & 1, i);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-          }
-          if (MODE < 3 && kk == 3 && i >= NM / 2) {
-            read_frag(nxt, 0, 0, i - NM / 2);
-            __builtin_amdgcn_sched_group_barrier(0x100, 1, 1);
-          }
-          if (MODE >= 2) continue;
-          if (kk < 2 && i >= NM / 2) {
-            const int j = kk * 8 + i - NM / 2;
-            *(__attribute__((address_space(3))) u32x4*)(uintptr_t)(nxt + dst[j]) = g[j];
-            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-          }
-          if ((kk == 2 && i >= NM / 2) || (kk == 3 && i < NM / 2)) {
-            const int j = kk == 2 ? i - NM / 2 : 8 + i;
-            g[j] = *(const u32x4*)src[j];
-            src[j] += adv;
-            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-          }
-        }
-    }
-  }
-  gemm_epilogue<EPI, MI, NI, TM, TN>(p, acc, m0, n0, wm, wn, lane);
-}
-
-template <int EPI, int MODE = 0>
-int launch_gemm4(GemmArgs a, hipStream_t st) {
-  constexpr int lds = 2 * (256 + 256) * BK * 2;
-  const int64_t tm = (a.M + 255) / 256;
-  const int64_t bn_out = EPI == VITA_EPI_SWIGLU ? 128 : 256;
-  const int64_t tn = (a.N + bn_out - 1) / bn_out;
-  if (tm * tn > 0x7fffffff) return VITA_ERR_UNSUPPORTED;
-  a.tiles_m = (int)tm; a.tiles_n = (int)tn;
-  static std::atomic<unsigned long long> attr_set{0};
-  vita_device_once(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm4_kernel<EPI, MODE>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-  });
-  hipLaunchKernelGGL((gemm4_kernel<EPI, MODE>), dim3((unsigned)(tm * tn)), dim3(256), lds, st, a);
-  return vita_check_launch();
 }
 
 // ---- 4 waves x (128 x 128), v_mfma_f32_16x16x32_bf16, accumulators pinned in AGPRs: the large-problem kernel (round 2) ------------
@@ -553,7 +377,8 @@ int launch_gemm4(GemmArgs a, hipStream_t st) {
 //     holds its second-half fragments (barrier in the first half of the iteration), so a piece has about 1.5 iterations to land;
 //   * the loop is one fixed instruction order (asm volatile statements + sched_barrier): MFMA slots 0..127, a fragment read behind
 //     every second MFMA of slots 0..30, lgkmcnt(0) + s_barrier at 36, one DMA piece every fourth slot 40..100 (a burst costs 6 %),
-//     vmcnt + s_barrier at 103, the next tile's 16 first-half reads behind slots 104..119.
+//     vmcnt + s_barrier at 63, the next tile's 16 first-half reads behind every second slot 64..94 — the two-barrier schedule that
+//     fc1 + SwiGLU and the NN mode run; the other modes run the operand-split schedule (r06, gemm_w4_tile).
 // Ragged M / N: source rows are clamped (their products land in rows / columns the epilogue does not store).
 template <int B, int E, class F>
 __device__ __forceinline__ void static_for(F& f) {            // f(std::integral_constant<int, B>) ... f(<E - 1>), in order
@@ -564,31 +389,30 @@ __device__ __forceinline__ void static_for(F& f) {            // f(std::integral
 }
 namespace w4 {
 constexpr int LINE = 1040, HALF = 16 * LINE, OPB = 2 * HALF, STAGE = 2 * OPB, LDS_BYTES = 2 * STAGE;   // 133120 B
-// the operand-split schedule's LDS-DMA slots: piece j (0 .. 7: A lines, 8 .. 15: W lines) is issued behind MFMA slot PIECE_SLOT[variant][j];
-// A pieces need slot > 21 (barrier 1), W pieces slot > 51 (barrier 2).  Variant 0: the vendor kernel's positions (three bursts of five, every
-// third slot); variant 1: the same window, evenly spaced (every 6 - 7 slots).
-constexpr int PIECE_SLOT[2][16] = {{22, 25, 28, 31, 34, 52, 55, 58, 61, 64, 85, 87, 89, 96, 100, 124},
-                                   {22, 28, 34, 40, 46, 52, 58, 65, 71, 78, 84, 91, 97, 104, 110, 117}};
-constexpr int piece_at(int variant, int slot) {
-  for (int j = 0; j < 16; ++j) if (PIECE_SLOT[variant][j] == slot) return j;
+// the operand-split schedule's LDS-DMA slots: piece j (0 .. 7: A lines, 8 .. 15: W lines) is issued behind MFMA slot PIECE_SLOT[j]; A pieces
+// need slot > 21 (barrier 1), W pieces slot > 51 (barrier 2).  The vendor kernel's positions: three bursts of five, every third slot (the same
+// window evenly spaced, every 6 - 7 slots, was a same-box A / B of r06).
+constexpr int PIECE_SLOT[16] = {22, 25, 28, 31, 34, 52, 55, 58, 61, 64, 85, 87, 89, 96, 100, 124};
+constexpr int piece_at(int slot) {
+  for (int j = 0; j < 16; ++j) if (PIECE_SLOT[j] == slot) return j;
   return -1;
 }
-constexpr int pieces_before(int variant, int slot) {
+constexpr int pieces_before(int slot) {
   int n = 0;
-  for (int j = 0; j < 16; ++j) n += PIECE_SLOT[variant][j] < slot;
+  for (int j = 0; j < 16; ++j) n += PIECE_SLOT[j] < slot;
   return n;
 }
-// what the schedule relies on: A pieces (0 .. 7) behind barrier 1 (slot 21), W pieces (8 .. 15) behind barrier 2 (slot 51), increasing slots (the
-// vmcnt of barrier 3 counts the pieces in front of it), and room for the three slots a staggered wave adds
-constexpr bool piece_table_ok(int variant) {
+// what the schedule relies on: A pieces (0 .. 7) behind barrier 1 (slot 21), W pieces (8 .. 15) behind barrier 2 (slot 51), slots inside the
+// tile and increasing (the vmcnt of barrier 3 counts the pieces in front of it)
+constexpr bool piece_table_ok() {
   for (int j = 0; j < 16; ++j) {
-    const int sl = PIECE_SLOT[variant][j];
-    if (sl <= (j < 8 ? 21 : 51) || sl + 3 > 127) return false;
-    if (j > 0 && sl <= PIECE_SLOT[variant][j - 1]) return false;
+    const int sl = PIECE_SLOT[j];
+    if (sl <= (j < 8 ? 21 : 51) || sl > 127) return false;
+    if (j > 0 && sl <= PIECE_SLOT[j - 1]) return false;
   }
   return true;
 }
-static_assert(piece_table_ok(0) && piece_table_ok(1), "LDS-DMA piece slots of the operand-split schedule");
+static_assert(piece_table_ok(), "LDS-DMA piece slots of the operand-split schedule");
 }
 
 // INTERIOR = every tile of the problem is whole (M % 256 == 0, N % tile width == 0): chosen at launch, so that each instantiation has
@@ -607,40 +431,15 @@ static_assert(piece_table_ok(0) && piece_table_ok(1), "LDS-DMA piece slots of th
 // OPM = 2 (r04, vita_gemm_bf16_nn): A as in the NT kernel ([M][K], row-major), W contraction-major ([K][N]) as in the TN kernel —
 // C = A W, which is what an input gradient is (dX [tokens, K_in] = dY [tokens, N] W [N, K_in] with the weight as the forward holds it),
 // so dgrad needs no vita_transpose_bf16 pass over the weight either.  A's half of a stage is the NT image, W's half the TN image.
-#ifndef VITA_GEMM_EARLY_NEXT
-#define VITA_GEMM_EARLY_NEXT 1
-#endif
-#ifndef VITA_GEMM_DMA_STEP
-#define VITA_GEMM_DMA_STEP 4       // two-barrier schedule: one LDS-DMA piece every DMA_STEP slots from slot 40 on (5: a same-box A / B of the window's width alone)
-#endif
-#ifndef VITA_GEMM_DMA_STEP_OTHER
-#define VITA_GEMM_DMA_STEP_OTHER 5 // the TN / NN / split-K modes (weight and input gradients): one piece every DMA_STEP_OTHER slots from slot 40 on
-#endif
-#ifndef VITA_GEMM_RD_STEP
-#define VITA_GEMM_RD_STEP 2        // two-barrier schedule: 1 = the 16 second-half reads in consecutive slots, barrier 1 at slot 20, pieces from slot 22
-#endif
-#ifndef VITA_GEMM_SPLIT_TN
-#define VITA_GEMM_SPLIT_TN 1       // the operand-split schedule in the TN mode (weight gradients, also split-K) too: -1 to -2.4 % same box; NN (input gradients) measured +0.3 to +1 % with it and keeps two barriers
-#endif
-#ifndef VITA_GEMM_WAVE_STAGGER
-#define VITA_GEMM_WAVE_STAGGER 0   // 1: the operand-split loop in four copies, wave w's LDS-DMA pieces w slots behind the table (same-box A / B)
-#endif
-#ifndef VITA_GEMM_SWIGLU_STEP5
-#define VITA_GEMM_SWIGLU_STEP5 1    // 1: fc1 + SwiGLU keeps the two-barrier schedule, with one piece every 5 slots (the variant it measured best with)
-#endif
-#ifndef VITA_GEMM_SCHED
-#define VITA_GEMM_SCHED 1          // 1: operand-split release of the stage, three barriers (r06); 0: the r05 two-barrier schedule (same-box A / B builds)
-#endif
 template <int EPI, bool INTERIOR, int OPM>
 __device__ __forceinline__ void gemm_w4_tile(const GemmArgs& p, const int bid_) {
   using namespace w4;
-  constexpr bool EARLY_NEXT = VITA_GEMM_EARLY_NEXT != 0;
-  // two-barrier schedule, NT one-pass kernels only (the other modes keep the r05 positions): reads of the second-half fragments every RD_STEP
-  // slots from slot 0, barrier 1 at BAR1, one LDS-DMA piece every DMA_STEP slots from DMA0
-  constexpr bool TUNED = OPM == 0 && EPI != VITA_EPI_F32_PARTIAL;
-  constexpr int DMA_STEP = TUNED ? ((VITA_GEMM_SWIGLU_STEP5 && EPI == VITA_EPI_SWIGLU) ? 5 : VITA_GEMM_DMA_STEP) : VITA_GEMM_DMA_STEP_OTHER, RD_STEP = TUNED ? VITA_GEMM_RD_STEP : 2;
-  constexpr int BAR1 = RD_STEP == 2 ? 36 : 20, DMA0 = RD_STEP == 2 ? 40 : 22;
-  static_assert(DMA0 + 15 * DMA_STEP < 128 && (RD_STEP == 1 || RD_STEP == 2), "pieces must fit the tile");      // (0: the r02 - r04 placement, kept for same-box A / B builds)
+  // two-barrier schedule: reads of the second-half fragments every other slot from slot 0, barrier 1 at BAR1, one LDS-DMA piece every DMA_STEP
+  // slots from DMA0 — every 4th in the NT mode, every 5th for fc1 + SwiGLU (the step it measured best with) and in the TN / NN / split-K modes
+  // (weight and input gradients); 5 for the NT mode alone was a same-box A / B of the window's width
+  constexpr int DMA_STEP = (OPM == 0 && EPI != VITA_EPI_F32_PARTIAL && EPI != VITA_EPI_SWIGLU) ? 4 : 5;
+  constexpr int BAR1 = 36, DMA0 = 40;
+  static_assert(DMA0 + 15 * DMA_STEP < 128, "pieces must fit the tile");
   constexpr bool TN = OPM == 1, TA = OPM == 1, TW = OPM != 0;          // TN: both operands contraction-major; TA / TW: per operand
   constexpr int STG = TN ? 65536 : STAGE, OPBS = TA ? 32768 : OPB;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -824,7 +623,7 @@ __device__ __forceinline__ void gemm_w4_tile(const GemmArgs& p, const int bid_) 
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   frag_commit(0);
 
-  // ---- r06: the operand-split schedule (VITA_GEMM_SCHED 1; NT mode, one pass over K).  The 2-barrier schedule below frees `cur` for the DMA of
+  // ---- r06: the operand-split schedule (NT mode with one pass over K, TN mode and split-K; not fc1 + SwiGLU, not NN).  The 2-barrier schedule below frees `cur` for the DMA of
   // tile t + 2 only once ALL 16 second-half fragments are in registers (slot 36), which squeezes the 16 pieces of a tile — 64 KiB per CU — into
   // slots 40 .. 100.  Here the stage is released one OPERAND at a time: the eight second-half A fragments are read first (slots 0 .. 14; their
   // first-half twins were read in the previous tile's tail), a barrier at slot 21 frees A's half of the stage and A's pieces start at slot 22; the W
@@ -832,11 +631,10 @@ __device__ __forceinline__ void gemm_w4_tile(const GemmArgs& p, const int bid_) 
   // vmcnt(13) — the 13 pieces of tile t + 2 issued by then stay in flight — and tile t + 1's first-half fragments are read in slots 93 .. 123.
   // The pieces go out in three bursts of five (every third slot) with 18 .. 21 slots of nothing between them, over slots 22 .. 124: the slot
   // positions are the ones the vendor library's MT256x256x64 kernel uses (read off its disassembly: profiles/r06_gemm_schedules.txt).
-  constexpr bool SPLIT_SCHED = VITA_GEMM_SCHED >= 1 && ((OPM == 0 && !SPLITK) || (VITA_GEMM_SPLIT_TN && OPM == 1)) && !(VITA_GEMM_SWIGLU_STEP5 && EPI == VITA_EPI_SWIGLU);
-  constexpr int SPLIT_VARIANT = VITA_GEMM_SCHED >= 2 ? 1 : 0;
-  constexpr bool PACED_READS = VITA_GEMM_SCHED >= 3;       // 3: fragment reads every other slot (the two-barrier schedule's pace) instead of the vendor's positions
-  auto tile_split = [&](auto W_, const bool DMA, const bool NEXT, unsigned cur, unsigned nxt) __attribute__((always_inline)) {
-    constexpr int WOFF = decltype(W_)::value;      // VITA_GEMM_WAVE_STAGGER: this wave's pieces go out WOFF slots behind the table's positions
+  // The TN mode (weight gradients, also split-K) measured -1 to -2.4 % same box with it; NN (input gradients) +0.3 to +1 %, and fc1 + SwiGLU
+  // measured best on the two-barrier schedule: both keep that one.
+  constexpr bool SPLIT_SCHED = ((OPM == 0 && !SPLITK) || OPM == 1) && EPI != VITA_EPI_SWIGLU;
+  auto tile_split = [&](const bool DMA, const bool NEXT, unsigned cur, unsigned nxt) __attribute__((always_inline)) {
     const StageBases bcur = bases_of(cur), bnxt = bases_of(NEXT ? nxt : cur);
     // (the slot number is a template constant — std::integral_constant through a generic lambda — so that every fragment / piece index below is a
     // constant expression: the "i" operands of the fragment reads need that, and a run-time `s` left them to the unroller's mercy)
@@ -846,42 +644,31 @@ __device__ __forceinline__ void gemm_w4_tile(const GemmArgs& p, const int bid_) 
       asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[nb][mb]) : "v"(wf[ks][nb]), "v"(af[ks][mb]));
       // second-half fragments of `cur`: A blocks 0 .. 7 (q = 1 .. 8), then W blocks 0 .. 7 (q = 0, 9 .. 15)
       if constexpr (s <= 14 && (s & 1) == 0) frag_read(bcur, 1, 1 + (s >> 1));
-      if constexpr (!PACED_READS) {
-        if constexpr (s == 24) frag_read(bcur, 1, 0);
-        if constexpr (s == 27 || s == 30 || s == 33 || s == 36) frag_read(bcur, 1, 9 + (s - 27) / 3);
-        if constexpr (s == 38 || s == 40 || s == 42) frag_read(bcur, 1, 13 + (s - 38) / 2);
-      } else {                                       // every other slot, 24 .. 38
-        if constexpr (s == 24) frag_read(bcur, 1, 0);
-        if constexpr (s >= 26 && s <= 38 && (s & 1) == 0) frag_read(bcur, 1, 9 + (s - 26) / 2);
-      }
+      if constexpr (s == 24) frag_read(bcur, 1, 0);
+      if constexpr (s == 27 || s == 30 || s == 33 || s == 36) frag_read(bcur, 1, 9 + (s - 27) / 3);
+      if constexpr (s == 38 || s == 40 || s == 42) frag_read(bcur, 1, 13 + (s - 38) / 2);
       if constexpr (s == 21 || s == 51) {
         if (DMA) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       }
       if (DMA) {
-        constexpr int pj = w4::piece_at(SPLIT_VARIANT, s - WOFF);
+        constexpr int pj = w4::piece_at(s);
         if constexpr (pj >= 0) dma_piece(cur, pj);
       }
       if constexpr (s == 92) {
         if (NEXT) {
-          if (DMA) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(w4::pieces_before(SPLIT_VARIANT, 93 - WOFF)) : "memory");   // (a piece AT slot 92 is issued in front of this wait)
+          if (DMA) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"(w4::pieces_before(93)) : "memory");   // (a piece AT slot 92 is issued in front of this wait)
           else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
         }
       }
       if (NEXT) {                                   // first-half fragments of `nxt`: A blocks, then W blocks
-        if constexpr (!PACED_READS) {
-          if constexpr (s == 93 || s == 94 || s == 95) frag_read(bnxt, 0, 1 + (s - 93));
-          if constexpr (s == 97 || s == 98) frag_read(bnxt, 0, 4 + (s - 97));
-          if constexpr (s == 102 || s == 103 || s == 104) frag_read(bnxt, 0, 6 + (s - 102));
-          if constexpr (s == 105) frag_read(bnxt, 0, 0);
-          if constexpr (s == 106) frag_read(bnxt, 0, 9);
-          if constexpr (s == 109 || s == 112) frag_read(bnxt, 0, 10 + (s - 109) / 3);
-          if constexpr (s == 114) frag_read(bnxt, 0, 12);
-          if constexpr (s == 117 || s == 120 || s == 123) frag_read(bnxt, 0, 13 + (s - 117) / 3);
-        } else {                                     // every other slot, 93 .. 123
-          if constexpr (s >= 93 && s <= 107 && (s & 1) == 1) frag_read(bnxt, 0, 1 + (s - 93) / 2);
-          if constexpr (s == 109) frag_read(bnxt, 0, 0);
-          if constexpr (s >= 111 && s <= 123 && (s & 1) == 1) frag_read(bnxt, 0, 9 + (s - 111) / 2);
-        }
+        if constexpr (s == 93 || s == 94 || s == 95) frag_read(bnxt, 0, 1 + (s - 93));
+        if constexpr (s == 97 || s == 98) frag_read(bnxt, 0, 4 + (s - 97));
+        if constexpr (s == 102 || s == 103 || s == 104) frag_read(bnxt, 0, 6 + (s - 102));
+        if constexpr (s == 105) frag_read(bnxt, 0, 0);
+        if constexpr (s == 106) frag_read(bnxt, 0, 9);
+        if constexpr (s == 109 || s == 112) frag_read(bnxt, 0, 10 + (s - 109) / 3);
+        if constexpr (s == 114) frag_read(bnxt, 0, 12);
+        if constexpr (s == 117 || s == 120 || s == 123) frag_read(bnxt, 0, 13 + (s - 117) / 3);
       }
       __builtin_amdgcn_sched_barrier(0);
     };
@@ -904,30 +691,22 @@ __device__ __forceinline__ void gemm_w4_tile(const GemmArgs& p, const int bid_) 
     auto slot = [&](const int s) __attribute__((always_inline)) {
       const int ks = s >> 6, nb = (s >> 3) & 7, mb = s & 7;
       asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[nb][mb]) : "v"(wf[ks][nb]), "v"(af[ks][mb]));
-      if (s < 16 * RD_STEP && s % RD_STEP == 0) frag_read(bcur, 1, s / RD_STEP);
+      if (s < 32 && (s & 1) == 0) frag_read(bcur, 1, s >> 1);
       if (s == BAR1) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
       // (r05 null: wave w issuing its piece at slot 40 + 4 j + w instead of all four waves in the same slot — so that the four requests do
       // not queue in the CU's one texture addresser — is 19 % SLOWER: the 64 wave-dependent scalar branches per tile cost more than the queue.)
       if (DMA && s >= DMA0 && s < DMA0 + 16 * DMA_STEP && (s - DMA0) % DMA_STEP == 0) dma_piece(cur, (s - DMA0) / DMA_STEP);
-      if (EARLY_NEXT) {
-        // r05: the next tile's first-half fragments are read at the LDS port's pace — one ds_read_b128 every other slot from slot 64 on,
-        // where the first-half registers are dead (slots 0 .. 63 were their last readers) — instead of 16 back to back behind slot
-        // 103: four waves x 16 KiB in one burst take the port 256 - 512 cycles, of which only the 8 slots up to the tile's end covered 128.
-        // The pieces of tile t + 1 (issued during tile t - 1) must have landed by then: all but the 6 pieces of tile t + 2 issued so far.
-        // Same-box A / B at 128K rows: fc2 13.44 -> 12.96 ms, fc1 + SwiGLU 26.3 -> 25.5, o 4.91 -> 4.81, qkv at 16K 0.859 -> 0.851.
-        // (Going on to ONE barrier per tile — at slot 63, the DMA of tile t + 2 issued behind it — was mixed: fc1 - 3 %, fc2 + 1 %.)
-        if (NEXT && s == 63) {
-          if (DMA) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"((63 - DMA0) / DMA_STEP + 1) : "memory");    // the pieces of tile t + 2 issued by slot 63 stay in flight
-          else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-        if (NEXT && s >= 64 && s < 96 && (s & 1) == 0) frag_read(bnxt, 0, (s - 64) >> 1);
-      } else {
-        if (NEXT && s == 103) {
-          if (DMA) asm volatile("s_waitcnt vmcnt(16)\n\ts_barrier" ::: "memory");
-          else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-        }
-        if (NEXT && s >= 104 && s < 120) frag_read(bnxt, 0, s - 104);
+      // r05: the next tile's first-half fragments are read at the LDS port's pace — one ds_read_b128 every other slot from slot 64 on,
+      // where the first-half registers are dead (slots 0 .. 63 were their last readers) — instead of 16 back to back behind slot
+      // 103: four waves x 16 KiB in one burst take the port 256 - 512 cycles, of which only the 8 slots up to the tile's end covered 128.
+      // The pieces of tile t + 1 (issued during tile t - 1) must have landed by then: all but the 6 pieces of tile t + 2 issued so far.
+      // Same-box A / B at 128K rows: fc2 13.44 -> 12.96 ms, fc1 + SwiGLU 26.3 -> 25.5, o 4.91 -> 4.81, qkv at 16K 0.859 -> 0.851.
+      // (Going on to ONE barrier per tile — at slot 63, the DMA of tile t + 2 issued behind it — was mixed: fc1 - 3 %, fc2 + 1 %.)
+      if (NEXT && s == 63) {
+        if (DMA) asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"i"((63 - DMA0) / DMA_STEP + 1) : "memory");    // the pieces of tile t + 2 issued by slot 63 stay in flight
+        else asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
       }
+      if (NEXT && s >= 64 && s < 96 && (s & 1) == 0) frag_read(bnxt, 0, (s - 64) >> 1);
       __builtin_amdgcn_sched_barrier(0);
     };
     // (two loops: the TN fragment assembly sits between them, outside either body — with it inside, the fully unrolled 128-slot
@@ -944,10 +723,10 @@ __device__ __forceinline__ void gemm_w4_tile(const GemmArgs& p, const int bid_) 
     }
   };
 
-  // the K loop; W_ = std::integral_constant<int, slots this wave's LDS-DMA pieces are shifted by>
-  auto k_loop = [&](auto W_) __attribute__((always_inline)) {
+  // the K loop (a lambda of its own: written out in place, the same loop gets other SGPRs for its K offsets)
+  auto k_loop = [&]() __attribute__((always_inline)) {
     auto tile = [&](const bool DMA, const bool NEXT, unsigned cur, unsigned nxt) __attribute__((always_inline)) {
-      if (SPLIT_SCHED) tile_split(W_, DMA, NEXT, cur, nxt);
+      if (SPLIT_SCHED) tile_split(DMA, NEXT, cur, nxt);
       else tile_two_barriers(DMA, NEXT, cur, nxt);
     };
     int t = 0;
@@ -958,17 +737,7 @@ __device__ __forceinline__ void gemm_w4_tile(const GemmArgs& p, const int bid_) 
     }
     tile(false, false, lds0 + (t & 1) * STG, 0u);
   };
-  if (VITA_GEMM_WAVE_STAGGER && SPLIT_SCHED) {
-    // r06 A / B: the four waves of a workgroup issue their pieces in DIFFERENT slots (wave w one slot behind wave w - 1), so that the texture
-    // addresser does not get four 1-KiB requests in the same cycle.  Four copies of the loop behind one branch on the wave number (r05's attempt
-    // branched per piece and lost 19 % to the branches); barriers and waits are at the same slots in all four.
-    if (wave == 0) k_loop(std::integral_constant<int, 0>{});
-    else if (wave == 1) k_loop(std::integral_constant<int, 1>{});
-    else if (wave == 2) k_loop(std::integral_constant<int, 2>{});
-    else k_loop(std::integral_constant<int, 3>{});
-  } else {
-    k_loop(std::integral_constant<int, 0>{});
-  }
+  k_loop();
 
   // ---- epilogue.  The inline-asm MFMAs are invisible to the compiler's hazard tracking: one wait for the matrix pipe, then every row
   // block's accumulators pass through an (empty) asm statement of their own right before they are read — asm volatile statements
@@ -1085,23 +854,10 @@ __device__ __forceinline__ void gemm_w4_tile(const GemmArgs& p, const int bid_) 
   }
 }
 
-// r06, VITA_GEMM_PERSIST 1 (a same-box A / B of PERSISTENCE ALONE; off): a grid of one workgroup per CU, each walking the tiles bid, bid + grid, ...
-// (bid % 8 — the XCD the tile order is built on — is the same for all of them).  Nothing is carried from one tile to the next: the prologue of tile
-// i + 1 starts behind the epilogue of tile i, after a workgroup barrier (a wave that is done must not refill a stage a slower wave still reads).
-#ifndef VITA_GEMM_PERSIST
-#define VITA_GEMM_PERSIST 0
-#endif
+// (a kernel of its own around the tile body: with `p` a reference rather than the kernel argument, hipcc addresses the epilogue differently)
 template <int EPI, bool INTERIOR, int OPM = 0>
 __global__ __launch_bounds__(256, 1) void gemm_w4_kernel(GemmArgs p) {
-  if (VITA_GEMM_PERSIST && OPM == 0 && EPI != VITA_EPI_F32_PARTIAL) {
-    const int nwg = p.tiles_m * p.tiles_n;
-    for (int bid = blockIdx.x; bid < nwg; bid += gridDim.x) {
-      gemm_w4_tile<EPI, INTERIOR, OPM>(p, bid);
-      __syncthreads();
-    }
-  } else {
-    gemm_w4_tile<EPI, INTERIOR, OPM>(p, blockIdx.x);
-  }
+  gemm_w4_tile<EPI, INTERIOR, OPM>(p, blockIdx.x);
 }
 
 template <int EPI, bool INTERIOR>
@@ -1111,9 +867,7 @@ int launch_gemm_w4_cfg(const GemmArgs& a, hipStream_t st) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<EPI, INTERIOR>), hipFuncAttributeMaxDynamicSharedMemorySize,
                               w4::LDS_BYTES);
   });
-  unsigned grid = (unsigned)(a.tiles_m * a.tiles_n);
-  if (VITA_GEMM_PERSIST && grid > 256u) grid = 256u;            // one workgroup per CU (256 = 8 XCDs x 32)
-  hipLaunchKernelGGL((gemm_w4_kernel<EPI, INTERIOR>), dim3(grid), dim3(256), w4::LDS_BYTES, st, a);
+  hipLaunchKernelGGL((gemm_w4_kernel<EPI, INTERIOR>), dim3((unsigned)(a.tiles_m * a.tiles_n)), dim3(256), w4::LDS_BYTES, st, a);
   return vita_check_launch();
 }
 
@@ -1189,7 +943,7 @@ __global__ __launch_bounds__(256) void gemm_skinny_kernel(const bf16_t* __restri
   }
 }
 
-template <int EPI, int BM, int BN, int WM, int WN, bool PIN = true>
+template <int EPI, int BM, int BN, int WM, int WN>
 int launch_gemm_cfg(GemmArgs a, hipStream_t st) {
   constexpr int lds = 2 * (BM + BN) * BK * 2;
   const int64_t tm = (a.M + BM - 1) / BM;
@@ -1199,21 +953,11 @@ int launch_gemm_cfg(GemmArgs a, hipStream_t st) {
   a.tiles_m = (int)tm; a.tiles_n = (int)tn;
   static std::atomic<unsigned long long> attr_set{0};
   vita_device_once(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<EPI, BM, BN, WM, WN, PIN>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_bf16_kernel<EPI, BM, BN, WM, WN>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   });
-  hipLaunchKernelGGL((gemm_bf16_kernel<EPI, BM, BN, WM, WN, PIN>), dim3((unsigned)(tm * tn)), dim3(64 * WM * WN), lds, st, a);
+  hipLaunchKernelGGL((gemm_bf16_kernel<EPI, BM, BN, WM, WN>), dim3((unsigned)(tm * tn)), dim3(64 * WM * WN), lds, st, a);
   return vita_check_launch();
-}
-
-// VITA_GEMM_TILE=128|256 forces a tile configuration (developer tuning aid).
-inline int gemm_tile_override() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = vita_dev_getenv("VITA_GEMM_TILE");
-    v = e ? atoi(e) : 0;
-  }
-  return v;
 }
 
 template <int EPI>
@@ -1221,27 +965,17 @@ int launch_gemm(const GemmArgs& a, hipStream_t st) {
   // the 256x256 tile needs enough tiles to fill 256 CUs with one workgroup each
   const int64_t bn_out = EPI == VITA_EPI_SWIGLU ? 128 : 256;
   const int64_t big_tiles = ((a.M + 255) / 256) * ((a.N + bn_out - 1) / bn_out);
-  bool big = big_tiles >= 192;
-  if (gemm_tile_override() == 128) big = false;
-  if (gemm_tile_override() == 256) big = true;
-  static const bool nopin = vita_dev_getenv("VITA_GEMM_NOPIN") != nullptr;     // developer tuning aid
-  if (gemm_tile_override() == 2564) return launch_gemm_cfg<EPI, 256, 256, 2, 2>(a, st);   // 4 waves x (128 x 128), compiler-scheduled
+  const bool big = big_tiles >= 192;
   // VITA_GEMM_KERNEL (developer aid, read per launch): "w4" / "w8" force the large-problem kernel, "128" the small tile
   const char* kn = vita_dev_getenv("VITA_GEMM_KERNEL");
   const bool w4_ok = gemm_w4_addressable(a, EPI == VITA_EPI_SWIGLU);
   if (kn && kn[0] == 'w' && kn[1] == '4' && w4_ok) return launch_gemm_w4<EPI>(a, st);
   if (kn && kn[0] == 'w' && kn[1] == '8') return launch_gemm_cfg<EPI, 256, 256, 2, 4>(a, st);
   if (kn && kn[0] == '1') return launch_gemm_cfg<EPI, 128, 128, 2, 2>(a, st);
-  if (EPI == VITA_EPI_NONE) {     // developer measurement aids, read per launch (tools/microbench.py variants)
+  if (EPI == VITA_EPI_NONE) {     // developer measurement aid, read per launch
     const char* e = vita_dev_getenv("VITA_GEMM_EXP");
-    const int v = e ? atoi(e) : 0;
-    if (v == 10) { GemmArgs b = a; b.ldr = -1; return launch_gemm_cfg<EPI, 256, 256, 2, 4>(b, st); }   // 8 waves, L2-hit loads
-    if (v == 4) return launch_gemm4<EPI>(a, st);                                                        // 4 waves x (128 x 128)
-    if (v == 41) return launch_gemm4<VITA_EPI_NONE, 1>(a, st);
-    if (v == 42) return launch_gemm4<VITA_EPI_NONE, 2>(a, st);
-    if (v == 43) return launch_gemm4<VITA_EPI_NONE, 3>(a, st);
+    if (e && atoi(e) == 10) { GemmArgs b = a; b.ldr = -1; return launch_gemm_cfg<EPI, 256, 256, 2, 4>(b, st); }   // 8 waves, L2-hit loads
   }
-  if (nopin) return big ? launch_gemm_cfg<EPI, 256, 256, 2, 4, false>(a, st) : launch_gemm_cfg<EPI, 128, 128, 2, 2, false>(a, st);
   if (big && w4_ok) return launch_gemm_w4<EPI>(a, st);
   return big ? launch_gemm_cfg<EPI, 256, 256, 2, 4>(a, st) : launch_gemm_cfg<EPI, 128, 128, 2, 2>(a, st);
 }

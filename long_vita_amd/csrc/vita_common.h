@@ -80,13 +80,8 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
 // whole and the upper lanes group rg + 1 whole: two 16-byte stores per block instead of four 8-byte ones.  A workgroup's store tail is
 // bound by store ISSUE, not bytes (MI355X_MICROARCH.md: ~9.3 k -> ~5.3 k cycles for the attention forward's shape).  `dst` = the row's
 // first column of this block; it must be 16-byte aligned (the launchers check the strides).  Both lanes of a pair must be active.
-// VITA_WIDE_STORE 0 builds the r05 form (same-box A / B).
-#ifndef VITA_WIDE_STORE
-#define VITA_WIDE_STORE 1
-#endif
 template <class Acc>
 __device__ __forceinline__ void store_row_block32(bf16_t* dst, const Acc& acc, float scale, int hi) {
-#if VITA_WIDE_STORE
 #pragma unroll
   for (int pr = 0; pr < 2; ++pr) {
     const int k0 = 8 * pr, k1 = 8 * pr + 4;                      // accumulator registers of groups rg = 2 pr and 2 pr + 1
@@ -97,13 +92,6 @@ __device__ __forceinline__ void store_row_block32(bf16_t* dst, const Acc& acc, f
     const u32x4 w = {r0[0], r1[0], r0[1], r1[1]};
     *reinterpret_cast<u32x4*>(dst + 16 * pr + 8 * hi) = w;
   }
-#else
-#pragma unroll
-  for (int rg = 0; rg < 4; ++rg) {
-    const u32x2 w = {pack_bf16x2(acc[rg * 4 + 0] * scale, acc[rg * 4 + 1] * scale), pack_bf16x2(acc[rg * 4 + 2] * scale, acc[rg * 4 + 3] * scale)};
-    *reinterpret_cast<u32x2*>(dst + 8 * rg + 4 * hi) = w;
-  }
-#endif
 }
 
 __device__ __forceinline__ void rope_rotate8(u32x4& x1, u32x4& x2, const u32x4& c, const u32x4& s,

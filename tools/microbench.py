@@ -159,26 +159,6 @@ def bench_peaks():
     emit(kind="peak_hbm_read_only", bytes=n, ms=med, ms_best=best, gbps=n / med / 1e6)
 
 
-def bench_gemm_variants():
-    """Experiment: placement of the LDS-DMA pieces in the 256x256 GEMM (VITA_GEMM_EXP, see gemm.hip)."""
-    for (M, N, K, tag) in [(131072, 5120, 5120, "S128K/o"), (131072, 5120, 13824, "S128K/fc2"), (16384, 7168, 5120, "S16K/qkv"),
-                           (8192, 8192, 8192, "square8k")]:
-        a = (torch.randn(M, K, device=DEV) * 0.5).bfloat16()
-        w = (torch.randn(N, K, device=DEV) * 0.02).bfloat16()
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
-        ref = torch.matmul(a[:4096], w.t()).float()
-        for v in os.environ.get("VARIANTS", "0,4").split(","):
-            os.environ["VITA_GEMM_EXP"] = v
-            out.zero_()
-            med, best = timeit(lambda: ops.gemm(a, w, 0, None, None, None, out=out))
-            err = float((out[:4096].float() - ref).abs().max())
-            tail = float((out[-256:].float() - torch.matmul(a[-256:], w.t()).float()).abs().max())
-            emit(kind="gemm_dma_variant", variant=v, tag=tag, ms=med, ms_best=best, tflops=2.0 * M * N * K / med / 1e9,
-                 max_abs_err_vs_vendor=err, tail_err=tail)
-        os.environ.pop("VITA_GEMM_EXP")
-        del a, w, out
-
-
 LLM_SHAPES = [(131072, 7168, 5120, 1, "S128K/qkv"), (131072, 5120, 5120, 3, "S128K/o"),
               (131072, 13824, 5120, 5, "S128K/fc1_swiglu"), (131072, 5120, 13824, 3, "S128K/fc2"),
               (16384, 7168, 5120, 1, "S16K/qkv"), (16384, 5120, 13824, 3, "S16K/fc2")]
@@ -214,8 +194,6 @@ if __name__ == "__main__":
     if which and which[0] in ("env", "envvit"):
         bench_gemm_env(which[1], which[2].split(","), VIT_SHAPES if which[0] == "envvit" else None)
         sys.exit(0)
-    if "variants" in which:
-        bench_gemm_variants()
     if "peaks" in which:
         bench_peaks()
     if "gemm_tn" in which:
