@@ -445,6 +445,46 @@ int vita_ce_vp_grad(const void* logits, int is_f32, int64_t ld, const int64_t* l
 int vita_row_scatter_add_f32(const void* src, const int64_t* idx, float* dst, int64_t dst_rows,
                              int64_t n, int cols, int* err_flag, void* stream);
 
+/* ABI 19: the ORDERED (deterministic) forms of the backward's parameter-gradient reductions — the reference's `--use-deter-comp`
+ * (M/training/arguments.py:557) and torch.use_deterministic_algorithms(True).  The entries above add each workgroup's column sums
+ * into the caller's fp32 buffer with atomics, in arrival order, so two runs can differ in the last bits.  These run the same kernels,
+ * with the same per-workgroup arithmetic and the same dx bits, but workgroup b stores its sums to row b of `workspace` and a finish pass
+ * adds the rows in ascending block order: acc[c] = ((acc[c] + p0[c]) + p1[c]) + ...  The block count depends on (rows, cols) only,
+ * so the bits do not depend on the CU count, occupancy or other work on the device.  Accumulation contract as above (caller zeroes
+ * or holds a running sum).  workspace: *_workspace_bytes(rows, cols) bytes (<= 32 MiB), 16-byte aligned, contents ignored; NULL
+ * with rows > 0 is VITA_ERR_INVALID_ARG, checked before anything is launched.
+ *   vita_rmsnorm_bwd_ordered            vita_rmsnorm_bwd (transformer_engine.py:74-79); dw_acc NULL: no reduction, workspace unused.
+ *   vita_layernorm_bwd_ordered          vita_layernorm_bwd (intern_vit_model.py:46,72).
+ *   vita_bias_scale_res_bwd_ordered     vita_bias_scale_res_bwd (intern_vit_model.py:60-66,79-82); at most 2048 row blocks.
+ *   vita_layernorm_param_grad_ordered   vita_layernorm_param_grad (M/pretrain_long_vita.py:443-446); the four waves of a
+ *                                       workgroup are summed in wave order before the store.
+ *   vita_pixel_shuffle_ln_bwd_ordered   vita_pixel_shuffle_ln_bwd with norm = 1 (M/pretrain_long_vita.py:467-483 + :443-446);
+ *                                       workspace_bytes takes rows = n (grid / 2)^2, cols = 4 hidden. */
+size_t vita_rmsnorm_bwd_workspace_bytes(int64_t rows, int cols);
+int vita_rmsnorm_bwd_ordered(const void* dy, const void* x, const void* w, const void* res, void* dx, float* dw_acc, int64_t rows, int cols,
+                             float eps, void* workspace, void* stream);
+size_t vita_layernorm_bwd_workspace_bytes(int64_t rows, int cols);
+int vita_layernorm_bwd_ordered(const void* dy, const void* x, const void* w, void* dx, float* dgamma, float* dbeta, int64_t rows, int cols,
+                               float eps, void* workspace, void* stream);
+size_t vita_bias_scale_res_bwd_workspace_bytes(int64_t rows, int cols);
+int vita_bias_scale_res_bwd_ordered(const void* g, const void* x, const void* bias, const void* scale, void* dx, float* d_bias,
+                                    float* d_scale, int64_t rows, int cols, void* workspace, void* stream);
+size_t vita_layernorm_param_grad_workspace_bytes(int64_t rows, int cols);
+int vita_layernorm_param_grad_ordered(const void* dy, const void* x, float* dgamma, float* dbeta, int64_t rows, int cols, float eps,
+                                      int prenormalized, void* workspace, void* stream);
+size_t vita_pixel_shuffle_ln_bwd_workspace_bytes(int64_t rows, int cols);
+int vita_pixel_shuffle_ln_bwd_ordered(const void* dy, const void* x, const void* w, void* dx, float* dgamma, float* dbeta, int64_t n,
+                                      int grid, int hidden, int has_cls, float eps, int64_t img_stride, int64_t tok_stride,
+                                      void* workspace, void* stream);
+/* ABI 19: the ordered word-embedding gradient (the backward of M/core/tensor_parallel/layers.py:216-232) without atomics.  The caller
+ * stable-sorts the ids: sorted_idx[k] ascending, order[k] = the row of src holding the k-th entry (rows ascending among equal ids).
+ * Each id's rows are summed in row order — long runs in fixed 256-entry chunks whose partials are added in chunk order — and every
+ * destination row is written once: dst[id] = dst[id] + sum.  Negative ids are skipped; ids >= dst_rows set *err_flag.  cols % 8 == 0;
+ * src / dst / workspace 16-byte aligned; workspace: vita_row_scatter_add_workspace_bytes(n, cols) bytes. */
+size_t vita_row_scatter_add_workspace_bytes(int64_t n, int cols);
+int vita_row_scatter_add_f32_sorted(const void* src, const int64_t* sorted_idx, const int64_t* order, float* dst, int64_t dst_rows,
+                                    int64_t n, int cols, void* workspace, int* err_flag, void* stream);
+
 /* delta[h, row] = sum_d float(dO[row,h,d]) * float(O[row,h,d])  (attention backward pre-pass).
  * First kernel of the flash-attention backward that stands behind M/core/transformer/dot_product_attention.py:374-390. */
 int vita_attn_delta(const void* o, const void* d_o, float* delta, int64_t rows, int heads,

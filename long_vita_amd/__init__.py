@@ -5,4 +5,6 @@ lib.py / ops.py    ctypes binding and tensor-level entry points (no CPU fallback
 the rest           host-side mirror of the reference's operator / plugin interface for this path
                    (same names, argument meaning and error behaviour as long_vita_megatron/*).
 """
-__all__ = ["lib", "ops"]
+from .ops import deterministic, deterministic_enabled, set_deterministic  # noqa: E402  (deterministic mode, ABI 19)
+
+__all__ = ["lib", "ops", "deterministic", "deterministic_enabled", "set_deterministic"]

@@ -50,8 +50,10 @@ __global__ __launch_bounds__(256) void transpose_kernel(const bf16_t* __restrict
 // line operations they cost (lane-strided: 0.15 ms per call; consecutive: 0.02 ms).  Measured at 5120 columns with dw and the
 // residual branch, 16384 / 131072 rows: 0.17 / 1.13 ms = 3.9 / 4.7 TB/s (r02 kernel: 0.46 / 3.58 ms; profiles/r03_rmsnorm_bwd_ab.jsonl).
 // rmsnorm_bwd_wave_kernel (r02: a wave per row, dw in 8 VPL registers per lane) keeps the wider rows.
+// ORDERED (ABI 19, both kernels): dw_acc is the workspace [blocks][cols]; the workgroup stores its column sums to row blockIdx.x and
+// vita_ordered_finish adds the rows in block order (vita_common.h).  ORDERED = false is the atomic form, unchanged.
 // ---------------------------------------------------------------------------------------------
-template <int VPL>
+template <int VPL, bool ORDERED>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                              const bf16_t* __restrict__ w, const bf16_t* __restrict__ res,
                                                              bf16_t* __restrict__ dx, float* __restrict__ dw_acc, int64_t rows,
@@ -131,7 +133,14 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
       }
     }
   }
-  if (dw_acc) {
+  if (ORDERED) {
+    // each lane owns its columns whole: its registers are the workgroup's sums, stored as they are
+#pragma unroll
+    for (int i = 0; i < VPL; ++i) {
+      const int vi = tid + i * 256;
+      if (vi < nvec) vita_store_row8(dw_acc + (int64_t)blockIdx.x * cols + vi * 8, dwl[i]);
+    }
+  } else if (dw_acc) {
     // flush through LDS so that a wave's atomic instruction covers 64 CONSECUTIVE columns (two cache lines) instead of 64 columns
     // 32 bytes apart (sixteen lines): the atomics of all workgroups meet on the same cols / 32 lines, and line operations are what they cost
     extern __shared__ float dw_lds[];                // [8][nvec]: element e of vector vi at e * nvec + vi (bank = lane)
@@ -149,7 +158,7 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_kernel(const bf16_t* __restri
 }
 
 
-template <int VPL>
+template <int VPL, bool ORDERED>
 __global__ __launch_bounds__(256) void rmsnorm_bwd_wave_kernel(const bf16_t* __restrict__ dy,
                                                           const bf16_t* __restrict__ x,
                                                           const bf16_t* __restrict__ w,
@@ -242,9 +251,16 @@ __global__ __launch_bounds__(256) void rmsnorm_bwd_wave_kernel(const bf16_t* __r
       for (int j = 0; j < 8; ++j) red[wv][lane][j] = dwl[i][j];
       __syncthreads();
       if (wv == 0 && vi < nvec) {
+        if (ORDERED) {
+          float s8[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-          atomicAdd(dw_acc + vi * 8 + j, (red[0][lane][j] + red[1][lane][j]) + (red[2][lane][j] + red[3][lane][j]));
+          for (int j = 0; j < 8; ++j) s8[j] = (red[0][lane][j] + red[1][lane][j]) + (red[2][lane][j] + red[3][lane][j]);
+          vita_store_row8(dw_acc + (int64_t)blockIdx.x * cols + vi * 8, s8);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            atomicAdd(dw_acc + vi * 8 + j, (red[0][lane][j] + red[1][lane][j]) + (red[2][lane][j] + red[3][lane][j]));
+        }
       }
     }
   }
@@ -346,7 +362,8 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16_t* __restrict_
 // LayerNorm backward (torch.nn.LayerNorm / TENorm; forward y = bf16(xhat * w + b), xhat = (x - mean) * rstd in fp32):
 //   g = dy * w ; dx = bf16( rstd * (g - mean(g) - xhat * mean(g * xhat)) ) ; dgamma += sum_rows dy * xhat ; dbeta += sum_rows dy.
 // One wave per row (strided over rows); parameter gradients per lane in registers, flushed with fp32 atomics (caller zeroes).
-template <int VPL>
+// ORDERED (ABI 19): dgamma / dbeta are the workspace rows [blocks][cols] of the two gradients; the LDS image goes to row blockIdx.x.
+template <int VPL, bool ORDERED>
 __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                             const bf16_t* __restrict__ w, bf16_t* __restrict__ dx,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
@@ -448,6 +465,11 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const bf16_t* __rest
     }
     __syncthreads();
   }
+  if (ORDERED) {
+    vita_store_image_row(pg_lds, dgamma + (int64_t)blockIdx.x * cols, nvec);
+    vita_store_image_row(pg_lds + cols, dbeta + (int64_t)blockIdx.x * cols, nvec);
+    return;
+  }
   for (int i = threadIdx.x; i < cols; i += 256) {
     const int at = (i & 7) * nvec + (i >> 3);
     atomicAdd(dgamma + i, pg_lds[at]);
@@ -502,6 +524,8 @@ __global__ __launch_bounds__(256) void bias_scale_res_fwd_kernel(const bf16_t* _
 
 // its backward, g = d(out):  d_residual = g (the caller aliases it) ; dx = bf16(g * scale) ; d_bias += sum_rows dx ;
 //   d_scale += sum_rows g * bf16(x + bias).   One workgroup = a block of rows x all columns; column sums per thread, then fp32 atomics.
+// ORDERED (ABI 19): d_bias / d_scale are the workspace rows [blocks][cols]; the flush image goes to row blockIdx.x.
+template <bool ORDERED>
 __global__ __launch_bounds__(256) void bias_scale_res_bwd_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ x,
                                                                  const bf16_t* __restrict__ bias, const bf16_t* __restrict__ scale,
                                                                  bf16_t* __restrict__ dx, float* __restrict__ d_bias,
@@ -538,6 +562,11 @@ __global__ __launch_bounds__(256) void bias_scale_res_bwd_kernel(const bf16_t* _
     for (int j = 0; j < 8; ++j) { bs_lds[j * nvec + vi] = ab[j]; bs_lds[cols + j * nvec + vi] = as[j]; }
   }
   __syncthreads();
+  if (ORDERED) {
+    if (d_bias) vita_store_image_row(bs_lds, d_bias + (int64_t)blockIdx.x * cols, nvec);
+    if (d_scale) vita_store_image_row(bs_lds + cols, d_scale + (int64_t)blockIdx.x * cols, nvec);
+    return;
+  }
   for (int i = threadIdx.x; i < cols; i += blockDim.x) {
     const int at = (i & 7) * nvec + (i >> 3);
     if (d_bias) atomicAdd(d_bias + i, bs_lds[at]);
@@ -547,7 +576,9 @@ __global__ __launch_bounds__(256) void bias_scale_res_bwd_kernel(const bf16_t* _
 
 // LayerNorm parameter gradients (the projector pre-norm; its input comes from the frozen ViT, so dx
 // is not needed): dgamma += sum_rows dy * xhat, dbeta += sum_rows dy   (fp32 atomics).
-template <int VPL>
+// ORDERED (ABI 19): the four waves' registers are summed in wave order through LDS (as layernorm_bwd_kernel does) and the image goes to
+// row blockIdx.x of the workspace rows dgamma / dbeta [blocks][cols]; dynamic LDS 8 cols bytes.
+template <int VPL, bool ORDERED>
 __global__ __launch_bounds__(256) void layernorm_param_grad_kernel(const bf16_t* __restrict__ dy,
                                                                    const bf16_t* __restrict__ x,
                                                                    float* __restrict__ dgamma,
@@ -607,6 +638,31 @@ __global__ __launch_bounds__(256) void layernorm_param_grad_kernel(const bf16_t*
         }
       }
     }
+  }
+  if (ORDERED) {
+    extern __shared__ float pq_lds[];                // [2][8][nvec], as layernorm_bwd_kernel's flush image
+    const int wv = threadIdx.x >> 6;
+    for (int w4 = 0; w4 < 4; ++w4) {
+      if (wv == w4) {
+#pragma unroll
+        for (int i = 0; i < VPL; ++i) {
+          const int vi = lane + i * 64;
+          if (vi < nvec) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+              float* pgm = pq_lds + j * nvec + vi;
+              float* pbt = pq_lds + cols + j * nvec + vi;
+              *pgm = (w4 ? *pgm : 0.f) + dg[i][j];
+              *pbt = (w4 ? *pbt : 0.f) + db[i][j];
+            }
+          }
+        }
+      }
+      __syncthreads();
+    }
+    vita_store_image_row(pq_lds, dgamma + (int64_t)blockIdx.x * cols, nvec);
+    vita_store_image_row(pq_lds + cols, dbeta + (int64_t)blockIdx.x * cols, nvec);
+    return;
   }
 #pragma unroll
   for (int i = 0; i < VPL; ++i) {
@@ -772,6 +828,148 @@ __global__ __launch_bounds__(256) void row_scatter_add_kernel(const bf16_t* __re
   }
 }
 
+// The ORDERED embedding gradient (ABI 19; no atomics, cdna_hip_programming.md Appendix B "Scatter / gather / embedding"): the caller
+// stable-sorts the ids, sorted[k] ascending and order[k] = the source row of the k-th entry (positions ascending among equal ids).
+// The sorted list is cut into chunks of SCATTER_CHUNK entries, one wave per (chunk, 512-column slab), 8 columns per lane.  Pass 1 sums
+// each run of equal ids in position order: a run inside its chunk is added to dst[id] by this wave alone (no other wave holds that id);
+// a run the chunk's end cuts is stored to the chunk's workspace row; a run the chunk's start cuts is left to pass 2.  Pass 2: the chunk
+// in which a cut run ENDS adds dst[id] + P[first chunk] + ... + P[previous chunk] in chunk order, then its own head piece.  A token
+// repeated 65536 times is so summed by 256 waves in parallel plus one wave over 256 partials (the guide's split rule), and every
+// destination row is written exactly once.  Negative ids are skipped; ids >= dst_rows set *err_flag, as the atomic form does.
+constexpr int SCATTER_CHUNK = 256;
+constexpr int SCATTER_BATCH = 8;                     // source rows in flight per lane
+
+__device__ __forceinline__ void add_bf16x8(float* acc, const u32x4 v) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { acc[2 * j] += bf16lo_to_f32(v[j]); acc[2 * j + 1] += bf16hi_to_f32(v[j]); }
+}
+
+__global__ __launch_bounds__(256) void row_scatter_sorted_kernel(const bf16_t* __restrict__ src, const int64_t* __restrict__ sorted,
+                                                                 const int64_t* __restrict__ order, float* __restrict__ dst,
+                                                                 int64_t dst_rows, int64_t n, int cols, float* __restrict__ part,
+                                                                 int* __restrict__ err_flag) {
+  const int lane = threadIdx.x & 63;
+  const int nvec = cols >> 3, nslab = (nvec + 63) >> 6;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t chunk = wid / nslab;
+  const int slab = (int)(wid - chunk * nslab);
+  const int64_t k0 = chunk * SCATTER_CHUNK;
+  if (k0 >= n) return;
+  const int64_t k1 = k0 + SCATTER_CHUNK < n ? k0 + SCATTER_CHUNK : n;
+  const int vi = slab * 64 + lane;
+  const bool live = vi < nvec;
+  float acc[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+  int64_t cur = sorted[k0];
+  bool head_open = k0 > 0 && sorted[k0 - 1] == cur;
+  auto flush = [&](bool tail_open) {
+    if (cur < 0) return;                                            // negative index = "skip this row"
+    if (cur >= dst_rows) {
+      if (err_flag && lane == 0 && slab == 0) atomicExch(err_flag, 1);
+      return;
+    }
+    if (!live) return;
+    if (tail_open) {
+      vita_store_row8(part + chunk * cols + vi * 8, acc);
+    } else if (!head_open) {
+      float* d = dst + cur * cols + vi * 8;
+      f32x4 lo = *reinterpret_cast<const f32x4*>(d), hi = *reinterpret_cast<const f32x4*>(d + 4);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { lo[j] += acc[j]; hi[j] += acc[4 + j]; }
+      *reinterpret_cast<f32x4*>(d) = lo;
+      *reinterpret_cast<f32x4*>(d + 4) = hi;
+    }
+  };
+  for (int64_t k = k0; k < k1; k += SCATTER_BATCH) {
+    u32x4 v[SCATTER_BATCH];
+#pragma unroll
+    for (int u = 0; u < SCATTER_BATCH; ++u) {
+      v[u] = u32x4{0u, 0u, 0u, 0u};
+      if (k + u < k1) {
+        const int64_t r = order[k + u];
+        if (live && r >= 0 && r < n) v[u] = *reinterpret_cast<const u32x4*>(src + r * cols + vi * 8);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < SCATTER_BATCH; ++u) {
+      if (k + u < k1) {
+        const int64_t id = sorted[k + u];
+        if (id != cur) {
+          flush(false);
+          cur = id;
+          head_open = false;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) acc[j] = 0.f;
+        }
+        add_bf16x8(acc, v[u]);
+      }
+    }
+  }
+  flush(k1 < n && sorted[k1] == cur);
+}
+
+__global__ __launch_bounds__(256) void row_scatter_sorted_owner_kernel(const bf16_t* __restrict__ src, const int64_t* __restrict__ sorted,
+                                                                       const int64_t* __restrict__ order, float* __restrict__ dst,
+                                                                       int64_t dst_rows, int64_t n, int cols, const float* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int nvec = cols >> 3, nslab = (nvec + 63) >> 6;
+  const int64_t wid = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int64_t chunk = wid / nslab;
+  const int slab = (int)(wid - chunk * nslab);
+  const int64_t k0 = chunk * SCATTER_CHUNK;
+  if (k0 == 0 || k0 >= n) return;
+  const int64_t k1 = k0 + SCATTER_CHUNK < n ? k0 + SCATTER_CHUNK : n;
+  const int64_t id = sorted[k0];
+  if (sorted[k0 - 1] != id || id < 0 || id >= dst_rows) return;     // the first run starts in this chunk (pass 1 added it) / skipped
+  if (k1 < n && sorted[k1] == id) return;                           // the run goes on past this chunk: a later chunk owns it
+  const int vi = slab * 64 + lane;
+  if (vi >= nvec) return;
+  int64_t lo = 0, hi = k0;                                          // first entry of the run: lower bound of id in sorted[0, k0)
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (sorted[mid] < id) lo = mid + 1; else hi = mid;
+  }
+  float* d = dst + id * cols + vi * 8;
+  float acc[8], own[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) { acc[j] = d[j]; own[j] = 0.f; }
+  for (int64_t c = lo / SCATTER_CHUNK; c < chunk; ++c) {
+    const float* p = part + c * cols + vi * 8;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { acc[j] += a[j]; acc[4 + j] += b[j]; }
+  }
+  for (int64_t k = k0; k < k1 && sorted[k] == id; ++k) {
+    const int64_t r = order[k];
+    if (r >= 0 && r < n) add_bf16x8(own, *reinterpret_cast<const u32x4*>(src + r * cols + vi * 8));
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) acc[j] += own[j];
+  vita_store_row8(d, acc);
+}
+
+// the finish of every ORDERED reduction (vita_common.h): acc[c] = ((acc[c] + part[0][c]) + part[1][c]) + ...; blockIdx.y picks the gradient.
+// One thread per column; 16 partial rows in flight per thread (the loop is latency-bound: a few hundred rows per column)
+__global__ __launch_bounds__(256) void ordered_finish_kernel(const float* __restrict__ part, float* __restrict__ acc0, float* __restrict__ acc1,
+                                                             int blocks, int cols) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  float* acc = blockIdx.y ? acc1 : acc0;
+  if (c >= cols || !acc) return;
+  const float* p = part + (int64_t)blockIdx.y * blocks * cols + c;
+  float s = acc[c];
+  int b = 0;
+  for (; b + 16 <= blocks; b += 16) {
+    float t[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) t[u] = p[(int64_t)(b + u) * cols];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) s += t[u];
+  }
+  for (; b < blocks; ++b) s += p[(int64_t)b * cols];
+  acc[c] = s;
+}
+
 // D[b, h, row] = sum_d float(dO[b,row,h,d]) * float(O[b,row,h,d])  — attention backward pre-pass.
 // one wave per (row, head): 64 lanes x 2 (d=128) or x1 (d=64) elements
 __global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restrict__ o,
@@ -848,26 +1046,62 @@ extern "C" int vita_transpose_bf16(const void* src, int64_t ld_src, void* dst, i
   return vita_check_launch();
 }
 
+// row blocks of the two RMSNorm backward kernels (the workgroup kernel for cols <= 6144, else the wave-per-row kernel)
+static bool rmsnorm_bwd_wg_kernel(int cols) {
+  const char* e = vita_dev_getenv("VITA_RMSNORM_BWD");           // developer A/B switch: "o" = the r02 wave-per-row kernel everywhere
+  return cols <= 6144 && !(e && e[0] == 'o');
+}
+static int64_t rmsnorm_bwd_blocks(int64_t rows, int cols) {
+  return rmsnorm_bwd_wg_kernel(cols) ? (rows < 512 ? rows : 512) : ((rows + 3) / 4 < 512 ? (rows + 3) / 4 : 512);
+}
+
+// part == nullptr: the atomic form (dw_acc += column sums in arrival order).  part != nullptr: the ordered form (vita_common.h).
+static int rmsnorm_bwd_launch(const void* dy, const void* x, const void* w, const void* res, void* dx, float* dw_acc, int64_t rows, int cols,
+                              float eps, float* part, hipStream_t st) {
+  const bool ord = part && dw_acc;
+  const int64_t nb = ord ? vita_ordered_blocks(rmsnorm_bwd_blocks(rows, cols), cols, 1) : rmsnorm_bwd_blocks(rows, cols);
+  float* dw = ord ? part : dw_acc;
+  if (rmsnorm_bwd_wg_kernel(cols)) {
+    dim3 grid((unsigned)nb), block(256);                         // 2 workgroups per CU
+#define VITA_RW(V) do { if (ord) hipLaunchKernelGGL((rmsnorm_bwd_kernel<V, true>), grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)res, (bf16_t*)dx, dw, rows, cols, eps); \
+                        else hipLaunchKernelGGL((rmsnorm_bwd_kernel<V, false>), grid, block, (size_t)cols * 4, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)res, (bf16_t*)dx, dw, rows, cols, eps); } while (0)
+    if (cols <= 2048) VITA_RW(1); else if (cols <= 4096) VITA_RW(2); else VITA_RW(3);
+#undef VITA_RW
+  } else {
+    const int vpl = (cols + 511) / 512;
+    dim3 grid((unsigned)nb), block(256);
+#define VITA_RB(V) do { if (ord) hipLaunchKernelGGL((rmsnorm_bwd_wave_kernel<V, true>), grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)res, (bf16_t*)dx, dw, rows, cols, eps); \
+                        else hipLaunchKernelGGL((rmsnorm_bwd_wave_kernel<V, false>), grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)res, (bf16_t*)dx, dw, rows, cols, eps); } while (0)
+    if (vpl <= 2) VITA_RB(2); else if (vpl <= 4) VITA_RB(4); else if (vpl <= 8) VITA_RB(8); else if (vpl <= 10) VITA_RB(10); else VITA_RB(16);
+#undef VITA_RB
+  }
+  if (ord) {
+    const int rc = vita_check_launch();
+    if (rc != VITA_OK) return rc;
+    return vita_ordered_finish(part, nb, cols, dw_acc, nullptr, st);
+  }
+  return vita_check_launch();
+}
+
 extern "C" int vita_rmsnorm_bwd(const void* dy, const void* x, const void* w, const void* res, void* dx,
                                 float* dw_acc, int64_t rows, int cols, float eps, void* stream) {
   if (!dy || !x || !w || !dx || rows < 0 || cols <= 0) return VITA_ERR_INVALID_ARG;
   if ((cols & 7) || cols > 8192) return VITA_ERR_UNSUPPORTED;
   if (rows == 0) return VITA_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const char* e = vita_dev_getenv("VITA_RMSNORM_BWD");           // developer A/B switch: "o" = the r02 wave-per-row kernel everywhere
-  if (cols <= 6144 && !(e && e[0] == 'o')) {
-    dim3 grid((unsigned)(rows < 512 ? rows : 512)), block(256);  // 2 workgroups per CU
-#define VITA_RW(V) hipLaunchKernelGGL(rmsnorm_bwd_kernel<V>, grid, block, (size_t)cols * 4, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)res, (bf16_t*)dx, dw_acc, rows, cols, eps)
-    if (cols <= 2048) VITA_RW(1); else if (cols <= 4096) VITA_RW(2); else VITA_RW(3);
-#undef VITA_RW
-    return vita_check_launch();
-  }
-  const int vpl = (cols + 511) / 512;
-  dim3 grid((unsigned)((rows + 3) / 4 < 512 ? (rows + 3) / 4 : 512)), block(256);
-#define VITA_RB(V) hipLaunchKernelGGL(rmsnorm_bwd_wave_kernel<V>, grid, block, 0, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (const bf16_t*)res, (bf16_t*)dx, dw_acc, rows, cols, eps)
-  if (vpl <= 2) VITA_RB(2); else if (vpl <= 4) VITA_RB(4); else if (vpl <= 8) VITA_RB(8); else if (vpl <= 10) VITA_RB(10); else VITA_RB(16);
-#undef VITA_RB
-  return vita_check_launch();
+  return rmsnorm_bwd_launch(dy, x, w, res, dx, dw_acc, rows, cols, eps, nullptr, (hipStream_t)stream);
+}
+
+extern "C" size_t vita_rmsnorm_bwd_workspace_bytes(int64_t rows, int cols) {
+  if (rows <= 0 || cols <= 0 || (cols & 7) || cols > 8192) return 0;
+  return (size_t)vita_ordered_blocks(rmsnorm_bwd_blocks(rows, cols), cols, 1) * (size_t)cols * sizeof(float);
+}
+
+extern "C" int vita_rmsnorm_bwd_ordered(const void* dy, const void* x, const void* w, const void* res, void* dx, float* dw_acc, int64_t rows,
+                                        int cols, float eps, void* workspace, void* stream) {
+  if (!dy || !x || !w || !dx || rows < 0 || cols <= 0 || (rows > 0 && !workspace)) return VITA_ERR_INVALID_ARG;
+  if ((cols & 7) || cols > 8192 || ((uintptr_t)workspace & 15)) return VITA_ERR_UNSUPPORTED;
+  if (rows == 0) return VITA_OK;
+  return rmsnorm_bwd_launch(dy, x, w, res, dx, dw_acc, rows, cols, eps, (float*)workspace, (hipStream_t)stream);
 }
 
 extern "C" int vita_add_bf16(const void* a, const void* b, void* out, int64_t n, void* stream) {
@@ -915,22 +1149,51 @@ extern "C" int vita_gelu_tanh_bwd(const void* x, const void* dy, void* dx, int64
   return gelu_bwd_launch(x, dy, dx, n, 1, stream);
 }
 
+static int64_t layernorm_bwd_blocks(int64_t rows) { return (rows + 3) / 4 < 512 ? (rows + 3) / 4 : 512; }
+
+static int layernorm_bwd_launch(const void* dy, const void* x, const void* w, void* dx, float* dgamma, float* dbeta, int64_t rows, int cols,
+                                float eps, float* part, hipStream_t st) {
+  const int64_t nb = part ? vita_ordered_blocks(layernorm_bwd_blocks(rows), cols, 2) : layernorm_bwd_blocks(rows);
+  float* pg = part ? part : dgamma;
+  float* pb = part ? part + nb * cols : dbeta;
+  dim3 grid((unsigned)nb), block(256);
+#define VITA_LB(V) do { if (part) hipLaunchKernelGGL((layernorm_bwd_kernel<V, true>), grid, block, (size_t)cols * 8, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)dx, pg, pb, rows, cols, eps); \
+                         else hipLaunchKernelGGL((layernorm_bwd_kernel<V, false>), grid, block, (size_t)cols * 8, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)dx, pg, pb, rows, cols, eps); } while (0)
+  const int vpl = (cols + 511) / 512;
+  static std::atomic<unsigned long long> attr_set{0};           // cols = 8192 needs 64 KiB of dynamic LDS for the flush image
+  vita_device_once(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&layernorm_bwd_kernel<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&layernorm_bwd_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+  });
+  if (vpl <= 2) VITA_LB(2); else if (vpl <= 4) VITA_LB(4); else if (vpl <= 8) VITA_LB(8); else VITA_LB(16);
+#undef VITA_LB
+  if (part) {
+    const int rc = vita_check_launch();
+    if (rc != VITA_OK) return rc;
+    return vita_ordered_finish(part, nb, cols, dgamma, dbeta, st);
+  }
+  return vita_check_launch();
+}
+
 extern "C" int vita_layernorm_bwd(const void* dy, const void* x, const void* w, void* dx, float* dgamma, float* dbeta,
                                   int64_t rows, int cols, float eps, void* stream) {
   if (!dy || !x || !w || !dx || !dgamma || !dbeta || rows < 0 || cols <= 0) return VITA_ERR_INVALID_ARG;
   if ((cols & 7) || cols > 8192) return VITA_ERR_UNSUPPORTED;
   if (rows == 0) return VITA_OK;
-  dim3 grid((unsigned)((rows + 3) / 4 < 512 ? (rows + 3) / 4 : 512)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-#define VITA_LB(V) hipLaunchKernelGGL(layernorm_bwd_kernel<V>, grid, block, (size_t)cols * 8, st, (const bf16_t*)dy, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)dx, dgamma, dbeta, rows, cols, eps)
-  const int vpl = (cols + 511) / 512;
-  static std::atomic<unsigned long long> attr_set{0};           // cols = 8192 needs 64 KiB of dynamic LDS for the flush image
-  vita_device_once(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&layernorm_bwd_kernel<16>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-  });
-  if (vpl <= 2) VITA_LB(2); else if (vpl <= 4) VITA_LB(4); else if (vpl <= 8) VITA_LB(8); else VITA_LB(16);
-#undef VITA_LB
-  return vita_check_launch();
+  return layernorm_bwd_launch(dy, x, w, dx, dgamma, dbeta, rows, cols, eps, nullptr, (hipStream_t)stream);
+}
+
+extern "C" size_t vita_layernorm_bwd_workspace_bytes(int64_t rows, int cols) {
+  if (rows <= 0 || cols <= 0 || (cols & 7) || cols > 8192) return 0;
+  return 2 * (size_t)vita_ordered_blocks(layernorm_bwd_blocks(rows), cols, 2) * (size_t)cols * sizeof(float);
+}
+
+extern "C" int vita_layernorm_bwd_ordered(const void* dy, const void* x, const void* w, void* dx, float* dgamma, float* dbeta, int64_t rows,
+                                          int cols, float eps, void* workspace, void* stream) {
+  if (!dy || !x || !w || !dx || !dgamma || !dbeta || rows < 0 || cols <= 0 || (rows > 0 && !workspace)) return VITA_ERR_INVALID_ARG;
+  if ((cols & 7) || cols > 8192 || ((uintptr_t)workspace & 15)) return VITA_ERR_UNSUPPORTED;
+  if (rows == 0) return VITA_OK;
+  return layernorm_bwd_launch(dy, x, w, dx, dgamma, dbeta, rows, cols, eps, (float*)workspace, (hipStream_t)stream);
 }
 
 extern "C" int vita_gelu_fwd(const void* x, void* a, int64_t n, int tanh_form, void* stream) {
@@ -952,21 +1215,60 @@ extern "C" int vita_bias_scale_res_fwd(const void* x, const void* bias, const vo
   return vita_check_launch();
 }
 
+// rows per block of the ORDERED form: the atomic form's 64 (one workgroup per 64 rows, no cap: 8104 workgroups at 506 frames x 1025
+// tokens) would need a 66 MB workspace there, so the ordered form caps the row blocks at 2048 and the workspace at 32 MiB
+static int bias_scale_res_ordered_rpb(int64_t rows, int cols) {
+  int64_t nb = (rows + 63) / 64;
+  nb = vita_ordered_blocks(nb < 2048 ? nb : 2048, cols, 2);
+  return (int)((rows + nb - 1) / nb);
+}
+
+static int bias_scale_res_bwd_launch(const void* g, const void* x, const void* bias, const void* scale, void* dx, float* d_bias, float* d_scale,
+                                     int64_t rows, int cols, float* part, hipStream_t st) {
+  static std::atomic<unsigned long long> attr_set{0};
+  vita_device_once(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bias_scale_res_bwd_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bias_scale_res_bwd_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+  });
+  const dim3 block(cols / 8 < 256 ? (cols / 8 + 63) / 64 * 64 : 256);
+  if (!part || (!d_bias && !d_scale)) {
+    const int rpb = 64;
+    hipLaunchKernelGGL(bias_scale_res_bwd_kernel<false>, dim3((unsigned)((rows + rpb - 1) / rpb)), block,
+                       (size_t)cols * 8, st, (const bf16_t*)g, (const bf16_t*)x, (const bf16_t*)bias, (const bf16_t*)scale,
+                       (bf16_t*)dx, d_bias, d_scale, rows, cols, rpb);
+    return vita_check_launch();
+  }
+  const int rpb = bias_scale_res_ordered_rpb(rows, cols);
+  const int64_t nb = (rows + rpb - 1) / rpb;
+  hipLaunchKernelGGL(bias_scale_res_bwd_kernel<true>, dim3((unsigned)nb), block, (size_t)cols * 8, st, (const bf16_t*)g, (const bf16_t*)x,
+                     (const bf16_t*)bias, (const bf16_t*)scale, (bf16_t*)dx, d_bias ? part : nullptr, d_scale ? part + nb * cols : nullptr,
+                     rows, cols, rpb);
+  const int rc = vita_check_launch();
+  if (rc != VITA_OK) return rc;
+  return vita_ordered_finish(part, nb, cols, d_bias, d_scale, st);
+}
+
 extern "C" int vita_bias_scale_res_bwd(const void* g, const void* x, const void* bias, const void* scale, void* dx, float* d_bias,
                                        float* d_scale, int64_t rows, int cols, void* stream) {
   if (!g || !x || rows < 0 || cols <= 0) return VITA_ERR_INVALID_ARG;
   if (cols & 7) return VITA_ERR_UNSUPPORTED;
   if (rows == 0) return VITA_OK;
   if (cols > 8192) return VITA_ERR_UNSUPPORTED;       // the flush image: 2 x cols floats of LDS
-  static std::atomic<unsigned long long> attr_set{0};
-  vita_device_once(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&bias_scale_res_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
-  });
-  const int rpb = 64;
-  hipLaunchKernelGGL(bias_scale_res_bwd_kernel, dim3((unsigned)((rows + rpb - 1) / rpb)), dim3(cols / 8 < 256 ? (cols / 8 + 63) / 64 * 64 : 256),
-                     (size_t)cols * 8, (hipStream_t)stream, (const bf16_t*)g, (const bf16_t*)x, (const bf16_t*)bias, (const bf16_t*)scale,
-                     (bf16_t*)dx, d_bias, d_scale, rows, cols, rpb);
-  return vita_check_launch();
+  return bias_scale_res_bwd_launch(g, x, bias, scale, dx, d_bias, d_scale, rows, cols, nullptr, (hipStream_t)stream);
+}
+
+extern "C" size_t vita_bias_scale_res_bwd_workspace_bytes(int64_t rows, int cols) {
+  if (rows <= 0 || cols <= 0 || (cols & 7) || cols > 8192) return 0;
+  const int rpb = bias_scale_res_ordered_rpb(rows, cols);
+  return 2 * (size_t)((rows + rpb - 1) / rpb) * (size_t)cols * sizeof(float);
+}
+
+extern "C" int vita_bias_scale_res_bwd_ordered(const void* g, const void* x, const void* bias, const void* scale, void* dx, float* d_bias,
+                                               float* d_scale, int64_t rows, int cols, void* workspace, void* stream) {
+  if (!g || !x || rows < 0 || cols <= 0 || (rows > 0 && !workspace)) return VITA_ERR_INVALID_ARG;
+  if ((cols & 7) || cols > 8192 || ((uintptr_t)workspace & 15)) return VITA_ERR_UNSUPPORTED;
+  if (rows == 0) return VITA_OK;
+  return bias_scale_res_bwd_launch(g, x, bias, scale, dx, d_bias, d_scale, rows, cols, (float*)workspace, (hipStream_t)stream);
 }
 
 extern "C" int vita_layernorm_param_grad(const void* dy, const void* x, float* dgamma, float* dbeta,
@@ -978,12 +1280,45 @@ extern "C" int vita_layernorm_param_grad(const void* dy, const void* x, float* d
   dim3 grid((unsigned)((rows + 3) / 4 < 1024 ? (rows + 3) / 4 : 1024)), block(256);
   hipStream_t st = (hipStream_t)stream;
   if (cols <= 4096)
-    hipLaunchKernelGGL(layernorm_param_grad_kernel<8>, grid, block, 0, st, (const bf16_t*)dy,
+    hipLaunchKernelGGL((layernorm_param_grad_kernel<8, false>), grid, block, 0, st, (const bf16_t*)dy,
                        (const bf16_t*)x, dgamma, dbeta, rows, cols, eps, prenormalized);
   else
-    hipLaunchKernelGGL(layernorm_param_grad_kernel<16>, grid, block, 0, st, (const bf16_t*)dy,
+    hipLaunchKernelGGL((layernorm_param_grad_kernel<16, false>), grid, block, 0, st, (const bf16_t*)dy,
                        (const bf16_t*)x, dgamma, dbeta, rows, cols, eps, prenormalized);
   return vita_check_launch();
+}
+
+static int64_t layernorm_param_grad_ordered_blocks(int64_t rows, int cols) {
+  return vita_ordered_blocks((rows + 3) / 4 < 1024 ? (rows + 3) / 4 : 1024, cols, 2);
+}
+
+extern "C" size_t vita_layernorm_param_grad_workspace_bytes(int64_t rows, int cols) {
+  if (rows <= 0 || cols <= 0 || (cols & 7) || cols > 8192) return 0;
+  return 2 * (size_t)layernorm_param_grad_ordered_blocks(rows, cols) * (size_t)cols * sizeof(float);
+}
+
+extern "C" int vita_layernorm_param_grad_ordered(const void* dy, const void* x, float* dgamma, float* dbeta, int64_t rows, int cols, float eps,
+                                                 int prenormalized, void* workspace, void* stream) {
+  if (!dy || !x || !dgamma || !dbeta || rows < 0 || cols <= 0 || (rows > 0 && !workspace)) return VITA_ERR_INVALID_ARG;
+  if ((cols & 7) || cols > 8192 || ((uintptr_t)workspace & 15)) return VITA_ERR_UNSUPPORTED;
+  if (rows == 0) return VITA_OK;
+  const int64_t nb = layernorm_param_grad_ordered_blocks(rows, cols);
+  float* part = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  static std::atomic<unsigned long long> attr_set{0};           // the wave-sum image: 8 cols bytes of dynamic LDS (64 KiB at 8192)
+  vita_device_once(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&layernorm_param_grad_kernel<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                              65536);
+  });
+  if (cols <= 4096)
+    hipLaunchKernelGGL((layernorm_param_grad_kernel<8, true>), dim3((unsigned)nb), dim3(256), (size_t)cols * 8, st, (const bf16_t*)dy,
+                       (const bf16_t*)x, part, part + nb * cols, rows, cols, eps, prenormalized);
+  else
+    hipLaunchKernelGGL((layernorm_param_grad_kernel<16, true>), dim3((unsigned)nb), dim3(256), (size_t)cols * 8, st, (const bf16_t*)dy,
+                       (const bf16_t*)x, part, part + nb * cols, rows, cols, eps, prenormalized);
+  const int rc = vita_check_launch();
+  if (rc != VITA_OK) return rc;
+  return vita_ordered_finish(part, nb, cols, dgamma, dbeta, st);
 }
 
 extern "C" int vita_ce_loss(const void* logits, int64_t ld, const int64_t* labels, float* loss,
@@ -1054,6 +1389,37 @@ extern "C" int vita_row_scatter_add_f32(const void* src, const int64_t* idx, flo
   if (n == 0) return VITA_OK;
   hipLaunchKernelGGL(row_scatter_add_kernel, dim3(grid_for(n * (cols / 2), 256)), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)src, idx, dst, dst_rows, n, cols, err_flag);
+  return vita_check_launch();
+}
+
+// ABI 19: the ordered embedding gradient (row_scatter_sorted_kernel); workspace = fp32 [ceil(n / 256)][cols]
+extern "C" size_t vita_row_scatter_add_workspace_bytes(int64_t n, int cols) {
+  if (n <= 0 || cols <= 0) return 0;
+  return (size_t)((n + SCATTER_CHUNK - 1) / SCATTER_CHUNK) * (size_t)cols * sizeof(float);
+}
+
+extern "C" int vita_row_scatter_add_f32_sorted(const void* src, const int64_t* sorted_idx, const int64_t* order, float* dst, int64_t dst_rows,
+                                               int64_t n, int cols, void* workspace, int* err_flag, void* stream) {
+  if (!src || !sorted_idx || !order || !dst || n < 0 || cols <= 0 || dst_rows < 0 || (n > 0 && !workspace)) return VITA_ERR_INVALID_ARG;
+  if ((cols & 7) || (((uintptr_t)src | (uintptr_t)dst | (uintptr_t)workspace) & 15)) return VITA_ERR_UNSUPPORTED;
+  if (n == 0) return VITA_OK;
+  const int64_t nslab = (cols / 8 + 63) / 64, nch = (n + SCATTER_CHUNK - 1) / SCATTER_CHUNK;
+  const int64_t blocks = (nch * nslab + 3) / 4;
+  if (blocks > 0x7fffffff) return VITA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(row_scatter_sorted_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)src, sorted_idx, order, dst, dst_rows,
+                     n, cols, (float*)workspace, err_flag);
+  int rc = vita_check_launch();
+  if (rc != VITA_OK || nch == 1) return rc;
+  hipLaunchKernelGGL(row_scatter_sorted_owner_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const bf16_t*)src, sorted_idx, order, dst,
+                     dst_rows, n, cols, (const float*)workspace);
+  return vita_check_launch();
+}
+
+int vita_ordered_finish(const float* part, int64_t blocks, int cols, float* acc0, float* acc1, hipStream_t stream) {
+  if (!acc0 && !acc1) return VITA_OK;
+  hipLaunchKernelGGL(ordered_finish_kernel, dim3((unsigned)((cols + 255) / 256), acc1 ? 2 : 1), dim3(256), 0, stream, part, acc0, acc1,
+                     (int)blocks, cols);
   return vita_check_launch();
 }
 

@@ -149,7 +149,8 @@ __global__ __launch_bounds__(256) void pixel_shuffle_ln_kernel(const bf16_t* __r
 // (NORM = false: dx[source positions] = dy).  dx (may be NULL: frozen encoder, parameter gradients only) has x's strides; the class
 // token's row receives zeros (vit_output[:, 1:, :] drops it, M/pretrain_long_vita.py:454-455).  Parameter gradients: per-lane
 // registers, summed over the workgroup's waves in LDS, flushed with fp32 atomics on consecutive columns (caller zeroes them).
-template <int VPL, bool NORM>
+// ORDERED (ABI 19): dgamma / dbeta are the workspace rows [blocks][cols]; the LDS image goes to row blockIdx.x (vita_common.h).
+template <int VPL, bool NORM, bool ORDERED>
 __global__ __launch_bounds__(256) void pixel_shuffle_ln_bwd_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                                    const bf16_t* __restrict__ w, bf16_t* __restrict__ dx,
                                                                    float* __restrict__ dgamma, float* __restrict__ dbeta,
@@ -276,6 +277,11 @@ __global__ __launch_bounds__(256) void pixel_shuffle_ln_bwd_kernel(const bf16_t*
     }
     __syncthreads();
   }
+  if (ORDERED) {
+    vita_store_image_row(pg_lds, dgamma + (int64_t)blockIdx.x * cols, nvec);
+    vita_store_image_row(pg_lds + cols, dbeta + (int64_t)blockIdx.x * cols, nvec);
+    return;
+  }
   for (int i = threadIdx.x; i < cols; i += 256) {
     const int at = (i & 7) * nvec + (i >> 3);
     atomicAdd(dgamma + i, pg_lds[at]);
@@ -396,10 +402,40 @@ extern "C" int vita_pixel_shuffle_ln_bwd(const void* dy, const void* x, const vo
   dim3 g((unsigned)((toks + 3) / 4 < 512 ? (toks + 3) / 4 : 512)), blk(256);
   hipStream_t st = (hipStream_t)stream;
   if (norm)
-    hipLaunchKernelGGL((pixel_shuffle_ln_bwd_kernel<8, true>), g, blk, (size_t)cols * 8, st, (const bf16_t*)dy, (const bf16_t*)x,
+    hipLaunchKernelGGL((pixel_shuffle_ln_bwd_kernel<8, true, false>), g, blk, (size_t)cols * 8, st, (const bf16_t*)dy, (const bf16_t*)x,
                        (const bf16_t*)w, (bf16_t*)dx, dgamma, dbeta, n, grid, hidden, has_cls, eps, img_stride, tok_stride);
   else
-    hipLaunchKernelGGL((pixel_shuffle_ln_bwd_kernel<8, false>), g, blk, 0, st, (const bf16_t*)dy, (const bf16_t*)x,
+    hipLaunchKernelGGL((pixel_shuffle_ln_bwd_kernel<8, false, false>), g, blk, 0, st, (const bf16_t*)dy, (const bf16_t*)x,
                        (const bf16_t*)w, (bf16_t*)dx, dgamma, dbeta, n, grid, hidden, has_cls, eps, img_stride, tok_stride);
   return vita_check_launch();
+}
+
+// ABI 19: the ordered form (vita_common.h).  rows = n (grid / 2)^2 tokens, cols = 4 hidden; workspace = fp32 [2][blocks][cols]
+static int64_t pixel_shuffle_ln_bwd_blocks(int64_t rows, int cols) {
+  return vita_ordered_blocks((rows + 3) / 4 < 512 ? (rows + 3) / 4 : 512, cols, 2);
+}
+
+extern "C" size_t vita_pixel_shuffle_ln_bwd_workspace_bytes(int64_t rows, int cols) {
+  if (rows <= 0 || cols <= 0) return 0;
+  return 2 * (size_t)pixel_shuffle_ln_bwd_blocks(rows, cols) * (size_t)cols * sizeof(float);
+}
+
+extern "C" int vita_pixel_shuffle_ln_bwd_ordered(const void* dy, const void* x, const void* w, void* dx, float* dgamma, float* dbeta,
+                                                 int64_t n, int grid, int hidden, int has_cls, float eps, int64_t img_stride,
+                                                 int64_t tok_stride, void* workspace, void* stream) {
+  if (!dy || !x || !w || !dgamma || !dbeta || n < 0 || grid <= 0 || hidden <= 0 || (n > 0 && !workspace)) return VITA_ERR_INVALID_ARG;
+  if ((grid & 1) || (hidden & 7) || hidden * 4 > 4096 || ((img_stride | tok_stride) & 7) || ((uintptr_t)workspace & 15))
+    return VITA_ERR_UNSUPPORTED;
+  if (n == 0) return VITA_OK;
+  const int64_t toks = n * (grid / 2) * (grid / 2);
+  const int cols = hidden * 4;
+  const int64_t nb = pixel_shuffle_ln_bwd_blocks(toks, cols);
+  float* part = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL((pixel_shuffle_ln_bwd_kernel<8, true, true>), dim3((unsigned)nb), dim3(256), (size_t)cols * 8, st, (const bf16_t*)dy,
+                     (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)dx, part, part + nb * cols, n, grid, hidden, has_cls, eps, img_stride,
+                     tok_stride);
+  const int rc = vita_check_launch();
+  if (rc != VITA_OK) return rc;
+  return vita_ordered_finish(part, nb, cols, dgamma, dbeta, st);
 }

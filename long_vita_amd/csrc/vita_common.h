@@ -128,6 +128,35 @@ static inline int vita_check_launch() {
   return e == hipSuccess ? VITA_OK : VITA_ERR_LAUNCH;
 }
 
+// ---- ordered (deterministic) parameter-gradient reductions (ABI 19) ------------------------------------------------------------
+// The *_ordered launchers run the same kernels with ORDERED = true: workgroup b writes its column sums with plain 16-byte stores to
+// row b of a workspace [n_grads][blocks][cols] instead of adding them to the caller's buffer with fp32 atomics (which land in arrival
+// order), and vita_ordered_finish (bwd.hip) then forms acc[c] = ((acc[c] + part[0][c]) + part[1][c]) + ... in ascending block order.
+// The block count is a function of (rows, cols) only, never of a device query, and the workspace stays within 32 MiB.
+inline int64_t vita_ordered_blocks(int64_t blocks, int cols, int n_grads) {
+  const int64_t cap = (int64_t(32) << 20) / ((int64_t)n_grads * cols * (int64_t)sizeof(float));
+  return blocks < cap ? blocks : (cap < 1 ? 1 : cap);
+}
+// acc0 / acc1 (either may be null) += the partial rows part[0] / part[1], each [blocks][cols], in block order; part 16-byte aligned
+int vita_ordered_finish(const float* part, int64_t blocks, int cols, float* acc0, float* acc1, hipStream_t stream);
+
+// the ORDERED flush of an LDS image laid out [8][nvec] (column vi * 8 + j of the workgroup's sum at img[j * nvec + vi], the layout the
+// atomic flushes read): row = this workgroup's row of the workspace, written with 16-byte stores
+__device__ __forceinline__ void vita_store_image_row(const float* img, float* row, int nvec) {
+  for (int vi = threadIdx.x; vi < nvec; vi += blockDim.x) {
+    f32x4 lo, hi;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { lo[j] = img[j * nvec + vi]; hi[j] = img[(j + 4) * nvec + vi]; }
+    *reinterpret_cast<f32x4*>(row + vi * 8) = lo;
+    *reinterpret_cast<f32x4*>(row + vi * 8 + 4) = hi;
+  }
+}
+__device__ __forceinline__ void vita_store_row8(float* p, const float* v) {
+  const f32x4 lo = {v[0], v[1], v[2], v[3]}, hi = {v[4], v[5], v[6], v[7]};
+  *reinterpret_cast<f32x4*>(p) = lo;
+  *reinterpret_cast<f32x4*>(p + 4) = hi;
+}
+
 // ---- LDS-DMA issued from inline asm ------------------------------------------------------------------------------------------
 // `buffer_load_dword[x4] ... lds` moves 4 / 16 bytes per lane from a buffer address (descriptor base + per-lane byte offset) to
 // LDS address m0 + lane * size.  Issued through the compiler's builtin, hipcc remembers that an LDS write is in flight and puts

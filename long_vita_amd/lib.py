@@ -23,7 +23,7 @@ if os.environ.get("VITA_HIP_LIB"):                    # developer A / B switch: 
     LIB_PATH = os.path.abspath(os.environ["VITA_HIP_LIB"])
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "vita_hip.h")
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 VITA_OK = 0
 VITA_ERR_INVALID_ARG = -1
 VITA_ERR_UNSUPPORTED = -2
@@ -181,6 +181,19 @@ PROTOTYPES = {
     "vita_ce_vp_finish": (_i, [_p, _i, _l, _p, _p, _p]),
     "vita_ce_vp_grad": (_i, [_p, _i, _l, _p, _l, _p, _p, _p, _l, _l, _i, _p]),
     "vita_row_scatter_add_f32": (_i, [_p, _p, _p, _l, _l, _i, _p, _p]),
+    # ABI 19: the ordered (deterministic) parameter-gradient reductions
+    "vita_rmsnorm_bwd_workspace_bytes": (C.c_size_t, [_l, _i]),
+    "vita_rmsnorm_bwd_ordered": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _f, _p, _p]),
+    "vita_layernorm_bwd_workspace_bytes": (C.c_size_t, [_l, _i]),
+    "vita_layernorm_bwd_ordered": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _f, _p, _p]),
+    "vita_bias_scale_res_bwd_workspace_bytes": (C.c_size_t, [_l, _i]),
+    "vita_bias_scale_res_bwd_ordered": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _i, _p, _p]),
+    "vita_layernorm_param_grad_workspace_bytes": (C.c_size_t, [_l, _i]),
+    "vita_layernorm_param_grad_ordered": (_i, [_p, _p, _p, _p, _l, _i, _f, _i, _p, _p]),
+    "vita_pixel_shuffle_ln_bwd_workspace_bytes": (C.c_size_t, [_l, _i]),
+    "vita_pixel_shuffle_ln_bwd_ordered": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _i, _i, _f, _l, _l, _p, _p]),
+    "vita_row_scatter_add_workspace_bytes": (C.c_size_t, [_l, _i]),
+    "vita_row_scatter_add_f32_sorted": (_i, [_p, _p, _p, _p, _l, _l, _i, _p, _p, _p]),
     "vita_attn_delta": (_i, [_p, _p, _p, _l, _i, _i, _l, _l, _l, _l, _p]),
     "vita_flash_attn_bwd": (_i, [C.POINTER(AttnBwdParams), _p]),
     "vita_flash_attn_bwd_parts": (_i, [C.POINTER(AttnBwdParams), _i, _p]),

@@ -6,6 +6,7 @@ fallback and nothing here imports ``oracle/``.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
 import os
@@ -34,6 +35,45 @@ def _dev(t: torch.Tensor, name: str, dtype=None) -> int:
 
 def _opt(t: Optional[torch.Tensor], name: str, dtype=None) -> Optional[int]:
     return None if t is None else _dev(t, name, dtype)
+
+
+# ------------------------------------------------------------------------------------------------
+# deterministic mode (ABI 19)
+# ------------------------------------------------------------------------------------------------
+# The backward's parameter-gradient reductions (RMSNorm / LayerNorm weights, ViT bias and LayerScale, the word embedding) add their
+# workgroups' sums with fp32 atomics, in arrival order.  With the mode on, the wrappers below call the *_ordered entries instead: the
+# same kernels store their partial sums and a finish pass adds them in a fixed order, so every gradient is bit-identical from run to
+# run.  None follows torch.are_deterministic_algorithms_enabled(); the setting is process-wide (the simulated CP / TP ranks are threads).
+_deterministic: Optional[bool] = None
+
+
+def set_deterministic(mode: Optional[bool]) -> None:
+    """True / False force the ordered / atomic reductions; None (the default) follows torch.use_deterministic_algorithms."""
+    global _deterministic
+    if mode is not None and not isinstance(mode, bool):
+        raise TypeError("mode must be True, False or None")
+    _deterministic = mode
+
+
+def deterministic_enabled() -> bool:
+    return torch.are_deterministic_algorithms_enabled() if _deterministic is None else _deterministic
+
+
+@contextlib.contextmanager
+def deterministic(mode: Optional[bool] = True):
+    """set_deterministic(mode) for the duration of a with-block; the previous setting comes back on exit."""
+    prev = _deterministic
+    set_deterministic(mode)
+    try:
+        yield
+    finally:
+        set_deterministic(prev)
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """A per-call fp32 workspace from torch's caching allocator (16-byte aligned; stream-ordered, so rank threads and graph capture
+    each get their own)."""
+    return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.float32, device=device)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -592,6 +632,14 @@ def pixel_shuffle_ln_bwd(dy: torch.Tensor, x: torch.Tensor, weight: Optional[tor
         # dx is written with x's strides: give it the same layout ([s, b, h] memory, viewed [n, seq, h])
         dx = torch.empty_strided((n, seq, hidden), x.stride(), dtype=BF16, device=x.device)
     si, st = _img_tok_strides(x)
+    if norm and deterministic_enabled():
+        h = _L.load()
+        ws = _workspace(h.vita_pixel_shuffle_ln_bwd_workspace_bytes(n * (grid // 2) ** 2, 4 * hidden), x.device)
+        _L.check(h.vita_pixel_shuffle_ln_bwd_ordered(_dev(dy.contiguous(), "dy", BF16), _dev(x, "x", BF16), _opt(weight, "weight", BF16),
+                                                     _opt(dx, "dx", BF16), _opt(dgamma, "dgamma", torch.float32),
+                                                     _opt(dbeta, "dbeta", torch.float32), n, grid, hidden, int(has_cls), float(eps), si, st,
+                                                     _dev(ws, "workspace", torch.float32), _stream()), "vita_pixel_shuffle_ln_bwd_ordered")
+        return dx
     _L.check(_L.load().vita_pixel_shuffle_ln_bwd(_dev(dy.contiguous(), "dy", BF16), _dev(x, "x", BF16), _opt(weight, "weight", BF16),
                                                  _opt(dx, "dx", BF16), _opt(dgamma, "dgamma", torch.float32),
                                                  _opt(dbeta, "dbeta", torch.float32), n, grid, hidden, int(has_cls), float(eps),
@@ -626,6 +674,14 @@ def rmsnorm_bwd(dy, x, weight, eps: float, dw_acc: Optional[torch.Tensor] = None
     rows = x.numel() // cols
     dx = torch.empty_like(x) if out is None else out
     if rows == 0:
+        return dx
+    if dw_acc is not None and deterministic_enabled():
+        h = _L.load()
+        ws = _workspace(h.vita_rmsnorm_bwd_workspace_bytes(rows, cols), x.device)
+        _L.check(h.vita_rmsnorm_bwd_ordered(_dev(dy, "dy", BF16), _dev(x, "x", BF16), _dev(weight, "weight", BF16),
+                                            _opt(residual, "residual", BF16), _dev(dx, "dx", BF16), _dev(dw_acc, "dw_acc", torch.float32),
+                                            rows, cols, float(eps), _dev(ws, "workspace", torch.float32), _stream()),
+                 "vita_rmsnorm_bwd_ordered")
         return dx
     _L.check(_L.load().vita_rmsnorm_bwd(_dev(dy, "dy", BF16), _dev(x, "x", BF16), _dev(weight, "weight", BF16),
                                         _opt(residual, "residual", BF16), _dev(dx, "dx", BF16), _opt(dw_acc, "dw_acc", torch.float32), rows, cols,
@@ -670,6 +726,14 @@ def layernorm_bwd(dy: torch.Tensor, x: torch.Tensor, weight: torch.Tensor, eps: 
     dx = torch.empty_like(x) if out is None else out
     if x.numel() == 0:                      # an empty frame batch: no rows, dgamma / dbeta stay as the caller zeroed them
         return dx
+    if deterministic_enabled():
+        h = _L.load()
+        rows = x.numel() // cols
+        ws = _workspace(h.vita_layernorm_bwd_workspace_bytes(rows, cols), x.device)
+        _L.check(h.vita_layernorm_bwd_ordered(_dev(dy, "dy", BF16), _dev(x, "x", BF16), _dev(weight, "weight", BF16), _dev(dx, "dx", BF16),
+                                              _dev(dgamma, "dgamma", torch.float32), _dev(dbeta, "dbeta", torch.float32), rows, cols,
+                                              float(eps), _dev(ws, "workspace", torch.float32), _stream()), "vita_layernorm_bwd_ordered")
+        return dx
     _L.check(_L.load().vita_layernorm_bwd(_dev(dy, "dy", BF16), _dev(x, "x", BF16), _dev(weight, "weight", BF16), _dev(dx, "dx", BF16),
                                           _dev(dgamma, "dgamma", torch.float32), _dev(dbeta, "dbeta", torch.float32),
                                           x.numel() // cols, cols, float(eps), _stream()), "vita_layernorm_bwd")
@@ -703,6 +767,15 @@ def bias_scale_residual_bwd(g: torch.Tensor, x: torch.Tensor, bias, scale, d_bia
     dx = torch.empty_like(x) if scale is not None else None
     if x.numel() == 0:
         return g if dx is None else dx
+    if (d_bias is not None or d_scale is not None) and deterministic_enabled():
+        h = _L.load()
+        rows = x.numel() // cols
+        ws = _workspace(h.vita_bias_scale_res_bwd_workspace_bytes(rows, cols), x.device)
+        _L.check(h.vita_bias_scale_res_bwd_ordered(_dev(g, "g", BF16), _dev(x, "x", BF16), _opt(bias, "bias", BF16), _opt(scale, "scale", BF16),
+                                                   _opt(dx, "dx", BF16), _opt(d_bias, "d_bias", torch.float32),
+                                                   _opt(d_scale, "d_scale", torch.float32), rows, cols, _dev(ws, "workspace", torch.float32),
+                                                   _stream()), "vita_bias_scale_res_bwd_ordered")
+        return g if dx is None else dx
     _L.check(_L.load().vita_bias_scale_res_bwd(_dev(g, "g", BF16), _dev(x, "x", BF16), _opt(bias, "bias", BF16), _opt(scale, "scale", BF16),
                                                _opt(dx, "dx", BF16), _opt(d_bias, "d_bias", torch.float32),
                                                _opt(d_scale, "d_scale", torch.float32), x.numel() // cols, cols, _stream()),
@@ -713,6 +786,14 @@ def bias_scale_residual_bwd(g: torch.Tensor, x: torch.Tensor, bias, scale, d_bia
 def layernorm_param_grad(dy, x, dgamma: torch.Tensor, dbeta: torch.Tensor, eps: float,
                          prenormalized: bool = False) -> None:
     cols = x.shape[-1]
+    rows = x.numel() // cols
+    if rows and deterministic_enabled():
+        h = _L.load()
+        ws = _workspace(h.vita_layernorm_param_grad_workspace_bytes(rows, cols), x.device)
+        _L.check(h.vita_layernorm_param_grad_ordered(_dev(dy, "dy", BF16), _dev(x, "x", BF16), _dev(dgamma, "dgamma", torch.float32),
+                                                     _dev(dbeta, "dbeta", torch.float32), rows, cols, float(eps), int(prenormalized),
+                                                     _dev(ws, "workspace", torch.float32), _stream()), "vita_layernorm_param_grad_ordered")
+        return
     _L.check(_L.load().vita_layernorm_param_grad(_dev(dy, "dy", BF16), _dev(x, "x", BF16),
                                                  _dev(dgamma, "dgamma", torch.float32),
                                                  _dev(dbeta, "dbeta", torch.float32), x.numel() // cols, cols,
@@ -799,6 +880,19 @@ def row_scatter_add_f32_(dst: torch.Tensor, idx: torch.Tensor, src: torch.Tensor
     if n == 0:
         return dst
     flag = _err_flag(dst.device)
+    if deterministic_enabled():
+        # no atomics: stable-sort the ids (rows ascending among equal ids), then every destination row is summed in row order and
+        # written once (vita_row_scatter_add_f32_sorted)
+        h = _L.load()
+        sorted_idx, order = torch.sort(idx.reshape(-1), stable=True)
+        src_c = src.contiguous()
+        ws = _workspace(h.vita_row_scatter_add_workspace_bytes(n, cols), dst.device)
+        _L.check(h.vita_row_scatter_add_f32_sorted(_dev(src_c, "src", BF16), _dev(sorted_idx, "idx", torch.int64), _dev(order, "order", torch.int64),
+                                                   _dev(dst, "dst", torch.float32), dst.shape[0], n, cols, _dev(ws, "workspace", torch.float32),
+                                                   _dev(flag, "flag"), _stream()), "vita_row_scatter_add_f32_sorted")
+        if int(flag.item()):
+            raise IndexError("vita_row_scatter_add_f32: index out of range")
+        return dst
     _L.check(_L.load().vita_row_scatter_add_f32(_dev(src, "src", BF16), _dev(idx.contiguous(), "idx", torch.int64),
                                                 _dev(dst, "dst", torch.float32), dst.shape[0], n, cols,
                                                 _dev(flag, "flag"), _stream()), "vita_row_scatter_add_f32")

@@ -332,8 +332,24 @@ def gpt_vl_model_init_wrapper(fn):
     def wrapper(self, *args, **kwargs):
         fn(self, *args, **kwargs)
         install_hip_vision_path(getattr(self, "external_feature_model", None))
+        follow_use_deter_comp()
 
     return wrapper
+
+
+def follow_use_deter_comp() -> bool:
+    """The reference's `--use-deter-comp` ("enable deterministic computing", M/training/arguments.py:557): when Megatron's parsed
+    arguments carry it set, turn the library's deterministic mode on (ops.set_deterministic: ordered parameter-gradient reductions,
+    bit-identical from run to run).  Without Megatron's globals, or without the attribute, the mode is left as it is."""
+    try:
+        from megatron.training import get_args
+        args = get_args()
+    except (ImportError, AttributeError, AssertionError):     # no Megatron / arguments not parsed yet
+        return False
+    if getattr(args, "use_deter_comp", False):
+        ops.set_deterministic(True)
+        return True
+    return False
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
