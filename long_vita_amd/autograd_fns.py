@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 import torch.distributed as dist
 
-from . import ops, parallel_state as mpu
+from . import context_parallel as cpl, ops, parallel_state as mpu
 
 
 # ------------------------------------------------------------------------------------------------
@@ -43,6 +43,15 @@ def wgrad(dy_t: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     return ops.gemm(dy_t, transpose(x))
 
 
+def wgrad_tn(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """wgrad from the operands AS THE FORWARD LEFT THEM: dy [M, N], x [M, K] -> [N, K] through vita_gemm_bf16_tn (both operands
+    contraction-major, no transposed copies); shapes the kernel does not tile (output dims not multiples of 256) take two
+    vita_transpose_bf16 passes and the NT GEMM."""
+    if ops.gemm_tn_ok(dy, x):
+        return ops.gemm_tn(dy, x)
+    return wgrad(transpose(dy), x)
+
+
 def bias_grad(dy: torch.Tensor) -> torch.Tensor:
     """grad_bias = grad_output.sum(dim=0) (layers.py:524): dy [rows, N] -> [N], one pass over dy (vita_colsum_bf16, fp32 sums; through
     r03 a GEMM against a block of ones: a whole-sequence contraction on N / 256 workgroups)."""
@@ -59,8 +68,7 @@ def _tp():
 
 def weight_bias_grads(go: torch.Tensor, x: torch.Tensor, need_weight: bool, need_bias: bool, n_out: int, dtype):
     """grad_weight = grad_output.t().matmul(total_input), grad_bias = grad_output.sum(dim=0) (layers.py:522-524) for go [rows, n_out],
-    x [rows, k].  The TN kernel takes both operands contraction-major as they are; shapes it does not tile (output dims not multiples
-    of 256) go through two vita_transpose_bf16 passes and the NT GEMM.  No rows (an empty logit-mask selection on this rank): zeros."""
+    x [rows, k], rows zero-padded to the GEMMs' contraction granule.  No rows (an empty logit-mask selection on this rank): zeros."""
     grad_weight = grad_bias = None
     if go.shape[0] == 0:
         if need_weight:
@@ -73,11 +81,7 @@ def weight_bias_grads(go: torch.Tensor, x: torch.Tensor, need_weight: bool, need
     if need_bias:
         grad_bias = bias_grad(go).to(dtype)                                               # :524
     if need_weight:
-        go_p, x_p = pad_rows(go), pad_rows(x.contiguous())
-        if ops.gemm_tn_ok(go_p, x_p):            # both operands contraction-major as they are: no transposed copies
-            grad_weight = ops.gemm_tn(go_p, x_p)                                          # :522-523
-        else:
-            grad_weight = wgrad(transpose(go_p), x_p)
+        grad_weight = wgrad_tn(pad_rows(go), pad_rows(x.contiguous()))                    # :522-523
     return grad_weight, grad_bias
 
 
@@ -545,17 +549,6 @@ class FlashAttnNonCausalFn(torch.autograd.Function):
         return unpad(dq), unpad(dk), unpad(dv), None
 
 
-def zigzag_geometry(cp: int, rank: int, s_l: int) -> dict:
-    """Chunk tables of the rank-ordered gathered K / V buffer [CP][2][S_l] rows (K rows of rank p at p * 2 * S_l, V at + S_l):
-    chunk 2p + h of the buffer is global chunk (h ? 2CP - 1 - p : p) (M/training/utils.py:329-341)."""
-    c = s_l // 2
-    kv_gid, kv_row = [], []
-    for p in range(cp):
-        kv_gid += [p, 2 * cp - 1 - p]
-        kv_row += [p * 2 * s_l, p * 2 * s_l + c]
-    return dict(chunk_len=c, q_chunk_gid=mpu.zigzag_chunk_ids(cp, rank), kv_chunk_gid=kv_gid, kv_chunk_row=kv_row)
-
-
 class FlashAttnCPFn(torch.autograd.Function):
     """Context-parallel causal attention as ONE autograd node — what TransformerEngine's AttnFuncWithCP is to the reference's TE
     layer spec (M/core/models/gpt/gpt_layer_specs.py:40; every long-context script trains with CP, stage3 .sh:125,145).
@@ -573,13 +566,8 @@ class FlashAttnCPFn(torch.autograd.Function):
         its result is kept for the replay (recompute_cache)."""
         _, s_l, hq, d = q.shape
         hkv = k.shape[2]
-        if s_l % 2:
-            raise ValueError("local sequence must hold two zig-zag chunks")
         n_split = ops.cp_kv_split(hkv, hq, s_l)                            # gather j + 1 runs under the attention of split j
-        hg = hkv // n_split
-        kv_local = torch.empty(n_split, 2, s_l, hg, d, dtype=q.dtype, device=q.device)
-        kv_local[:, 0].copy_(k[0].reshape(s_l, n_split, hg, d).permute(1, 0, 2, 3))
-        kv_local[:, 1].copy_(v[0].reshape(s_l, n_split, hg, d).permute(1, 0, 2, 3))
+        kv_local = cpl.pack_kv(k, v, n_split)
         lse = torch.empty(1, hq, s_l, dtype=torch.float32, device=q.device)
         o = torch.empty(1, s_l, hq, d, dtype=q.dtype, device=q.device)
         impl.forward_cp(q.reshape(1, s_l, hkv, hq // hkv, d), kv_local, out=o, lse=lse)
@@ -607,36 +595,32 @@ class FlashAttnCPFn(torch.autograd.Function):
         n_split = ops.cp_kv_split(hkv, hq, s_l)
         hg, qpg = hkv // n_split, hq // hkv
         d_o = d_o.contiguous()
-        kv_local = torch.empty(n_split, 2, s_l, hg, d, dtype=q.dtype, device=q.device)        # the packed send buffers, one per split
-        kv_local[:, 0].copy_(k[0].reshape(s_l, n_split, hg, d).permute(1, 0, 2, 3))
-        kv_local[:, 1].copy_(v[0].reshape(s_l, n_split, hg, d).permute(1, 0, 2, 3))
+        kv_local = cpl.pack_kv(k, v, n_split)                                                # the packed send buffers, one per split
         gathered = torch.empty(n_split, cp * kv_local[0].numel(), dtype=q.dtype, device=q.device)
         gathers = [dist.all_gather_into_tensor(gathered[j], kv_local[j].reshape(-1), group=group, async_op=True) for j in range(n_split)]
-        d_rows = torch.empty_like(gathered)                                                  # dK rows of rank p at p * 2 * S_l, dV at + S_l
+        d_rows = torch.empty_like(gathered)                                                  # dK / dV in the gathered layout
         dkv = torch.empty(n_split, kv_local[0].numel(), dtype=q.dtype, device=q.device)
         dq = torch.empty(q.shape, dtype=q.dtype, device=q.device)
-        geo = zigzag_geometry(cp, r, s_l)
+        geo = cpl.chunk_tables(cp, r, s_l)
         q5, dq5 = q.view(1, s_l, hkv, qpg, d), dq.view(1, s_l, hkv, qpg, d)
         delta, reduces = None, []
         for j in range(n_split):
             if gathers[j] is not None:
                 gathers[j].wait()
-            rows, drows = gathered[j].view(cp * 2 * s_l, hg, d), d_rows[j].view(cp * 2 * s_l, hg, d)
+            (k_all, v_all), (dk_all, dv_all) = cpl.kv_views(gathered[j], s_l, hg, d), cpl.kv_views(d_rows[j], s_l, hg, d)
             hs = slice(j * hg * qpg, (j + 1) * hg * qpg)
-            args = (q5[:, :, j * hg:(j + 1) * hg], rows.unsqueeze(0), rows[s_l:].unsqueeze(0), o[:, :, hs], d_o[:, :, hs], lse[:, hs])
+            args = (q5[:, :, j * hg:(j + 1) * hg], k_all, v_all, o[:, :, hs], d_o[:, :, hs], lse[:, hs])
             if delta is None:            # row sums of dO * O for ALL heads, once: every split's passes read their head slice of it
                 delta = torch.empty((hq, s_l), dtype=torch.float32, device=q.device)
                 ops.attn_delta(o, d_o, delta)
             kw = dict(softmax_scale=ctx.softmax_scale, delta=delta[hs], **geo)
-            ops.flash_attn_bwd(*args, dk=drows.unsqueeze(0), dv=drows[s_l:].unsqueeze(0), parts=ops.ATTN_BWD_DKV, **kw)
+            ops.flash_attn_bwd(*args, dk=dk_all, dv=dv_all, parts=ops.ATTN_BWD_DKV, **kw)
             reduces.append(dist.reduce_scatter_tensor(dkv[j], d_rows[j], group=group, async_op=True))
             ops.flash_attn_bwd(*args, dq5=dq5[:, :, j * hg:(j + 1) * hg], parts=ops.ATTN_BWD_DQ, **kw)
         for w in reduces:
             if w is not None:
                 w.wait()
-        dkv = dkv.view(n_split, 2, s_l, hg, d)
-        dk = dkv[:, 0].permute(1, 0, 2, 3).reshape(1, s_l, hkv, d)
-        dv = dkv[:, 1].permute(1, 0, 2, 3).reshape(1, s_l, hkv, d)
+        dk, dv = cpl.unpack_kv(dkv.view(n_split, 2, s_l, hg, d)).unsqueeze(1)
         return dq, dk, dv, None, None
 
 

@@ -5,8 +5,8 @@ ViT branch  (:312-329)  non-causal, flash_attn_func            -> vita_flash_att
 LLM CP = 1  (:374-390)  causal, _flash_attention_forward        -> vita_flash_attn_fwd, d = 128
 LLM CP > 1  (TE AttnFuncWithCP P2P ring, gpt_layer_specs.py:40) -> ONE all-gather of the packed
             K/V shard over the CP group (RCCL; every peer pushes over its own xGMI link) followed by
-            one kernel launch over the zig-zag chunk tables.  The gathered buffer keeps rank order,
-            so chunk 2p+h of the buffer is global chunk (h ? 2CP-1-p : p).
+            one kernel launch over the zig-zag chunk tables (context_parallel.py owns the buffer
+            layout and the tables).
 """
 from __future__ import annotations
 
@@ -16,7 +16,7 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from . import ops, parallel_state as mpu, recompute_cache, training_utils
+from . import context_parallel as cpl, ops, parallel_state as mpu, recompute_cache, training_utils
 
 HEAD_SIZES = (64, 96, 128)         # head sizes the attention kernels are instantiated for (attn.hip, attn_bwd.hip)
 
@@ -157,8 +157,7 @@ class DotProductAttention:
         if self.causal and cp > 1:
             if b != 1:
                 raise ValueError("context-parallel attention runs batch 1")
-            kv = torch.stack([key.reshape(sq, self.ng, hn), value.reshape(sq, self.ng, hn)]).contiguous()
-            out = self.forward_cp(q.reshape(1, sq, self.ng, np_ // self.ng, hn), kv)
+            out = self.forward_cp(q.reshape(1, sq, self.ng, np_ // self.ng, hn), cpl.pack_kv(k, v, 1))
         else:
             # position ids with resets -> packed samples (_flash_attention_forward(position_ids=...), :374-390)
             seg = training_utils.get_packed_segments() if self.causal else None
@@ -185,9 +184,7 @@ class DotProductAttention:
         if kv_local.dim() == 4:
             kv_local = kv_local.unsqueeze(0)
         n_split, _, s_l, hg, d = kv_local.shape
-        if s_l % 2:
-            raise ValueError("local sequence must hold two zig-zag chunks")
-        c = s_l // 2
+        tables = cpl.chunk_tables(cp, r, s_l)
         qpg = self.np // self.ng
         if q5.dim() != 5:
             q5 = q5.reshape(1, s_l, self.ng, qpg, d)
@@ -203,10 +200,6 @@ class DotProductAttention:
             else:                                   # forced CP path without a process group
                 gathered[j].view(-1).copy_(kv_local[j].reshape(-1))
                 works.append(None)
-        kv_gid, kv_row = [], []
-        for p in range(cp):
-            kv_gid += [p, 2 * cp - 1 - p]
-            kv_row += [p * 2 * s_l, p * 2 * s_l + c]
         if events:
             events[0].record()
         # The per-split launches are a quarter of the heads each (640 workgroups at 128K / CP = 8 for 256 CUs): run them on
@@ -223,30 +216,25 @@ class DotProductAttention:
             with torch.cuda.stream(stream):
                 if stream is not main:
                     stream.wait_event(ready)
-                rows = gathered[j].view(cp * 2 * s_l, hg, d)        # K rows of rank p at p*2*s_l, V at +s_l
+                k_all, v_all = cpl.kv_views(gathered[j], s_l, hg, d)
                 qj, oj = q5[:, :, j * hg:(j + 1) * hg], out[:, :, j * hg * qpg:(j + 1) * hg * qpg]
                 lj = None if lse is None else lse[:, j * hg * qpg:(j + 1) * hg * qpg]     # batch 1: a head slice is contiguous
-                own = mpu.zigzag_chunk_ids(cp, r)
                 if j == 0 and cp > 1 and self.local_first:
                     # Gathers 1.. run under the attention of the split before them; gather 0 has nothing in front of it.  The rank's
                     # OWN two chunks need no remote K / V: attend to them (straight from the packed send buffer) while gather 0
                     # is in flight, then to the remote chunks, and merge the two partials (TE's ring does its
                     # local block first for the same reason).
-                    _, lse_a = ops.flash_attn(qj, kv_local[0, 0].unsqueeze(0), kv_local[0, 1].unsqueeze(0), causal=True,
-                                              softmax_scale=self.softmax_scale, chunk_len=c, q_chunk_gid=own, kv_chunk_gid=own,
-                                              kv_chunk_row=[0, c], out=oj, return_lse=True, lse_out=lj)
+                    own, remote = cpl.own_remote_tables(cp, r, s_l)
+                    _, lse_a = ops.flash_attn(qj, *cpl.unpack_kv(kv_local[:1]).unsqueeze(1), causal=True,
+                                              softmax_scale=self.softmax_scale, out=oj, return_lse=True, lse_out=lj, **own)
                     self._wait_gather(works[j], kv_local[j].numel() * kv_local.element_size())
-                    rem = [i for i in range(2 * cp) if i // 2 != r]
                     o_b = self._remote_buffer(oj)
-                    _, lse_b = ops.flash_attn(qj, rows.unsqueeze(0), rows[s_l:].unsqueeze(0), causal=True,
-                                              softmax_scale=self.softmax_scale, chunk_len=c, q_chunk_gid=own,
-                                              kv_chunk_gid=[kv_gid[i] for i in rem], kv_chunk_row=[kv_row[i] for i in rem], out=o_b,
-                                              return_lse=True)
+                    _, lse_b = ops.flash_attn(qj, k_all, v_all, causal=True, softmax_scale=self.softmax_scale, out=o_b,
+                                              return_lse=True, **remote)
                     ops.attn_merge_(oj, lse_a, o_b, lse_b)
                 else:
                     self._wait_gather(works[j], kv_local[j].numel() * kv_local.element_size())     # this stream waits for gather j only
-                    ops.flash_attn(qj, rows.unsqueeze(0), rows[s_l:].unsqueeze(0), causal=True, softmax_scale=self.softmax_scale,
-                                   chunk_len=c, q_chunk_gid=own, kv_chunk_gid=kv_gid, kv_chunk_row=kv_row, out=oj, lse_out=lj)
+                    ops.flash_attn(qj, k_all, v_all, causal=True, softmax_scale=self.softmax_scale, out=oj, lse_out=lj, **tables)
                 if stream is not main:
                     ev = torch.cuda.Event()
                     ev.record(stream)

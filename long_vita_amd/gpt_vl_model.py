@@ -18,7 +18,7 @@ from typing import Optional
 
 import torch
 
-from . import ops, parallel_state as mpu, tracing, training_utils
+from . import context_parallel, ops, parallel_state as mpu, tracing, training_utils
 from .dot_product_attention import DotProductAttention
 from .language_model_embedding import LanguageModelEmbedding
 from .layers import ColumnParallelLinear
@@ -121,8 +121,8 @@ class GPTVLModel:
         m5 = qkv.view(1, s, c.kv_groups, c.qpg + 2, c.head_dim)
         q5 = m5[:, :, :, : c.qpg]                                  # grouped query view, read in place
         if kv_dst is not None:
-            if use_cp:       # packed send buffer [split, 2, s, groups/split, d] -> [2, s, groups, d]
-                kv_dst[:, :s].view(2, s, ws["kv"].shape[0], -1, c.head_dim).copy_(ws["kv"].permute(1, 2, 0, 3, 4))
+            if use_cp:
+                context_parallel.unpack_kv(ws["kv"], out=kv_dst[:, :s])
             else:
                 kv_dst[0, :s].copy_(m5[0, :, :, c.qpg])
                 kv_dst[1, :s].copy_(m5[0, :, :, c.qpg + 1])

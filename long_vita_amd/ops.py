@@ -469,6 +469,27 @@ def gemm_skinny(a: torch.Tensor, w: torch.Tensor, out_f32: bool = False) -> torc
 # ------------------------------------------------------------------------------------------------
 # attention
 # ------------------------------------------------------------------------------------------------
+def _query_view(q: torch.Tensor):
+    """q [B, Sq, Hq, D] or grouped [B, Sq, Hkv, G, D] (dQ alike) -> (Sq, Hq, D, row stride, head stride, group stride); the flat form
+    has group stride 0."""
+    if q.dim() == 5:
+        _, Sq, Hkv, G, D = q.shape
+        return Sq, Hkv * G, D, q.stride(1), q.stride(3), q.stride(2)
+    if q.dim() == 4:
+        _, Sq, Hq, D = q.shape
+        return Sq, Hq, D, q.stride(1), q.stride(2), 0
+    raise ValueError("q must be [B, S, H, D] or [B, S, Hkv, G, D]")
+
+
+def _chunk_arrays(chunk_len, q_chunk_gid, kv_chunk_gid, kv_chunk_row, whole: int):
+    """The chunk geometry as the kernels' parameter blocks take it: (chunk_len, int32[] query gids, int32[] kv gids, int64[] kv rows).
+    chunk_len None: one chunk of `whole` rows, gid 0, at row 0."""
+    if chunk_len is None:
+        chunk_len, q_chunk_gid, kv_chunk_gid, kv_chunk_row = whole, [0], [0], [0]
+    qg, kg, kr = list(q_chunk_gid), list(kv_chunk_gid), list(kv_chunk_row)
+    return chunk_len, (C.c_int32 * len(qg))(*qg), (C.c_int32 * len(kg))(*kg), (C.c_int64 * len(kr))(*kr)
+
+
 def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: bool, softmax_scale: Optional[float] = None,
                chunk_len: Optional[int] = None, q_chunk_gid: Optional[Sequence[int]] = None,
                kv_chunk_gid: Optional[Sequence[int]] = None, kv_chunk_row: Optional[Sequence[int]] = None,
@@ -480,31 +501,20 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: boo
     Chunk geometry (zig-zag context parallelism): Sq = len(q_chunk_gid) * chunk_len local rows,
     kv chunk j starts at row kv_chunk_row[j] of k/v.  Defaults: one chunk, gid 0.
     lse_out: fp32 [B, Hq, Sq] contiguous destination of the row log-sum-exp (implies return_lse)."""
-    if q.dim() == 5:
-        B, Sq, Hkv_q, G, D = q.shape
-        Hq = Hkv_q * G
-        q_bs, q_rs, q_gs, q_hs = q.stride(0), q.stride(1), q.stride(2), q.stride(3)
-    elif q.dim() == 4:
-        B, Sq, Hq, D = q.shape
-        q_bs, q_rs, q_hs, q_gs = q.stride(0), q.stride(1), q.stride(2), 0
-    else:
-        raise ValueError("q must be [B, S, H, D] or [B, S, Hkv, G, D]")
+    Sq, Hq, D, q_rs, q_hs, q_gs = _query_view(q)
+    B = q.shape[0]
     if k.dim() != 4 or v.dim() != 4:
         raise ValueError("k, v must be [B, S, Hkv, D]")
     _, Sk, Hkv, _ = k.shape
     if q.stride(-1) != 1 or k.stride(3) != 1 or v.stride(3) != 1:
         raise ValueError("head_dim must be contiguous")
-    if chunk_len is None:
-        if Sq != Sk and causal:
-            raise ValueError("causal attention without chunk geometry needs Sq == Sk")
-        chunk_len = max(Sq, Sk)
-        qg, kg, kr = [0], [0], [0]
-        q_valid, kv_valid = Sq, Sk
-    else:
-        qg, kg, kr = list(q_chunk_gid), list(kv_chunk_gid), list(kv_chunk_row)
-        if Sq != len(qg) * chunk_len:
-            raise ValueError("Sq must equal len(q_chunk_gid) * chunk_len")
-        q_valid = kv_valid = chunk_len
+    chunked = chunk_len is not None
+    if not chunked and Sq != Sk and causal:
+        raise ValueError("causal attention without chunk geometry needs Sq == Sk")
+    chunk_len, qg, kg, kr = _chunk_arrays(chunk_len, q_chunk_gid, kv_chunk_gid, kv_chunk_row, whole=max(Sq, Sk))
+    if chunked and Sq != len(qg) * chunk_len:
+        raise ValueError("Sq must equal len(q_chunk_gid) * chunk_len")
+    q_valid, kv_valid = (chunk_len, chunk_len) if chunked else (Sq, Sk)
     o = torch.empty((B, Sq, Hq, D), dtype=BF16, device=q.device) if out is None else out
     if lse_out is not None:
         if tuple(lse_out.shape) != (B, Hq, Sq) or not lse_out.is_contiguous() or lse_out.dtype != torch.float32:
@@ -513,7 +523,7 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: boo
     else:
         lse = torch.empty((B, Hq, Sq), dtype=torch.float32, device=q.device) if return_lse else None
     p = AttnParams()
-    p.q, p.q_batch_stride, p.q_row_stride, p.q_head_stride, p.q_group_stride = _dev(q, "q", BF16), q_bs, q_rs, q_hs, q_gs
+    p.q, p.q_batch_stride, p.q_row_stride, p.q_head_stride, p.q_group_stride = _dev(q, "q", BF16), q.stride(0), q_rs, q_hs, q_gs
     p.k, p.k_batch_stride, p.k_row_stride, p.k_head_stride = _dev(k, "k", BF16), k.stride(0), k.stride(1), k.stride(2)
     p.v, p.v_batch_stride, p.v_row_stride, p.v_head_stride = _dev(v, "v", BF16), v.stride(0), v.stride(1), v.stride(2)
     p.o, p.o_batch_stride, p.o_row_stride, p.o_head_stride, p.o_group_stride = (
@@ -522,10 +532,7 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: boo
     p.batch, p.n_q_heads, p.n_kv_heads, p.head_dim = B, Hq, Hkv, D
     p.chunk_len, p.q_valid, p.kv_valid = chunk_len, q_valid, kv_valid
     p.n_q_chunks, p.n_kv_chunks = len(qg), len(kg)
-    qg_a = (C.c_int32 * len(qg))(*qg)
-    kg_a = (C.c_int32 * len(kg))(*kg)
-    kr_a = (C.c_int64 * len(kr))(*kr)
-    p.q_chunk_gid, p.kv_chunk_gid, p.kv_chunk_row = qg_a, kg_a, kr_a
+    p.q_chunk_gid, p.kv_chunk_gid, p.kv_chunk_row = qg, kg, kr
     p.causal = int(causal)
     p.softmax_scale = float(softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D))
     if seg_start is not None:           # packed sequences: int32 [rows], first row of each query row's segment
@@ -920,18 +927,9 @@ def flash_attn_bwd(q5, k, v, o, d_o, lse, *, chunk_len=None, q_chunk_gid=None, k
     lse [1, Hq, Sq].  Returns (dq like q5, dk, dv like k/v — dk/dv cover every row of k/v).
     parts: ATTN_BWD_DKV / ATTN_BWD_DQ run one pass only (a context-parallel caller starts the dK / dV reduce-scatter between them);
     delta: the fp32 [Hq, Sq] row sums of dO * O from an earlier call of this function (returned as 4th value when parts is partial)."""
-    if q5.dim() == 5:
-        _, Sq, Hkv_q, G, D = q5.shape
-        Hq = Hkv_q * G
-        q_rs, q_gs, q_hs = q5.stride(1), q5.stride(2), q5.stride(3)
-    else:
-        _, Sq, Hq, D = q5.shape
-        q_rs, q_hs, q_gs = q5.stride(1), q5.stride(2), 0
-    _, Sk, Hkv, _ = k.shape
-    if chunk_len is None:
-        chunk_len, qg, kg, kr = Sq, [0], [0], [0]
-    else:
-        qg, kg, kr = list(q_chunk_gid), list(kv_chunk_gid), list(kv_chunk_row)
+    Sq, Hq, D, q_rs, q_hs, q_gs = _query_view(q5)
+    _, _, Hkv, _ = k.shape
+    chunk_len, qg, kg, kr = _chunk_arrays(chunk_len, q_chunk_gid, kv_chunk_gid, kv_chunk_row, whole=Sq)
     both = parts == (ATTN_BWD_DQ | ATTN_BWD_DKV)
     if parts & ATTN_BWD_DQ:
         dq5 = torch.empty_like(q5) if dq5 is None else dq5
@@ -950,18 +948,14 @@ def flash_attn_bwd(q5, k, v, o, d_o, lse, *, chunk_len=None, q_chunk_gid=None, k
     p.d_o, p.do_row_stride, p.do_head_stride = _dev(d_o, "d_o", BF16), d_o.stride(1), d_o.stride(2)
     p.lse, p.delta = _dev(lse, "lse", torch.float32), _dev(delta, "delta")
     if dq5 is not None:
-        if dq5.dim() == 5:
-            p.dq, p.dq_row_stride, p.dq_group_stride, p.dq_head_stride = (_dev(dq5, "dq", BF16), dq5.stride(1),
-                                                                           dq5.stride(2), dq5.stride(3))
-        else:
-            p.dq, p.dq_row_stride, p.dq_head_stride, p.dq_group_stride = _dev(dq5, "dq", BF16), dq5.stride(1), dq5.stride(2), 0
+        p.dq = _dev(dq5, "dq", BF16)
+        p.dq_row_stride, p.dq_head_stride, p.dq_group_stride = _query_view(dq5)[3:]
     if dk is not None:
         p.dk, p.dk_row_stride, p.dk_head_stride = _dev(dk, "dk", BF16), dk.stride(1), dk.stride(2)
         p.dv, p.dv_row_stride, p.dv_head_stride = _dev(dv, "dv", BF16), dv.stride(1), dv.stride(2)
     p.n_q_heads, p.n_kv_heads, p.head_dim = Hq, Hkv, D
     p.chunk_len, p.n_q_chunks, p.n_kv_chunks = chunk_len, len(qg), len(kg)
-    qg_a, kg_a, kr_a = (C.c_int32 * len(qg))(*qg), (C.c_int32 * len(kg))(*kg), (C.c_int64 * len(kr))(*kr)
-    p.q_chunk_gid, p.kv_chunk_gid, p.kv_chunk_row = qg_a, kg_a, kr_a
+    p.q_chunk_gid, p.kv_chunk_gid, p.kv_chunk_row = qg, kg, kr
     p.softmax_scale = float(softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D))
     if seg_start is not None:
         p.q_seg_start, p.k_seg_end = _dev(seg_start, "seg_start", torch.int32), _dev(seg_end, "seg_end", torch.int32)

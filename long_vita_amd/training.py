@@ -30,39 +30,9 @@ from typing import Optional
 import torch
 import torch.distributed as dist
 
-from . import ops, parallel_state as mpu, tracing, training_utils
+from . import context_parallel as cpl, ops, parallel_state as mpu, tracing, training_utils
+from .autograd_fns import bias_grad, dgrad, pad_rows, transpose, wgrad, wgrad_tn
 from .gpt_vl_model import GPTVLModel
-
-
-def _t(x: torch.Tensor) -> torch.Tensor:
-    return ops.transpose(x)
-
-
-def _dgrad(dy: torch.Tensor, w: torch.Tensor, out=None, epilogue=ops.EPI_NONE, residual=None) -> torch.Tensor:
-    """grad_input = grad_output.matmul(weight)  (layers.py:444):  dy [M, N], w [N, K] -> [M, K]; whole-tile shapes read the weight
-    contraction-major as it lies (vita_gemm_bf16_nn, r04), others transpose it first."""
-    if epilogue == ops.EPI_NONE and residual is None and ops.gemm_nn_ok(dy, w) and (out is None or out.stride(1) == 1):
-        return ops.gemm_nn(dy, w, out=out)
-    return ops.gemm(dy, _t(w), epilogue, residual=residual, out=out)
-
-
-def _wgrad(dy_t: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    """grad_weight = grad_output.t().matmul(total_input)  (layers.py:522-523): dy_t [N, M], x [M, K] -> [N, K]."""
-    return ops.gemm(dy_t, _t(x))
-
-
-def _wgrad_tn(dy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
-    """grad_weight = grad_output.t().matmul(total_input) (layers.py:522-523) from the operands AS THE FORWARD LEFT THEM:
-    dy [M, N], x [M, K] -> [N, K] through vita_gemm_bf16_tn (both operands contraction-major, no transposed copies);
-    shapes the kernel does not tile (out dims not multiples of 256) take the two vita_transpose_bf16 passes + the NT GEMM."""
-    if ops.gemm_tn_ok(dy, x):
-        return ops.gemm_tn(dy, x)
-    return ops.gemm(_t(dy), _t(x))
-
-
-def _colsum(dy: torch.Tensor) -> torch.Tensor:
-    """grad_bias = grad_output.sum(dim=0) (layers.py:524): dy [M, N] -> [N] in one pass (vita_colsum_bf16; r03: a GEMM against ones)."""
-    return ops.colsum(dy).to(dy.dtype)
 
 
 def _tp_sum(t: torch.Tensor) -> torch.Tensor:
@@ -70,15 +40,6 @@ def _tp_sum(t: torch.Tensor) -> torch.Tensor:
     if mpu.get_tensor_model_parallel_world_size() > 1:
         dist.all_reduce(t, group=mpu.get_tensor_model_parallel_group())
     return t
-
-
-def _pad_rows(x: torch.Tensor, mult: int = 64) -> torch.Tensor:
-    m = x.shape[0]
-    if m % mult == 0:
-        return x
-    out = torch.zeros((m + mult - m % mult,) + tuple(x.shape[1:]), dtype=x.dtype, device=x.device)
-    out[:m] = x
-    return out
 
 
 class TrainStep:
@@ -167,7 +128,7 @@ class TrainStep:
         qkv = keep["qkv"]
         m5 = qkv.view(1, s, c.kv_groups, c.qpg + 2, c.head_dim)
         if cp > 1:
-            kv_local = torch.stack([m5[0, :, :, c.qpg], m5[0, :, :, c.qpg + 1]]).contiguous()      # rotated K, V of this rank
+            kv_local = cpl.pack_kv(m5[:, :, :, c.qpg], m5[:, :, :, c.qpg + 1], 1)[0]               # rotated K, V of this rank
             k_all, v_all, geo = self._gather_kv(kv_local)
         else:
             k_all, v_all, geo = m5[:, :, :, c.qpg], m5[:, :, :, c.qpg + 1], {}
@@ -178,19 +139,13 @@ class TrainStep:
                     h_mid=keep["h_mid"], x2=x2, y=y, act=ops.swiglu(y))
 
     def _gather_kv(self, kv_local):
+        """kv_local [2, S_l, groups, d] (one unsplit send buffer) -> (K, V) of all ranks and their chunk tables."""
         c = self.m.cfg
         cp, r = mpu.get_context_parallel_world_size(), mpu.get_context_parallel_rank()
         s_l = kv_local.shape[1]
-        ch = s_l // 2
         gathered = torch.empty(cp * kv_local.numel(), dtype=kv_local.dtype, device=kv_local.device)
         dist.all_gather_into_tensor(gathered, kv_local.view(-1), group=mpu.get_context_parallel_group())
-        rows = gathered.view(cp * 2 * s_l, c.kv_groups, c.head_dim)
-        kv_gid, kv_row = [], []
-        for p in range(cp):
-            kv_gid += [p, 2 * cp - 1 - p]
-            kv_row += [p * 2 * s_l, p * 2 * s_l + ch]
-        geo = dict(chunk_len=ch, q_chunk_gid=mpu.zigzag_chunk_ids(cp, r), kv_chunk_gid=kv_gid, kv_chunk_row=kv_row)
-        return rows.unsqueeze(0), rows[s_l:].unsqueeze(0), geo
+        return (*cpl.kv_views(gathered, s_l, c.kv_groups, c.head_dim), cpl.chunk_tables(cp, r, s_l))
 
     def _layer_backward(self, dh, h, lp, cos, sin, g, keep=None):
         """dh = dL/d(layer output) [s, hidden]; returns dL/d(layer input); fills g (this layer's grads).
@@ -201,41 +156,39 @@ class TrainStep:
         a = self._layer_recompute(h, lp, cos, sin) if keep is None else self._rebuild(h, lp, keep)
         f32 = lambda n: torch.zeros(n, dtype=torch.float32, device=h.device)  # noqa: E731
         # ---- MLP: out = h_mid + fc2(swiglu(fc1(norm2(h_mid)))) ------------------------------------
-        g["fc2_w"] = _wgrad_tn(dh, a["act"])
-        d_act = _dgrad(dh, lp["fc2_w"])
+        g["fc2_w"] = wgrad_tn(dh, a["act"])
+        d_act = dgrad(dh, lp["fc2_w"])
         dy = ops.swiglu_bwd(a["y"], d_act)
         del d_act
-        g["fc1_w"] = _wgrad_tn(dy, a["x2"])
-        dx2 = _tp_sum(_dgrad(dy, lp["fc1_w"]))
+        g["fc1_w"] = wgrad_tn(dy, a["x2"])
+        dx2 = _tp_sum(dgrad(dy, lp["fc1_w"]))
         del dy
         dln2 = f32(c.hidden)
         dh_mid = ops.rmsnorm_bwd(dx2, a["h_mid"], lp["ln2"], c.eps, dln2, residual=dh)
         g["ln2"] = dln2
         del dx2
         # ---- attention: h_mid = h + proj(attn(rope(qkv(norm1(h))))) -------------------------------
-        g["o_w"] = _wgrad_tn(dh_mid, a["ctx"].view(s, -1))
-        d_ctx = _dgrad(dh_mid, lp["o_w"]).view(1, s, c.heads, c.head_dim)
+        g["o_w"] = wgrad_tn(dh_mid, a["ctx"].view(s, -1))
+        d_ctx = dgrad(dh_mid, lp["o_w"]).view(1, s, c.heads, c.head_dim)
         d_mixed = torch.empty_like(a["qkv"])
         dm5 = d_mixed.view(1, s, c.kv_groups, c.qpg + 2, c.head_dim)
         if cp > 1:
-            dk_all = torch.empty_like(a["k_all"][0].reshape(-1)).view(cp * 2 * s, c.kv_groups, c.head_dim)
-            # dK rows of rank p start at p*2*s, dV at +s: the layout of the gathered K/V buffer
+            d_gathered = torch.empty_like(a["k_all"][0].reshape(-1))             # dK / dV in the layout of the gathered K / V
+            dk_all, dv_all = cpl.kv_views(d_gathered, s, c.kv_groups, c.head_dim)
             ops.flash_attn_bwd(a["q5"], a["k_all"], a["v_all"], a["ctx"], d_ctx, a["lse"], dq5=dm5[:, :, :, : c.qpg],
-                               dk=dk_all.unsqueeze(0), dv=dk_all[s:].unsqueeze(0), **a["geo"])
-            dkv_local = torch.empty(2 * s * c.kv_groups * c.head_dim, dtype=h.dtype, device=h.device)
-            dist.reduce_scatter_tensor(dkv_local, dk_all.view(-1), group=mpu.get_context_parallel_group())
-            dkv_local = dkv_local.view(2, s, c.kv_groups, c.head_dim)
-            dm5[0, :, :, c.qpg].copy_(dkv_local[0])
-            dm5[0, :, :, c.qpg + 1].copy_(dkv_local[1])
+                               dk=dk_all, dv=dv_all, **a["geo"])
+            dkv_local = torch.empty(1, 2, s, c.kv_groups, c.head_dim, dtype=h.dtype, device=h.device)
+            dist.reduce_scatter_tensor(dkv_local.view(-1), d_gathered, group=mpu.get_context_parallel_group())
+            cpl.unpack_kv(dkv_local, out=dm5[0, :, :, c.qpg:].permute(2, 0, 1, 3))
         else:
             seg = training_utils.get_packed_segments()
             ops.flash_attn_bwd(a["q5"], a["k_all"], a["v_all"], a["ctx"], d_ctx, a["lse"], dq5=dm5[:, :, :, : c.qpg],
                                dk=dm5[:, :, :, c.qpg], dv=dm5[:, :, :, c.qpg + 1],
                                seg_start=None if seg is None else seg[0], seg_end=None if seg is None else seg[1])
         ops.rope_qkv_bwd_(d_mixed, c.kv_groups, c.qpg, c.head_dim, cos, sin)
-        g["qkv_w"] = _wgrad_tn(d_mixed, a["x1"])
-        g["qkv_b"] = _colsum(d_mixed)                       # grad_bias = grad_output.sum(dim=0) (layers.py:524)
-        dx1 = _tp_sum(_dgrad(d_mixed, lp["qkv_w"]))
+        g["qkv_w"] = wgrad_tn(d_mixed, a["x1"])
+        g["qkv_b"] = bias_grad(d_mixed)                     # grad_bias = grad_output.sum(dim=0) (layers.py:524)
+        dx1 = _tp_sum(dgrad(d_mixed, lp["qkv_w"]))
         dln1 = f32(c.hidden)
         dh_in = ops.rmsnorm_bwd(dx1, h, lp["ln1"], c.eps, dln1, residual=dh_mid)
         g["ln1"] = dln1
@@ -328,7 +281,7 @@ class TrainStep:
         if n_sel > 0:
             rows = ops.row_gather(h, idx)
             hn = ops.rmsnorm(rows, m.p["final_ln"], c.eps)
-            hn_p = _pad_rows(hn)
+            hn_p = pad_rows(hn)
             logits_local = ops.gemm(hn_p, m.p["lm_head"])                # [n_sel (padded), V / TP]
             logits = m._gather_vocab_parallel(logits_local).contiguous() # [n_sel (padded), V]
             ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)     # gpt_vl_model.py:349-355
@@ -358,8 +311,8 @@ class TrainStep:
             if tp > 1:      # this rank's vocabulary slice of dlogits
                 v_l = logits_local.shape[1]
                 dlogits = dlogits[:, tp_rank * v_l: (tp_rank + 1) * v_l].contiguous()
-            grads["lm_head"] = _wgrad_tn(dlogits, hn_p)                      # [V / TP, hidden]
-            d_hn = _tp_sum(_dgrad(dlogits, m.p["lm_head"]))[:n_sel]
+            grads["lm_head"] = wgrad_tn(dlogits, hn_p)                      # [V / TP, hidden]
+            d_hn = _tp_sum(dgrad(dlogits, m.p["lm_head"]))[:n_sel]
             dfl = torch.zeros(c.hidden, dtype=torch.float32, device=h.device)
             d_rows = ops.rmsnorm_bwd(d_hn.contiguous(), rows, m.p["final_ln"], c.eps, dfl)
             grads["final_ln"] = dfl
@@ -415,13 +368,12 @@ class TrainStep:
 
     def _projector_backward(self, vis, proj, d_feats, grads):
         p, cfg = vis.p, vis.cfg
-        df_t = _t(_pad_rows(d_feats))
         g = {}
-        g["proj_fc2"] = ops.gemm(df_t, _t(_pad_rows(proj["a"])))
-        d_a = _dgrad(d_feats, p["proj_fc2"])
+        g["proj_fc2"] = wgrad(transpose(pad_rows(d_feats)), pad_rows(proj["a"]))
+        d_a = dgrad(d_feats, p["proj_fc2"])
         d_f1 = ops.gelu_bwd(proj["f1"], d_a)
-        g["proj_fc1"] = ops.gemm(_t(_pad_rows(d_f1)), _t(_pad_rows(proj["t"])))
-        d_t = _dgrad(d_f1, p["proj_fc1"])
+        g["proj_fc1"] = wgrad(transpose(pad_rows(d_f1)), pad_rows(proj["t"]))
+        d_t = dgrad(d_f1, p["proj_fc1"])
         dgam = torch.zeros(p["proj_ln_w"].numel(), dtype=torch.float32, device=d_feats.device)
         dbet = torch.zeros_like(dgam)
         ops.layernorm_param_grad(d_t, proj["xhat"], dgam, dbet, cfg.proj_ln_eps, prenormalized=True)

@@ -655,8 +655,9 @@ def test_gemm_nn_weight_read_contraction_major(ops, M, N, K):
         eye[:, :M] = torch.eye(M)                                      # A = [I | 0]: C = the first M rows of W
         wa = (torch.arange(K * N).reshape(K, N) % 251 - 125).float().bfloat16()
         assert torch.equal(ops.gemm_nn(eye.to(DEV), wa.to(DEV)).cpu(), wa[:M])
-    # the two dgrad helpers take this path for whole tiles and give what the transposing path gives
-    assert torch.equal(autograd_fns.dgrad(ad, wd), nt) and torch.equal(training._dgrad(ad, wd), nt)
+    # the dgrad helper (one function for the autograd path and training.TrainStep) takes this path for whole tiles and gives what the
+    # transposing path gives
+    assert training.dgrad is autograd_fns.dgrad and torch.equal(autograd_fns.dgrad(ad, wd), nt)
     assert not ops.gemm_nn_ok(ad[:M - 8], wd) and not ops.gemm_nn_ok(ad, wd[:, :N - 8])
     ragged = autograd_fns.dgrad(ad[:M - 8].contiguous(), wd)           # rows not a multiple of 256: the transposing fallback
     tol("ragged fallback", rel_l2(ragged, nt[:M - 8]), 2e-3)

@@ -171,7 +171,7 @@ def test_attention_backward_at_16k(ops):
 @pytest.mark.parametrize("S,rank", [(131072, 3), (1048576, 5)])
 def test_attention_cp8_chunk_tables_at_the_benchmark_geometry(ops, S, rank):
     """One rank, one kv-head split (2 kv heads, 10 query heads) of the CP = 8 layout: local queries in zig-zag order against
-    the gathered buffer [rank p][K | V][S_l][2][128] through chunk tables (long_vita_amd/dot_product_attention.py:forward_cp)."""
+    the gathered buffer [rank p][K | V][S_l][2][128] through chunk tables (layout: long_vita_amd/context_parallel.py)."""
     cp, hg, G, D = 8, 2, 5, 128
     C = S // (2 * cp)
     s_l = 2 * C

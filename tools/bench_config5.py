@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from long_vita_amd import gpt_vl_model, lib, ops, training  # noqa: E402
+from long_vita_amd import autograd_fns, context_parallel, gpt_vl_model, lib, ops, training  # noqa: E402
 
 DEV = "cuda:0"
 OUT = os.path.join(ROOT, "gpurun_out")
@@ -71,12 +71,8 @@ def bench_rank(rank=1):
     q = rnd(1, s_l, hq, D, seed=1)
     rows = rnd(cp * 2 * s_l, hkv, D, seed=2)                    # gathered [rank p][K | V][S_l][4][128]
     d_o = rnd(1, s_l, hq, D, seed=3)
-    kv_gid, kv_row = [], []
-    for p in range(cp):
-        kv_gid += [p, 2 * cp - 1 - p]
-        kv_row += [p * 2 * s_l, p * 2 * s_l + c]
-    geo = dict(chunk_len=c, q_chunk_gid=[rank, 2 * cp - 1 - rank], kv_chunk_gid=kv_gid, kv_chunk_row=kv_row)
-    k_all, v_all = rows.unsqueeze(0), rows[s_l:].unsqueeze(0)
+    geo = context_parallel.chunk_tables(cp, rank, s_l)
+    k_all, v_all = context_parallel.kv_views(rows, s_l, hkv, D)
     o = torch.empty_like(q)
     lse = torch.empty(1, hq, s_l, dtype=torch.float32, device=DEV)
     pairs = c * (rank + 0.5) * c + c * (2 * cp - 1 - rank + 0.5) * c
@@ -84,7 +80,8 @@ def bench_rank(rank=1):
     t_f = timeit(lambda: ops.flash_attn(q, k_all, v_all, causal=True, out=o, lse_out=lse, **geo))
     emit(kind="cfg5_attn_fwd", rank=rank, s_local=s_l, keys=S, heads=f"{hq}:{hkv}", ms=t_f, algorithmic_tflops=2 * unit / t_f / 1e9)
     dq, d_rows = torch.empty_like(q), torch.empty_like(rows)
-    t_b = timeit(lambda: ops.flash_attn_bwd(q, k_all, v_all, o, d_o, lse, dq5=dq, dk=d_rows.unsqueeze(0), dv=d_rows[s_l:].unsqueeze(0), **geo))
+    dk_all, dv_all = context_parallel.kv_views(d_rows, s_l, hkv, D)
+    t_b = timeit(lambda: ops.flash_attn_bwd(q, k_all, v_all, o, d_o, lse, dq5=dq, dk=dk_all, dv=dv_all, **geo))
     emit(kind="cfg5_attn_bwd", rank=rank, s_local=s_l, keys=S, heads=f"{hq}:{hkv}", ms=t_b, algorithmic_tflops=5 * unit / t_b / 1e9,
          note="delta pre-pass + dQ kernel + dK kernel + dV kernel; dK / dV written for all 131072 gathered rows")
     del q, rows, d_o, o, dq, d_rows
@@ -103,7 +100,7 @@ def bench_rank(rank=1):
         wt = ops.transpose(w)                                   # dgrad: dy [M, N] @ w [N, K] = gemm(dy, w^T [K, N])
         dx = torch.empty(M, K, dtype=torch.bfloat16, device=DEV)
         t_d = timeit(lambda: ops.gemm(dy, ops.transpose(w), out=dx))
-        t_w = timeit(lambda: training._wgrad_tn(dy, a))                          # wgrad: dy^T [N, M] @ a [M, K] (vita_gemm_bf16_tn, r03)
+        t_w = timeit(lambda: autograd_fns.wgrad_tn(dy, a))                          # wgrad: dy^T [N, M] @ a [M, K] (vita_gemm_bf16_tn, r03)
         fl = 2.0 * M * N * K
         emit(kind="cfg5_gemm", name=name, M=M, N=N, K=K, fwd_ms=t, dgrad_ms=t_d, wgrad_ms=t_w, fwd_tflops=fl / t / 1e9,
              dgrad_tflops=fl / t_d / 1e9, wgrad_tflops=fl / t_w / 1e9, note="dgrad includes the weight transpose it needs; wgrad = vita_gemm_bf16_tn on the operands as they are")

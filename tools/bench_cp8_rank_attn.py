@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from long_vita_amd import lib, ops  # noqa: E402
+from long_vita_amd import context_parallel, lib, ops  # noqa: E402
 
 DEV = "cuda:0"
 lib.load(allow_build=False)
@@ -26,10 +26,6 @@ G = Hq // Hkv
 gen = torch.Generator(device=DEV).manual_seed(1)
 q = torch.randn(1, s_l, Hq, D, generator=gen, device=DEV).bfloat16()
 o = torch.empty_like(q)
-kv_gid, kv_row = [], []
-for p in range(cp):
-    kv_gid += [p, 2 * cp - 1 - p]
-    kv_row += [p * 2 * s_l, p * 2 * s_l + c]
 
 
 def emit(**kw):
@@ -39,7 +35,8 @@ def emit(**kw):
 
 
 for r in (0, 3, 7):
-    own = [r, 2 * cp - 1 - r]
+    tables = context_parallel.chunk_tables(cp, r, s_l)
+    own_tables, remote_tables = context_parallel.own_remote_tables(cp, r, s_l)
     pairs = c * (r + 0.5) * c + c * (2 * cp - 1 - r + 0.5) * c
     flops = 4.0 * D * Hq * pairs
     for n_split in (1, 2, 4):
@@ -49,8 +46,8 @@ for r in (0, 3, 7):
         main = torch.cuda.current_stream()
 
         def launch(j):
-            ops.flash_attn(q[:, :, j * hg * G:(j + 1) * hg * G], rows[j].unsqueeze(0), rows[j][s_l:].unsqueeze(0), causal=True, chunk_len=c,
-                           q_chunk_gid=own, kv_chunk_gid=kv_gid, kv_chunk_row=kv_row, out=o[:, :, j * hg * G:(j + 1) * hg * G])
+            ops.flash_attn(q[:, :, j * hg * G:(j + 1) * hg * G], *context_parallel.kv_views(rows[j], s_l, hg, D), causal=True,
+                           out=o[:, :, j * hg * G:(j + 1) * hg * G], **tables)
 
         def one_stream():
             for j in range(n_split):
@@ -71,14 +68,12 @@ for r in (0, 3, 7):
         # flight), then to the 14 remote chunks, and merges; splits 1.. run on their own streams
         kv_own = torch.randn(2, s_l, hg, D, generator=gen, device=DEV).bfloat16()
         o_b = torch.empty(1, s_l, hg * G, D, dtype=torch.bfloat16, device=DEV)
-        rem = [i for i in range(2 * cp) if i // 2 != r]
 
         def own_first(j):
             qj, oj = q[:, :, j * hg * G:(j + 1) * hg * G], o[:, :, j * hg * G:(j + 1) * hg * G]
-            _, lse_a = ops.flash_attn(qj, kv_own[0].unsqueeze(0), kv_own[1].unsqueeze(0), causal=True, chunk_len=c, q_chunk_gid=own,
-                                      kv_chunk_gid=own, kv_chunk_row=[0, c], out=oj, return_lse=True)
-            _, lse_b = ops.flash_attn(qj, rows[j].unsqueeze(0), rows[j][s_l:].unsqueeze(0), causal=True, chunk_len=c, q_chunk_gid=own,
-                                      kv_chunk_gid=[kv_gid[i] for i in rem], kv_chunk_row=[kv_row[i] for i in rem], out=o_b, return_lse=True)
+            _, lse_a = ops.flash_attn(qj, *context_parallel.unpack_kv(kv_own.unsqueeze(0)).unsqueeze(1), causal=True, out=oj, return_lse=True, **own_tables)
+            _, lse_b = ops.flash_attn(qj, *context_parallel.kv_views(rows[j], s_l, hg, D), causal=True, out=o_b, return_lse=True,
+                                      **remote_tables)
             ops.attn_merge_(oj, lse_a, o_b, lse_b)
 
         def product_order():

@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from long_vita_amd import gpt_vl_model, lib, ops, parallel_state as mpu, vision  # noqa: E402
+from long_vita_amd import context_parallel, gpt_vl_model, lib, ops, parallel_state as mpu, vision  # noqa: E402
 
 DEV = "cuda:0"
 lib.load(allow_build=False)
@@ -94,11 +94,8 @@ def main():
     # positions of the rank's rows: chunks `rank` and `2 cp - 1 - rank` of the global sequence
     pos = torch.cat([torch.arange(rank * c, (rank + 1) * c, device=DEV), torch.arange((2 * cp - 1 - rank) * c, (2 * cp - rank) * c, device=DEV)])
     cos, sin = ops.rope_table(pos, model.rotary_pos_emb.inv_freq)
-    kv_gid, kv_row = [], []
-    for p_ in range(cp):
-        kv_gid += [p_, 2 * cp - 1 - p_]
-        kv_row += [p_ * 2 * s_l, p_ * 2 * s_l + c]
-    own = [rank, 2 * cp - 1 - rank]
+    tables = context_parallel.chunk_tables(cp, rank, s_l)
+    own = tables["q_chunk_gid"]
     qpg, d = cfg.qpg, cfg.head_dim
     times = []
     checks = []
@@ -115,15 +112,14 @@ def main():
         ev[2].record()
         m5 = qkv.view(1, s_l, cfg.kv_groups, qpg + 2, d)
         q1 = m5[:, :, 0:1, :qpg]                                          # ONE kv group: 5 query heads (grouped view, read in place)
-        rows = gathered[0].view(cp * 2 * s_l, hg, d)                      # K rows of rank p at p * 2 s_l, V at + s_l
+        k_all, v_all = (t[:, :, 0:1] for t in context_parallel.kv_views(gathered[0], s_l, hg, d))     # the kv group of q1
         ws["ctx"].zero_()
         o1 = ws["ctx"][:, :, :qpg]
         lse = torch.empty(1, qpg, s_l, dtype=torch.float32, device=DEV)
-        ops.flash_attn(q1, rows[:, 0:1].unsqueeze(0), rows[s_l:, 0:1].unsqueeze(0), causal=True, chunk_len=c, q_chunk_gid=own,
-                       kv_chunk_gid=kv_gid, kv_chunk_row=kv_row, out=o1, lse_out=lse)
+        ops.flash_attn(q1, k_all, v_all, causal=True, out=o1, lse_out=lse, **tables)
         ev[3].record()
         if li == 0:
-            checks = sampled_rows_check(q1, rows, o1, s_l, c, own, kv_gid, kv_row, qpg, d)
+            checks = sampled_rows_check(q1, k_all, v_all, o1, tables, qpg, d)
         ev[4].record()
         ops.gemm(ws["ctx"].view(s_l, cfg.heads * d), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
         x = ops.rmsnorm(h, lp["ln2"], cfg.eps, out=ws["x"])
@@ -153,9 +149,10 @@ def main():
               "for all 8 kv heads, the rank's frames, ViT chunk buffers); compute = ViT over the rank's frames + 2 decoder layers with one kv group's attention")
 
 
-def sampled_rows_check(q1, rows, o1, s_l, c, own, kv_gid, kv_row, qpg, d):
+def sampled_rows_check(q1, k_all, v_all, o1, tables, qpg, d):
     """fp32 attention of a few query rows (first / middle / last rows of both chunks, all 5 heads) over the same gathered buffer with torch ops."""
     scale = 1.0 / math.sqrt(d)
+    c, own = tables["chunk_len"], tables["q_chunk_gid"]
     out = []
     picks = [(0, 0), (0, 4097), (0, c // 2 + 13), (0, c - 1), (1, 0), (1, c // 3 + 5), (1, c - 1)]
     for qc, i in picks:
@@ -164,14 +161,14 @@ def sampled_rows_check(q1, rows, o1, s_l, c, own, kv_gid, kv_row, qpg, d):
         m = torch.full((qpg,), -float("inf"), device=q1.device)
         l = torch.zeros(qpg, device=q1.device)
         acc = torch.zeros(qpg, d, device=q1.device)
-        for j, (gid, row0) in enumerate(zip(kv_gid, kv_row)):
+        for j, (gid, row0) in enumerate(zip(tables["kv_chunk_gid"], tables["kv_chunk_row"])):
             if gid > own[qc]:
                 continue
             n_vis = c if gid < own[qc] else i + 1
             for a in range(0, n_vis, 1 << 18):
                 b = min(a + (1 << 18), n_vis)
-                k = rows[row0 + a: row0 + b, 0].float()                   # [n, d]
-                v = rows[s_l + row0 + a: s_l + row0 + b, 0].float()
+                k = k_all[0, row0 + a: row0 + b, 0].float()                # [n, d]
+                v = v_all[0, row0 + a: row0 + b, 0].float()
                 s = (qv @ k.t()) * scale                                  # [qpg, n]
                 m_new = torch.maximum(m, s.max(dim=1).values)
                 p = torch.exp(s - m_new[:, None])

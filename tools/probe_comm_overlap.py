@@ -28,7 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
-from long_vita_amd import lib, ops  # noqa: E402
+from long_vita_amd import context_parallel, lib, ops  # noqa: E402
 
 DEV = "cuda:0"
 OUT = os.path.join(ROOT, "gpurun_out")
@@ -56,18 +56,14 @@ gen = torch.Generator(device=DEV).manual_seed(1)
 q = torch.randn(1, s_l, hg * G, D, generator=gen, device=DEV).bfloat16()
 rows = torch.randn(cp * 2 * s_l, hg, D, generator=gen, device=DEV).bfloat16()
 o = torch.empty_like(q)
-kv_gid, kv_row = [], []
-for p in range(cp):
-    kv_gid += [p, 2 * cp - 1 - p]
-    kv_row += [p * 2 * s_l, p * 2 * s_l + c]
-own = [r, 2 * cp - 1 - r]
+k_all, v_all = context_parallel.kv_views(rows, s_l, hg, D)
+tables = context_parallel.chunk_tables(cp, r, s_l)
 N_ATT = 4
 
 
 def attention():
     for _ in range(N_ATT):
-        ops.flash_attn(q, rows.unsqueeze(0), rows[s_l:].unsqueeze(0), causal=True, chunk_len=c, q_chunk_gid=own, kv_chunk_gid=kv_gid,
-                       kv_chunk_row=kv_row, out=o)
+        ops.flash_attn(q, k_all, v_all, causal=True, out=o, **tables)
 
 
 MSG = 2 * s_l * hg * D * 2            # bytes of one rank's packed K/V shard of one split: 16.8 MB
