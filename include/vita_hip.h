@@ -261,6 +261,37 @@ typedef struct {
 int vita_flash_attn_fwd(const vita_attn_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Attention of t >= 1 NEW tokens behind a KV cache that already holds their rotated K / V rows (attn_extend.hip): a follow-up turn or
+ * one chunk of a chunked prefill.  Replaces the q_len > 1 step behind a DynamicCache of
+ * H/models/long_vita_qwen2_intern/modeling_long_vita.py:150-202 (cache_position = arange(past_seen, past_seen + s)) and the cached
+ * decode loop M/inference/text_generation/generation.py:127-131 fed more than one token (per-token passes before).
+ *   q: t rows read in place from the mixed QKV activation: head j of kv group g of row i at q + i * q_row_stride + g * q_group_stride
+ *      + j * q_head_stride.  k_cache / v_cache: rows [0, n_keys) of a cache shard [rows][n_kv_heads][128] (row / group strides in
+ *      elements, shared by K and V); rows behind n_keys are never read.  out [t][n_q_heads][128] through its strides; lse (optional)
+ *      fp32 [n_q_heads][t], natural log.  head_dim 128 only; every stride a multiple of 8 elements (else VITA_ERR_UNSUPPORTED).
+ *   Visibility by position: query row i sits at q_pos0 + i.  Keys [0, n_full) are visible to every row; key k >= n_full sits at
+ *      key_pos0 + (k - n_full) * key_pos_step and is visible iff that position <= the row's.  One device, one cache: n_full = the
+ *      cached length L, key_pos0 = q_pos0 = L, step 1; step > 1 describes a round-robin shard of the appended rows.  A row that sees no
+ *      key returns zeros and lse = -inf.
+ *   The keys are cut into splits (a function of t, n_q_heads and n_keys only) so that a short t behind a long cache fills the chip;
+ *      with more than one split the launch needs vita_flash_attn_extend_workspace_bytes of device memory (16-byte aligned, contents
+ *      ignored; 0 bytes = one split, workspace may be NULL) for the fp32 partials that a merge kernel folds.  Arguments are checked
+ *      before anything is launched. */
+typedef struct {
+  const void* q; int64_t q_row_stride, q_group_stride, q_head_stride;
+  const void* k_cache; const void* v_cache; int64_t kv_row_stride, kv_group_stride;
+  void* out; int64_t out_row_stride, out_head_stride;
+  float* lse;
+  int64_t t, n_keys, n_full;
+  int64_t q_pos0, key_pos0, key_pos_step;
+  int n_q_heads, n_kv_heads, head_dim;
+  float softmax_scale;
+  void* workspace; size_t workspace_bytes;
+} vita_attn_extend_params;
+size_t vita_flash_attn_extend_workspace_bytes(int64_t t, int n_q_heads, int64_t n_keys);
+int vita_flash_attn_extend_fwd(const vita_attn_extend_params* p, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Context-parallel core attention for callers without PyTorch (cp_attn.hip): the K/V exchange of one decoder layer over
  * RCCL + the zig-zag chunk-table attention.  Replaces TransformerEngine's AttnFuncWithCP (the core_attention of
  * M/core/models/gpt/gpt_layer_specs.py:40 under --context-parallel-size > 1: a CP-1-step P2P ring) with one all-gather per

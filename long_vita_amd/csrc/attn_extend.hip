@@ -1,0 +1,460 @@
+// Flash attention of t NEW query rows against a KV cache that already holds their keys ("extend": a follow-up turn or a prefill
+// chunk behind a cached context).  gfx950, head_dim 128, bf16 I/O, fp32 statistics, GQA.
+//
+// Geometry: query row i sits at position q_pos0 + i.  Cache rows [0, n_full) are visible to every row; row k >= n_full sits at
+// position key_pos0 + (k - n_full) * key_pos_step and is visible iff that position <= the row's.  Positions of the appended rows
+// ascend, so a row sees exactly the keys [0, lim] with lim = n_full + floor((pos - key_pos0) / step) (n_full - 1 when pos < key_pos0,
+// never beyond n_keys - 1): ONE integer per lane decides every mask, and only tiles that reach beyond the smallest lim of a wave
+// evaluate it.
+//
+// Built on flash_fwd_kernel<128, true> (attn.hip): 8 waves x 32 rows, 64-key K/V tiles staged by LDS-DMA with the bank swizzle on the
+// source address, S^T = K Q^T / O^T = V^T P^T on v_mfma_f32_32x32x16_bf16, in-lane online softmax.  What differs:
+//   * the 256 rows of a workgroup are STACKED (row, query head of the kv group) pairs, row-major: stacked index s = row * G + head.
+//     One K/V tile read serves all G heads of the group, and a 16-row follow-up fills 80 of 256 MFMA rows instead of 16;
+//   * the keys are cut into n_splits ranges of whole tiles (blocks = kv head x query tile x split) so that a short follow-up behind
+//     a long context still fills the chip; every split writes un-normalised fp32 partials (m, l in the log2 domain, o) and
+//     extend_merge_kernel forms the bf16 context and the natural-log lse.  One split writes the result directly.
+// decode_attn_merge_kernel (decode.hip) is not reused: it writes a dense [heads][128] context and no lse; this merge writes through
+// row / head strides and one workgroup handles four (row, head) pairs.
+//
+// Reference behaviour restated: H/models/long_vita_qwen2_intern/modeling_long_vita.py:150-202 (q_len > 1 behind a DynamicCache:
+// cache_position = arange(past_seen, past_seen + s), causal mask over past + new keys) and the cached decode loop
+// M/inference/text_generation/generation.py:127-131 fed more than one token.
+#include "vita_common.h"
+
+namespace {
+
+constexpr int QTILE = 256;       // stacked query rows per workgroup (8 waves x 32)
+constexpr int KVT = 64;          // keys per tile
+constexpr int D = 128;
+constexpr int kMaxSplits = 64;
+constexpr int kTargetBlocks = 512;      // two rounds of one workgroup per CU (256 CUs)
+constexpr int kMinTilesPerSplit = 4;
+
+struct ExtArgs {
+  const bf16_t* q; int64_t q_rs, q_gs, q_hs;
+  const bf16_t* k; const bf16_t* v; int64_t kv_rs, kv_gs;
+  bf16_t* o; int64_t o_rs, o_hs;
+  float* lse;                    // [heads][t] or null
+  float* pm; float* pl; float* po;   // partials [n_splits][heads][t] (x 128 for po); unused with one split
+  int t, G, n_kv_heads, n_q_tiles;
+  int n_keys, n_full;
+  int64_t q_pos0, key_pos0, key_pos_step;
+  int n_splits, tiles_per_split;
+  int quant_m;                   // running max kept on integers (log2 domain): see sm_pv_phase
+  float scale_log2e;
+};
+
+__device__ __forceinline__ float swap32_max(float x) {
+  const unsigned xi = __float_as_uint(x);
+  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
+  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
+}
+__device__ __forceinline__ float swap32_sum(float x) {
+  const unsigned xi = __float_as_uint(x);
+  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+}
+// the LDS layouts of attn.hip at d = 128
+__device__ __forceinline__ int k_lds_off(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
+__device__ __forceinline__ int v_lds_off(int row, int chunk, int b) { return row * 256 + ((chunk ^ ((row & 3) << 1)) << 5) + b; }
+
+// last visible key of query row i (-1: none)
+__device__ __forceinline__ int last_visible_key(const ExtArgs& p, int i) {
+  const int64_t pos = p.q_pos0 + i;
+  int64_t lim = (int64_t)p.n_full - 1;
+  if (pos >= p.key_pos0) lim = (int64_t)p.n_full + (pos - p.key_pos0) / p.key_pos_step;
+  if (lim > (int64_t)p.n_keys - 1) lim = (int64_t)p.n_keys - 1;
+  return (int)lim;
+}
+
+// SPLIT_P: the probabilities enter O^T = V^T P^T as TWO bf16 terms, p = hi + lo (lo = bf16(p - hi)), so the product carries ~16 bits of
+// p instead of 8 — the precision of the decode kernels' fp32 p.  With random V the 2^-9 rounding of a single bf16 p is the largest error
+// of the whole kernel (it does not average out: the error sum has the size of the output sum).  Used when all stacked rows fit ONE
+// query tile (t * G <= 256: a launch that streams K/V once, the decode kernels' regime); it costs 16 more MFMAs per tile (48 instead of
+// 32), whose effect on the launch time has not been measured apart.  Longer launches keep the prefill kernels' single bf16 term.
+template <bool SPLIT_P>
+__global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
+  constexpr int DS = D / 16;              // QK^T k-steps
+  constexpr int DB = D / 32;              // O^T row blocks
+  constexpr int ROWB = D * 2;             // bytes per K/V row
+  constexpr int TILEB = KVT * ROWB;       // bytes per K (or V) tile
+  constexpr int SLOTB = 2 * TILEB;        // bytes per ring slot (K tile | V tile)
+  constexpr int SLOTS = ROWB / 16;        // 16-byte slots per row
+  constexpr int QK_AHEAD = 3;             // K-fragment reads pinned that many k-steps ahead of their MFMAs (attn.hip)
+  constexpr int PIECES = TILEB / 1024 / 8;   // 1-KiB DMA pieces per operand per wave
+  constexpr int RPP = 1024 / ROWB;           // tile rows per piece
+
+  extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K tile | V tile]
+  typedef __attribute__((address_space(3))) char lds_char;
+  typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
+  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+  const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int hi = lane >> 5, l31 = lane & 31;
+
+  // ---- work decomposition: block = (kv head, key split, query tile), late (long) query tiles first -----------------------------
+  int bid = blockIdx.x;
+  const int kvh = bid % p.n_kv_heads; bid /= p.n_kv_heads;
+  const int split = bid % p.n_splits;
+  const int qt = p.n_q_tiles - 1 - bid / p.n_splits;
+  const int G = p.G;
+  const int n_stack = p.t * G;                                  // stacked rows of this kv group
+  const int s_wg = qt * QTILE, s_wave = s_wg + wave * 32;
+  const int s_mine = s_wave + l31;
+  const bool live = s_mine < n_stack;
+  const int s_c = live ? s_mine : n_stack - 1;
+  const int my_row = s_c / G, my_hq = s_c - my_row * G;
+  const int my_lim = last_visible_key(p, my_row);
+  // wave- and workgroup-uniform limits (the limit ascends with the stacked index)
+  const int wg_lim = last_visible_key(p, (min(s_wg + QTILE, n_stack) - 1) / G);
+  const bool wave_live = s_wave < n_stack;
+  const int wave_lim = wave_live ? last_visible_key(p, (min(s_wave + 32, n_stack) - 1) / G) : -1;
+  const int wave_min_lim = wave_live ? last_visible_key(p, s_wave / G) : -1;
+  const float scale_log2e = p.scale_log2e;
+
+  const int j_begin = split * p.tiles_per_split;
+  const int j_end = min(j_begin + p.tiles_per_split, wg_lim >= 0 ? wg_lim / KVT + 1 : 0);
+
+  // ---- Q fragments (B operand of S^T = K Q^T): lane = (stacked row l31, k-slot half hi) -----------------------------------------
+  bf16x8 qf[DS];
+  {
+    const bf16_t* qp = p.q + (int64_t)my_row * p.q_rs + (int64_t)kvh * p.q_gs + (int64_t)my_hq * p.q_hs + hi * 8;
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) qf[ds] = *reinterpret_cast<const bf16x8*>(qp + ds * 16);
+  }
+
+  // ---- per-lane LDS read offsets ---------------------------------------------------------------------------------------------------
+  unsigned koff[DS];
+#pragma unroll
+  for (int ds = 0; ds < DS; ++ds) koff[ds] = k_lds_off(l31, 2 * ds + hi);
+  unsigned voff[DB];
+  {
+    const int g16 = lane >> 4, i16 = lane & 15;
+    const int key_l = 4 * (g16 >> 1) + (i16 >> 2);
+#pragma unroll
+    for (int db = 0; db < DB; ++db) {
+      const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
+      voff[db] = TILEB + v_lds_off(key_l, col >> 4, (col & 15) * 2);
+    }
+  }
+
+  f32x16 o_acc[DB];
+#pragma unroll
+  for (int i = 0; i < DB; ++i)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o_acc[i][r] = 0.f;
+  float m_run = -1.0e30f, l_run = 0.f;
+
+  const bf16_t* kbase = p.k + (int64_t)kvh * p.kv_gs;
+  const bf16_t* vbase = p.v + (int64_t)kvh * p.kv_gs;
+
+  // ---- LDS-DMA: wave w issues pieces q = 0 .. PIECES - 1 of K and of V; the bank swizzle is applied to the SOURCE address ----------
+  typedef __attribute__((address_space(1))) const void gvoid;
+  typedef __attribute__((address_space(3))) void lvoid;
+  unsigned dk_off[PIECES], dv_off[PIECES];
+  int d_row[PIECES], d_ks[PIECES], d_vs[PIECES];
+#pragma unroll
+  for (int q = 0; q < PIECES; ++q) {
+    const int row = (wave * PIECES + q) * RPP + lane / SLOTS;   // tile row this lane fills
+    const int ps = lane % SLOTS;                                // physical 16-byte slot in the row
+    d_ks[q] = ps ^ (row & 15);
+    d_vs[q] = (((ps >> 1) ^ ((row & 3) << 1)) << 1) | (ps & 1);
+    d_row[q] = row;
+    dk_off[q] = (unsigned)(row * p.kv_rs + d_ks[q] * 8);
+    dv_off[q] = (unsigned)(row * p.kv_rs + d_vs[q] * 8);
+  }
+  auto dma_tile = [&](int j, unsigned sl) __attribute__((always_inline)) {
+    const int64_t row0 = (int64_t)j * KVT;
+    const bf16_t* kp = kbase + row0 * p.kv_rs;          // wave-uniform bases + 32-bit lane offsets
+    const bf16_t* vp = vbase + row0 * p.kv_rs;
+    const int64_t left = (int64_t)p.n_keys - row0;      // rows of the cache behind row0 (>= 1): nothing past n_keys is ever read
+    if (left >= KVT) {
+#pragma unroll
+      for (int q = 0; q < PIECES; ++q) {
+        const int piece = wave * PIECES + q;
+        __builtin_amdgcn_global_load_lds((gvoid*)(kp + dk_off[q]), (lvoid*)(uintptr_t)(sl + piece * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gvoid*)(vp + dv_off[q]), (lvoid*)(uintptr_t)(sl + TILEB + piece * 1024), 16, 0, 0);
+      }
+    } else {                                            // last tile: clamp rows (masked later)
+#pragma unroll
+      for (int q = 0; q < PIECES; ++q) {
+        const int piece = wave * PIECES + q;
+        const int row = d_row[q] < (int)left ? d_row[q] : (int)left - 1;
+        __builtin_amdgcn_global_load_lds((gvoid*)(kp + (int64_t)row * p.kv_rs + d_ks[q] * 8),
+                                         (lvoid*)(uintptr_t)(sl + piece * 1024), 16, 0, 0);
+        __builtin_amdgcn_global_load_lds((gvoid*)(vp + (int64_t)row * p.kv_rs + d_vs[q] * 8),
+                                         (lvoid*)(uintptr_t)(sl + TILEB + piece * 1024), 16, 0, 0);
+      }
+    }
+  };
+
+  // ---- the phases of one tile ------------------------------------------------------------------------------------------------------
+  f32x16 s0, s1;
+  auto qk_phase = [&](unsigned sl) __attribute__((always_inline)) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
+    bf16x8 ka[DS], kb[DS];
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) {
+      const unsigned a = sl + koff[ds];
+      ka[ds] = *(lds_bf16x8*)(uintptr_t)(a);
+      kb[ds] = *(lds_bf16x8*)(uintptr_t)(a + 32 * ROWB);
+    }
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) {
+      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka[ds], qf[ds], s0, 0, 0, 0);
+      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb[ds], qf[ds], s1, 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_group_barrier(0x100, 2 * QK_AHEAD, 0);
+#pragma unroll
+    for (int ds = 0; ds < DS; ++ds) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      if (ds + QK_AHEAD < DS) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
+    }
+  };
+  auto sm_pv_phase = [&](unsigned sl, int k0) __attribute__((always_inline)) {
+    // key index (inside the tile) of accumulator register r: (r&3) + 8*(r>>2) + 4*hi (+32 for s1)
+    if (k0 + KVT - 1 > wave_min_lim) {                 // the tile reaches past the n_full / diagonal / n_keys limit of some row
+      const int lim = my_lim - k0;                     // key <= lim visible
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int key = (r & 3) + 8 * (r >> 2) + 4 * hi;
+        if (key > lim) s0[r] = -INFINITY;
+        if (key + 32 > lim) s1[r] = -INFINITY;
+      }
+    }
+    float mx = fmaxf(s0[0], s1[0]);
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(fmaxf(s0[r], s1[r]), mx);
+    mx = swap32_max(mx);
+    // quant_m (every launch whose shape is split over the keys): the running max moves on INTEGERS of the log2 domain.  Two histories
+    // of a row (one split or many, wherever the cuts fall) then differ by whole powers of two in every p = 2^(s - m): bf16(p) is the
+    // same mantissa, the rescales are exact, and the splits compose to the unsplit result up to fp32 summation order.  With a real-valued
+    // max the two bf16 roundings of p are unrelated and split and unsplit results sit 2.8e-3 apart (each 2.2e-3 from the exact one).
+    // Unsplit shapes keep the real-valued max: the prefill kernel's arithmetic on the same rows.
+    float m_tile = mx * scale_log2e;
+    if (p.quant_m) m_tile = ceilf(m_tile);
+    const float m_new = fmaxf(m_run, m_tile);
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+    m_run = m_new;
+    float psum = 0.f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      s0[r] = __builtin_amdgcn_exp2f(fmaf(s0[r], scale_log2e, -m_new));
+      s1[r] = __builtin_amdgcn_exp2f(fmaf(s1[r], scale_log2e, -m_new));
+      psum += s0[r] + s1[r];
+    }
+    l_run = l_run * alpha + psum;
+    if (!__all(alpha == 1.0f)) {
+#pragma unroll
+      for (int i = 0; i < DB; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o_acc[i][r] *= alpha;
+    }
+    bf16x8 pf[4];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      pf[0][j] = (__bf16)s0[j];
+      pf[1][j] = (__bf16)s0[8 + j];
+      pf[2][j] = (__bf16)s1[j];
+      pf[3][j] = (__bf16)s1[8 + j];
+    }
+    bf16x8 pl[4];
+    if (SPLIT_P) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        pl[0][j] = (__bf16)(s0[j] - (float)pf[0][j]);
+        pl[1][j] = (__bf16)(s0[8 + j] - (float)pf[1][j]);
+        pl[2][j] = (__bf16)(s1[j] - (float)pf[2][j]);
+        pl[3][j] = (__bf16)(s1[8 + j] - (float)pf[3][j]);
+      }
+    }
+    unsigned va[DB];
+#pragma unroll
+    for (int db = 0; db < DB; ++db) va[db] = sl + voff[db];
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+      for (int db = 0; db < DB; ++db) {
+        const unsigned vp = va[db] + 16 * t * ROWB;
+        const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(vp));
+        const s16x4 c = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(vp + 8 * ROWB));
+        typedef __attribute__((ext_vector_type(8))) short s16x8;
+        const s16x8 ac = __builtin_shufflevector(a, c, 0, 1, 2, 3, 4, 5, 6, 7);
+        o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ac), pf[t], o_acc[db], 0, 0, 0);
+        if (SPLIT_P) o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ac), pl[t], o_acc[db], 0, 0, 0);
+      }
+    }
+  };
+
+  // ---- main loop: tile j in LDS slot (j - j_begin) & 1, tile j + 1 lands under its MFMA work ---------------------------------------
+  if (j_begin < j_end) dma_tile(j_begin, lds0);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  int slot = 0;
+  for (int j = j_begin; j < j_end; ++j) {
+    if (j + 1 < j_end) dma_tile(j + 1, lds0 + (slot ^ 1) * SLOTB);
+    const unsigned sl = lds0 + slot * SLOTB;
+    const int k0 = j * KVT;
+    if (k0 <= wave_lim) {                               // wave-uniform: some row of this wave sees a key of the tile
+      qk_phase(sl);
+      sm_pv_phase(sl, k0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's DMA pieces have landed
+    __syncthreads();
+    slot ^= 1;
+  }
+
+  // ---- epilogue ------------------------------------------------------------------------------------------------------------------------
+  const float l_tot = swap32_sum(l_run);
+  if (!live) return;
+  const int head = kvh * G + my_hq;
+  if (p.n_splits == 1) {
+    const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+    bf16_t* op = p.o + (int64_t)my_row * p.o_rs + (int64_t)head * p.o_hs;
+#pragma unroll
+    for (int db = 0; db < DB; ++db) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const int d = 32 * db + 8 * rg + 4 * hi;
+        u32x2 w = {pack_bf16x2(o_acc[db][rg * 4 + 0] * inv, o_acc[db][rg * 4 + 1] * inv),
+                   pack_bf16x2(o_acc[db][rg * 4 + 2] * inv, o_acc[db][rg * 4 + 3] * inv)};
+        *reinterpret_cast<u32x2*>(op + d) = w;
+      }
+    }
+    if (p.lse && hi == 0)
+      p.lse[(int64_t)head * p.t + my_row] = l_tot > 0.f ? (m_run + log2f(l_tot)) * 0.69314718055994530942f : -INFINITY;
+  } else {
+    const int64_t rec = ((int64_t)split * (p.n_kv_heads * G) + head) * p.t + my_row;
+    float* po = p.po + rec * D;
+#pragma unroll
+    for (int db = 0; db < DB; ++db) {
+#pragma unroll
+      for (int rg = 0; rg < 4; ++rg) {
+        const f32x4 w = {o_acc[db][rg * 4 + 0], o_acc[db][rg * 4 + 1], o_acc[db][rg * 4 + 2], o_acc[db][rg * 4 + 3]};
+        *reinterpret_cast<f32x4*>(po + 32 * db + 8 * rg + 4 * hi) = w;
+      }
+    }
+    if (hi == 0) { p.pm[rec] = m_run; p.pl[rec] = l_tot; }
+  }
+}
+
+// ---- merge of the key splits: one wave per (head, row); lane p < n_splits holds part p's statistics, every lane two columns ------------
+__global__ __launch_bounds__(256) void extend_merge_kernel(const float* __restrict__ pm, const float* __restrict__ pl,
+                                                           const float* __restrict__ po, int n_splits, int64_t n_rec, int t,
+                                                           bf16_t* __restrict__ out, int64_t o_rs, int64_t o_hs, float* __restrict__ lse) {
+  const int lane = threadIdx.x & 63;
+  const int64_t rec = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);       // head * t + row
+  if (rec >= n_rec) return;
+  const bool has = lane < n_splits;
+  const float m = has ? pm[(int64_t)lane * n_rec + rec] : -1.0e30f;       // an empty part carries m = -1e30, l = 0
+  float M = m;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) M = fmaxf(M, __shfl_xor(M, o));
+  const float w = has ? __builtin_amdgcn_exp2f(m - M) : 0.f;
+  const float L = wave_reduce_sum(has ? pl[(int64_t)lane * n_rec + rec] * w : 0.f);
+  float a0 = 0.f, a1 = 0.f;
+  for (int s = 0; s < n_splits; ++s) {
+    const float ws = __shfl(w, s);
+    const float2 v = *reinterpret_cast<const float2*>(po + ((int64_t)s * n_rec + rec) * D + 2 * lane);
+    a0 += v.x * ws;
+    a1 += v.y * ws;
+  }
+  const float inv = L > 0.f ? 1.0f / L : 0.f;
+  const int64_t head = rec / t, row = rec - head * t;
+  *reinterpret_cast<unsigned*>(out + row * o_rs + head * o_hs + 2 * lane) = pack_bf16x2(a0 * inv, a1 * inv);
+  if (lse && lane == 0) lse[rec] = L > 0.f ? (M + log2f(L)) * 0.69314718055994530942f : -INFINITY;
+}
+
+// The split count: a function of the shapes only (and, under VITA_DEBUG, of VITA_ATTN_EXTEND_SPLITS — the tests force 1 and the maximum).
+// The smallest count that gives the launch kTargetBlocks workgroups, every split at least kMinTilesPerSplit key tiles.
+int extend_splits(int64_t t, int n_q_heads, int64_t n_keys, bool allow_override = true) {
+  const int64_t key_tiles = (n_keys + KVT - 1) / KVT;
+  const int64_t cap = key_tiles < kMaxSplits ? (key_tiles < 1 ? 1 : key_tiles) : kMaxSplits;
+  int64_t splits;
+  const char* e = vita_dev_getenv("VITA_ATTN_EXTEND_SPLITS");
+  if (allow_override && e && atoi(e) > 0) {
+    splits = atoi(e);
+  } else {
+    const int64_t blocks = (t * n_q_heads + QTILE - 1) / QTILE;     // 256-row tiles of the stacked (row, head) pairs, all kv groups
+    splits = (kTargetBlocks + blocks - 1) / blocks;
+    const int64_t by_len = key_tiles / kMinTilesPerSplit;
+    if (splits > by_len) splits = by_len;
+  }
+  if (splits > cap) splits = cap;
+  if (splits < 1) splits = 1;
+  const int64_t per = (key_tiles + splits - 1) / splits;           // whole tiles per split; drop splits that would start past the end
+  return per > 0 ? (int)((key_tiles + per - 1) / per) : 1;
+}
+
+bool extend_shape_ok(int64_t t, int n_q_heads, int64_t n_keys) { return t > 0 && n_q_heads > 0 && n_keys > 0; }
+
+}  // namespace
+
+extern "C" size_t vita_flash_attn_extend_workspace_bytes(int64_t t, int n_q_heads, int64_t n_keys) {
+  if (!extend_shape_ok(t, n_q_heads, n_keys)) return 0;
+  const int splits = extend_splits(t, n_q_heads, n_keys);
+  return splits == 1 ? 0 : (size_t)splits * (size_t)n_q_heads * (size_t)t * (D + 2) * sizeof(float);
+}
+
+extern "C" int vita_flash_attn_extend_fwd(const vita_attn_extend_params* p, void* stream) {
+  if (!p || !p->q || !p->k_cache || !p->v_cache || !p->out) return VITA_ERR_INVALID_ARG;
+  if (!extend_shape_ok(p->t, p->n_q_heads, p->n_keys) || p->n_kv_heads <= 0 || p->n_q_heads % p->n_kv_heads) return VITA_ERR_INVALID_ARG;
+  if (p->n_full < 0 || p->n_full > p->n_keys || p->key_pos_step < 1 || p->q_pos0 < 0 || p->key_pos0 < 0) return VITA_ERR_INVALID_ARG;
+  // the running max is max(score) * scale: the scale must be positive (and finite); distinct cache rows need a positive row stride
+  if (!(p->softmax_scale > 0.f) || !(p->softmax_scale < INFINITY) || p->kv_row_stride <= 0) return VITA_ERR_INVALID_ARG;
+  if (p->head_dim != D) return VITA_ERR_UNSUPPORTED;
+  if (p->n_keys > 0x7fffffffLL - 256 || p->t * (int64_t)p->n_q_heads > 0x7fffff00LL || p->q_pos0 + p->t > (int64_t(1) << 40))
+    return VITA_ERR_UNSUPPORTED;
+  const int64_t strides[] = {p->q_row_stride, p->q_group_stride, p->q_head_stride, p->kv_row_stride, p->kv_group_stride,
+                             p->out_row_stride, p->out_head_stride};
+  for (int64_t s : strides)
+    if (s & 7) return VITA_ERR_UNSUPPORTED;            // 16-byte vector loads / LDS-DMA pieces
+  if (p->kv_row_stride * KVT > 0x7fffffffLL) return VITA_ERR_UNSUPPORTED;   // 32-bit lane offsets inside a tile
+  const uintptr_t bases = (uintptr_t)p->q | (uintptr_t)p->k_cache | (uintptr_t)p->v_cache | (uintptr_t)p->out;
+  if (bases & 15) return VITA_ERR_UNSUPPORTED;         // 16-byte vector loads / LDS-DMA pieces start at the bases
+
+  ExtArgs a;
+  a.q = (const bf16_t*)p->q; a.q_rs = p->q_row_stride; a.q_gs = p->q_group_stride; a.q_hs = p->q_head_stride;
+  a.k = (const bf16_t*)p->k_cache; a.v = (const bf16_t*)p->v_cache; a.kv_rs = p->kv_row_stride; a.kv_gs = p->kv_group_stride;
+  a.o = (bf16_t*)p->out; a.o_rs = p->out_row_stride; a.o_hs = p->out_head_stride;
+  a.lse = p->lse;
+  a.t = (int)p->t; a.G = p->n_q_heads / p->n_kv_heads; a.n_kv_heads = p->n_kv_heads;
+  a.n_q_tiles = (int)((p->t * a.G + QTILE - 1) / QTILE);
+  a.n_keys = (int)p->n_keys; a.n_full = (int)p->n_full;
+  a.q_pos0 = p->q_pos0; a.key_pos0 = p->key_pos0; a.key_pos_step = p->key_pos_step;
+  a.n_splits = extend_splits(p->t, p->n_q_heads, p->n_keys);
+  const int64_t key_tiles = (p->n_keys + KVT - 1) / KVT;
+  a.tiles_per_split = (int)((key_tiles + a.n_splits - 1) / a.n_splits);
+  a.quant_m = extend_splits(p->t, p->n_q_heads, p->n_keys, false) > 1;      // by shape, whatever the developer switch forces
+  a.scale_log2e = p->softmax_scale * 1.44269504088896340736f;
+  const int64_t n_rec = (int64_t)p->n_q_heads * p->t;
+  a.pm = a.pl = a.po = nullptr;
+  if (a.n_splits > 1) {
+    const size_t need = (size_t)a.n_splits * (size_t)n_rec * (D + 2) * sizeof(float);
+    if (!p->workspace || p->workspace_bytes < need || ((uintptr_t)p->workspace & 15)) return VITA_ERR_INVALID_ARG;
+    a.po = (float*)p->workspace;                                   // [splits][heads][t][128], then m and l [splits][heads][t]
+    a.pm = a.po + (int64_t)a.n_splits * n_rec * D;
+    a.pl = a.pm + (int64_t)a.n_splits * n_rec;
+  }
+  const int64_t nblocks = (int64_t)a.n_kv_heads * a.n_q_tiles * a.n_splits;
+  if (nblocks > 0x7fffffff) return VITA_ERR_UNSUPPORTED;
+
+  constexpr int lds = 2 * 2 * KVT * D * 2;
+  static std::atomic<unsigned long long> attr_set{0};
+  vita_device_once(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_extend_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_extend_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  });
+  hipStream_t st = (hipStream_t)stream;
+  if (a.n_q_tiles == 1) hipLaunchKernelGGL(flash_extend_kernel<true>, dim3((unsigned)nblocks), dim3(512), lds, st, a);
+  else hipLaunchKernelGGL(flash_extend_kernel<false>, dim3((unsigned)nblocks), dim3(512), lds, st, a);
+  int rc = vita_check_launch();
+  if (rc != VITA_OK || a.n_splits == 1) return rc;
+  hipLaunchKernelGGL(extend_merge_kernel, dim3((unsigned)((n_rec + 3) / 4)), dim3(256), 0, st, a.pm, a.pl, a.po, a.n_splits, n_rec, a.t,
+                     a.o, a.o_rs, a.o_hs, a.lse);
+  return vita_check_launch();
+}

@@ -49,6 +49,9 @@ class GPTConfig:
         return (self.heads + 2 * self.kv_groups) * self.head_dim
 
 
+EXTEND_MIN_TOKENS = 1 << 30      # off until profiles/r08_extend.jsonl exists: then the smallest t faster at 16K and at 128K
+
+
 class GPTVLModel:
     def __init__(self, cfg: GPTConfig, params: dict, external_feature_model=None):
         self.cfg, self.p = cfg, params
@@ -65,6 +68,9 @@ class GPTVLModel:
         self.decode_fused = bool(int(os.environ.get("VITA_DECODE_FUSED", "1")))   # one C call per half layer (decode)
         self.decode_graph = bool(int(os.environ.get("VITA_DECODE_GRAPH", "0")))   # capture the token step (CP = 1)
         self.attn_events = None      # bench.py: list collecting (start, end) HIP events per attention launch
+        # cached calls that feed at least this many tokens (CP = 1, TP = 1) run ONE pass through the prefill layers with
+        # ops.flash_attn_extend instead of one decode step per token (where the default comes from)
+        self.extend_min_tokens = int(os.environ.get("VITA_EXTEND_MIN_TOKENS", str(EXTEND_MIN_TOKENS)))
 
     # ---------------------------------------------------------------------------------------------
     @classmethod
@@ -96,36 +102,44 @@ class GPTVLModel:
         return cls(cfg, p, external_feature_model)
 
     # ---------------------------------------------------------------------------------------------
-    def _workspace(self, s: int, device):
-        ws = self._ws.get(s)
+    def _workspace(self, s: int, device, extend: bool = False):
+        """Activations of s rows.  One prefill size and one extend size are kept side by side: a conversation alternates a long
+        prefill with short follow-ups, and neither may evict the other on every turn."""
+        key = ("extend", s) if extend else s
+        ws = self._ws.get(key)
         if ws is None:
             c = self.cfg
             e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=device)  # noqa: E731
-            n_msg = self.kv_split if self.kv_split is not None else ops.cp_kv_split(c.kv_groups, c.heads, s)
-            ws = {"x": e(s, c.hidden), "qkv": e(s, c.qkv_out), "ctx": e(1, s, c.heads, c.head_dim),
-                  "act": e(s, c.ffn), "kv": e(n_msg, 2, s, c.kv_groups // n_msg, c.head_dim)}
-            self._ws = {k: v for k, v in self._ws.items() if k == "decode"}    # keep one prefill size only
-            self._ws[s] = ws
+            ws = {"x": e(s, c.hidden), "qkv": e(s, c.qkv_out), "ctx": e(1, s, c.heads, c.head_dim), "act": e(s, c.ffn)}
+            if not extend:
+                n_msg = self.kv_split if self.kv_split is not None else ops.cp_kv_split(c.kv_groups, c.heads, s)
+                ws["kv"] = e(n_msg, 2, s, c.kv_groups // n_msg, c.head_dim)
+            self._ws = {k: v for k, v in self._ws.items() if k == "decode" or isinstance(k, tuple) != extend}   # one size of this kind
+            self._ws[key] = ws
         return ws
 
-    def decoder_layer(self, h: torch.Tensor, lp: dict, cos, sin, ws, kv_dst: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def decoder_layer(self, h: torch.Tensor, lp: dict, cos, sin, ws, kv_dst: Optional[torch.Tensor] = None,
+                      cached_rows: Optional[int] = None) -> torch.Tensor:
         """h [s, hidden] updated in place.  kv_dst [2, cap, groups, d]: this rank's cache shard for the
-        layer; the rotated K and V rows of the local sequence are stored into rows [0, s)."""
+        layer; the rotated K and V rows of the local sequence are stored into rows [0, s).
+        cached_rows = L (CP = 1): the s rows are NEW tokens behind L rows the shard already holds — their K / V go to rows
+        [L, L + s) and the attention runs over the L + s cache rows (ops.flash_attn_extend); everything else is the same layer."""
         c = self.cfg
         s = h.shape[0]
         cp = mpu.get_context_parallel_world_size()
-        use_cp = cp > 1 or self.force_cp_path          # force: exercise pack + all-gather + chunk tables at CP = 1
+        row0 = cached_rows or 0
+        use_cp = (cp > 1 or self.force_cp_path) and cached_rows is None   # force: exercise pack + all-gather + chunk tables at CP = 1
         x = ops.rmsnorm(h, lp["ln1"], c.eps, out=ws["x"])
         qkv = ops.gemm(x, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"])
-        ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ws["kv"] if use_cp else None, ws["kv"].shape[0])
+        ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ws["kv"] if use_cp else None, ws["kv"].shape[0] if "kv" in ws else 1)
         m5 = qkv.view(1, s, c.kv_groups, c.qpg + 2, c.head_dim)
         q5 = m5[:, :, :, : c.qpg]                                  # grouped query view, read in place
         if kv_dst is not None:
             if use_cp:
                 context_parallel.unpack_kv(ws["kv"], out=kv_dst[:, :s])
             else:
-                kv_dst[0, :s].copy_(m5[0, :, :, c.qpg])
-                kv_dst[1, :s].copy_(m5[0, :, :, c.qpg + 1])
+                kv_dst[0, row0: row0 + s].copy_(m5[0, :, :, c.qpg])
+                kv_dst[1, row0: row0 + s].copy_(m5[0, :, :, c.qpg + 1])
         ev = None
         if self.attn_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -136,9 +150,14 @@ class GPTVLModel:
         else:
             if ev:
                 ev[0].record()
-            seg = training_utils.get_packed_segments()       # position ids with resets -> packed samples
-            ctx = ops.flash_attn(q5, m5[:, :, :, c.qpg], m5[:, :, :, c.qpg + 1], causal=True, out=ws["ctx"],
-                                 seg_start=None if seg is None else seg[0])
+            if cached_rows is not None:
+                # the shard is in sequence order at CP = 1: visibility is by cache row, whatever position ids rotated the rows
+                ops.flash_attn_extend(q5[0], kv_dst[0], kv_dst[1], row0 + s, q_pos0=row0, out=ws["ctx"][0])
+                ctx = ws["ctx"]
+            else:
+                seg = training_utils.get_packed_segments()       # position ids with resets -> packed samples
+                ctx = ops.flash_attn(q5, m5[:, :, :, c.qpg], m5[:, :, :, c.qpg + 1], causal=True, out=ws["ctx"],
+                                     seg_start=None if seg is None else seg[0])
             if ev:
                 ev[1].record()
         if ev:
@@ -457,7 +476,10 @@ class GPTVLModel:
             kv = ip.key_value_memory_dict[1]
             if ip.local_len + 1 > kv.shape[1]:
                 raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
-            return self._decode_graphed(input_ids[0], position_ids[0], ip).view(1, 1, -1).clone()
+            logits = self._decode_graphed(input_ids[0], position_ids[0], ip).view(1, 1, -1).clone()
+            return ops.logit_postprocess_(logits, self.cfg.output_multiplier_scale, self.cfg.output_logit_softcapping)
+        if t >= max(2, self.extend_min_tokens) and tp == 1 and mpu.get_context_parallel_world_size() == 1:
+            return self._extend_forward(input_ids, position_ids, ip)
         ip._graph = None                      # eager steps move the python-side counters only
         # tensor parallelism (the released server runs TP 8 x CP 4, server_cp .sh:102-104): the kernel-by-kernel step, whose
         # row-parallel GEMVs all-reduce their partial sums; the C-side fused layer adds the residual inside the GEMV epilogue
@@ -466,4 +488,37 @@ class GPTVLModel:
         rows = rows[0] if t == 1 else torch.cat(rows, dim=0)
         logits, _ = self.output_layer(rows.view(t, 1, -1), weight=None, logit_mask=None)
         logits = self._gather_vocab_parallel(logits)
+        ops.logit_postprocess_(logits, self.cfg.output_multiplier_scale, self.cfg.output_logit_softcapping)   # as the prefill (no-op at 0 / 0)
+        return logits.transpose(0, 1).contiguous()
+
+    def _extend_forward(self, input_ids: torch.Tensor, position_ids: torch.Tensor, ip) -> torch.Tensor:
+        """t > 1 new tokens behind the cached context in ONE pass (CP = 1, TP = 1): the prefill's layers on t rows, K / V appended to
+        the shard, attention over the whole shard (vita_flash_attn_extend_fwd) — a follow-up turn, or one chunk of a chunked prefill.
+        What modeling_long_vita.py:150-202 does with q_len > 1 behind a DynamicCache.  Returns logits [1, n, vocab] of the rows
+        ip.logit_mask ([1, t]) keeps, of all t rows without one."""
+        c = self.cfg
+        t = input_ids.shape[1]
+        row0 = ip.local_len
+        if row0 + t > ip.key_value_memory_dict[1].shape[1]:
+            raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
+        logit_mask = getattr(ip, "logit_mask", None)
+        if logit_mask is not None and tuple(logit_mask.shape) != (1, t):
+            raise ValueError(f"logit_mask must be [1, {t}] on a cached call of {t} tokens")
+        ip._graph = None                      # the captured token step holds its own row counters
+        with tracing.range("extend: embedding"):
+            h = ops.row_gather(self.p["embed"], input_ids[0].contiguous())                # [t, hidden]
+        cos, sin = ops.rope_table(position_ids[0].contiguous(), self.rotary_pos_emb.inv_freq)
+        ws = self._workspace(t, h.device, extend=True)
+        for li, lp in enumerate(self.p["layers"]):
+            with tracing.range(f"extend: layer {li}"):
+                self.decoder_layer(h, lp, cos, sin, ws, ip.key_value_memory_dict[li + 1], cached_rows=row0)
+        ip.local_len = row0 + t
+        ip.decode_steps += t
+        ip.consumed_tokens = t
+        rows = h if logit_mask is None else ops.row_gather(h, ops.mask_to_index(logit_mask.reshape(-1)))
+        rows = ops.rmsnorm(rows, self.p["final_ln"], c.eps)
+        logits, _ = self.output_layer(rows.view(rows.shape[0], 1, -1), weight=None, logit_mask=None)
+        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)
+        if bool(torch.isnan(logits.float().sum())):                                       # as the prefill (gpt_vl_model.py:393-396)
+            raise ValueError("found NaN in local forward logits calculation")
         return logits.transpose(0, 1).contiguous()

@@ -175,9 +175,15 @@ class LongVITAForCausalLM:
                 raise NotImplementedError("cached decode steps take input_ids")
             off = step.inference_params.sequence_len_offset
             pos = position_ids.to(self.device) if position_ids is not None else torch.arange(off, off + s, device=self.device)[None]
-            step.inference_params.logit_mask = None
-            logits = step(input_ids, pos, None)                                         # [1, s, V]
-            if num_logits_to_keep:
+            ip = step.inference_params
+            self._grow_cache(ip, s)
+            ip.logit_mask = None
+            if num_logits_to_keep and 0 < num_logits_to_keep < s:                        # head on the kept rows only (the one-pass extend
+                ip.logit_mask = torch.zeros(1, s, dtype=torch.bool, device=self.device)  # path; the per-token loop returns every row)
+                ip.logit_mask[0, -num_logits_to_keep:] = True
+            logits = step(input_ids, pos, None)                                         # [1, s or kept, V]
+            ip.logit_mask = None
+            if num_logits_to_keep and logits.shape[1] > num_logits_to_keep:
                 logits = logits[:, -num_logits_to_keep:]
             out = _output(logits, past_key_values)
             return out if return_dict is not False else (out.logits, out.past_key_values)
@@ -209,14 +215,39 @@ class LongVITAForCausalLM:
 
     __call__ = forward
 
+    def _grow_cache(self, ip, n_new: int) -> None:
+        """transformers' DynamicCache has no ceiling: when a cached call would run past the shard's capacity, move the valid rows to a
+        larger allocation: at least `cache_headroom` spare rows behind the new tokens and at least half as many rows again as before, so
+        that a long conversation copies its cache a logarithmic number of times.  The pointers the decode step captured go."""
+        from . import parallel_state as mpu
+        kv = ip.key_value_memory_dict
+        cap = kv[1].shape[1]
+        need = ip.local_len + n_new
+        if need <= cap or mpu.get_context_parallel_world_size() > 1:
+            return
+        layers = len(kv)
+        old = kv[1]
+        rows = max(need + max(int(self.cache_headroom), 1), cap + cap // 2)
+        buf = torch.empty((layers, 2, rows) + tuple(old.shape[2:]), dtype=old.dtype, device=old.device)
+        for li in range(layers):
+            buf[li, :, : ip.local_len].copy_(kv[li + 1][:, : ip.local_len])
+        ip.key_value_memory_dict = {li + 1: buf[li] for li in range(layers)}
+        ip.max_sequence_length = max(ip.max_sequence_length, ip.sequence_len_offset + n_new + int(self.cache_headroom))
+        ip._graph = None
+        ip._layer_structs = None
+
     # -- generate -------------------------------------------------------------------------------------
     @torch.no_grad()
     def generate(self, inputs: Optional[torch.Tensor] = None, images: Optional[torch.Tensor] = None,
                  image_indices: Optional[torch.Tensor] = None, input_ids: Optional[torch.Tensor] = None, generation_config=None,
-                 max_new_tokens: Optional[int] = None, do_sample: Optional[bool] = None, eos_token_id=None, **kwargs):
+                 max_new_tokens: Optional[int] = None, do_sample: Optional[bool] = None, eos_token_id=None, past_key_values=None,
+                 return_dict_in_generate: bool = False, **kwargs):
         """`model.generate(inputs=inputs, images=images, image_indices=image_indices)` (inference_long_vita.py:868): one prefill over
         the prompt (ViT + scatter + decoder), then one cached step per token; stops behind the first end-of-sequence token.  Returns
-        [1, prompt + generated] like transformers' greedy search."""
+        [1, prompt + generated] like transformers' greedy search.
+        past_key_values = the cache of an earlier call and inputs = the WHOLE conversation (as transformers takes it): only the tokens
+        behind cache.get_seq_length() are fed, in one extend step, then one cached step per token.  return_dict_in_generate: an object
+        with `sequences` and `past_key_values` (the cache holds everything but the last generated token, as transformers' does)."""
         ids = inputs if inputs is not None else input_ids
         if ids is None or ids.dim() != 2 or ids.shape[0] != 1:
             raise ValueError("generate(inputs=[1, S] token ids) — the Long-VITA path runs batch 1")
@@ -227,6 +258,8 @@ class LongVITAForCausalLM:
         eos = set() if eos is None else set(eos) if isinstance(eos, (list, tuple, set)) else {int(eos)}
         ids = ids.to(self.device)
         s = ids.shape[1]
+        if past_key_values is not None or return_dict_in_generate:
+            return self._generate_cached(ids, images, image_indices, past_key_values, n_new, eos, bool(do_sample), gc, return_dict_in_generate)
         pad = _get(gc, "pad_token_id")
         tokens = torch.full((1, s + n_new), 0 if pad is None else int(pad), dtype=torch.long, device=self.device)
         tokens[:, :s] = ids
@@ -241,3 +274,29 @@ class LongVITAForCausalLM:
             if int(out[0, -1]) in eos:
                 break
         return out.clone()
+
+    def _generate_cached(self, ids, images, image_indices, cache, n_new, eos, do_sample, gc, return_dict):
+        """The decode loop over forward(past_key_values=): the uncached part of `ids` in one call (a prefill without a cache, an extend
+        step behind one), then single-token steps; sampling and the stopping rule are the loop's above."""
+        s = ids.shape[1]
+        if cache is not None and not isinstance(cache, HipCache):
+            raise TypeError("past_key_values must come from this model's own forward(use_cache=True) / generate(return_dict_in_generate=True)")
+        if cache is not None and len(cache) > 0:
+            seen = cache.get_seq_length()
+            if s <= seen:
+                raise ValueError(f"generate(past_key_values=): inputs hold {s} tokens, the cache already {seen} — pass the whole conversation "
+                                 "with at least one token the cache has not seen (its logits start the answer)")
+            out = self.forward(input_ids=ids[:, seen:], past_key_values=cache, num_logits_to_keep=1)
+        else:
+            out = self.forward(input_ids=ids, images=images, image_indices=image_indices, use_cache=True, num_logits_to_keep=1)
+        cache = out.past_key_values
+        kw = dict(do_sample=do_sample, top_k=int(_get(gc, "top_k", 0) or 0) if do_sample else 0,
+                  top_p=float(_get(gc, "top_p", 0.0) or 0.0) if do_sample else 0.0, temperature=float(_get(gc, "temperature", 1.0) or 1.0))
+        seq = ids
+        for j in range(n_new):
+            _, tok = generation._sample_strategy(out.logits[:, -1, :], **kw)
+            seq = torch.cat([seq, tok.view(1, 1)], dim=1)
+            if int(tok[0]) in eos or j + 1 == n_new:
+                break
+            out = self.forward(input_ids=tok.view(1, 1), past_key_values=cache)
+        return types.SimpleNamespace(sequences=seq, past_key_values=cache) if return_dict else seq

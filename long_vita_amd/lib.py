@@ -99,6 +99,22 @@ class CpAttnParams(C.Structure):
     ]
 
 
+class AttnExtendParams(C.Structure):
+    """Mirror of ``vita_attn_extend_params`` (include/vita_hip.h)."""
+
+    _fields_ = [
+        ("q", C.c_void_p), ("q_row_stride", C.c_int64), ("q_group_stride", C.c_int64), ("q_head_stride", C.c_int64),
+        ("k_cache", C.c_void_p), ("v_cache", C.c_void_p), ("kv_row_stride", C.c_int64), ("kv_group_stride", C.c_int64),
+        ("out", C.c_void_p), ("out_row_stride", C.c_int64), ("out_head_stride", C.c_int64),
+        ("lse", C.c_void_p),
+        ("t", C.c_int64), ("n_keys", C.c_int64), ("n_full", C.c_int64),
+        ("q_pos0", C.c_int64), ("key_pos0", C.c_int64), ("key_pos_step", C.c_int64),
+        ("n_q_heads", C.c_int), ("n_kv_heads", C.c_int), ("head_dim", C.c_int),
+        ("softmax_scale", C.c_float),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+    ]
+
+
 class DecodeLayerParams(C.Structure):
     """Mirror of ``vita_decode_layer_params`` (include/vita_hip.h)."""
 
@@ -154,6 +170,8 @@ PROTOTYPES = {
     "vita_colsum_bf16_ordered": (_i, [_p, _l, _p, _l, _i, _p, _p]),
     "vita_gemm_skinny_bf16": (_i, [_p, _l, _p, _l, _p, _l, _i, _l, _l, _i, _p]),
     "vita_flash_attn_fwd": (_i, [C.POINTER(AttnParams), _p]),
+    "vita_flash_attn_extend_workspace_bytes": (C.c_size_t, [_l, _i, _l]),
+    "vita_flash_attn_extend_fwd": (_i, [C.POINTER(AttnExtendParams), _p]),
     "vita_patchify14": (_i, [_p, _p, _l, _i, _i, _i, _p]),
     "vita_vit_assemble": (_i, [_p, _p, _p, _p, _l, _i, _i, _i, _p]),
     "vita_pixel_shuffle_ln": (_i, [_p, _p, _p, _p, _l, _i, _i, _i, _f, _p]),

@@ -16,7 +16,7 @@ import torch
 
 from . import lib as _L
 from .lib import (EPI_BIAS, EPI_BIAS2_GELU, EPI_BIAS2_GELU_TANH, EPI_BIAS2_RES, EPI_BIAS_GELU, EPI_BIAS_SCALE_RES, EPI_NONE,  # noqa: F401
-                  EPI_RESIDUAL, EPI_SWIGLU, AttnParams)
+                  EPI_RESIDUAL, EPI_SWIGLU, AttnExtendParams, AttnParams)
 
 BF16 = torch.bfloat16
 
@@ -538,6 +538,63 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: boo
     if seg_start is not None:           # packed sequences: int32 [rows], first row of each query row's segment
         p.q_seg_start = _dev(seg_start, "seg_start", torch.int32)
     _L.check(_L.load().vita_flash_attn_fwd(C.byref(p), _stream()), "vita_flash_attn_fwd")
+    return (o, lse) if return_lse else o
+
+
+_extend_ws: dict = {}      # device index -> the fp32 split partials of flash_attn_extend: one buffer, grown to the largest request
+
+
+def _extend_workspace(nbytes: int, device: torch.device) -> torch.Tensor:
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    ws = _extend_ws.get(key)
+    if ws is None or ws.numel() * 4 < nbytes:
+        _extend_ws.pop(key, None)                       # free the smaller one first
+        ws = _extend_ws[key] = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device)
+    return ws
+
+
+def flash_attn_extend(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, n_keys: int, *, q_pos0: int,
+                      n_full: Optional[int] = None, key_pos0: Optional[int] = None, key_pos_step: int = 1,
+                      softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None, return_lse: bool = False):
+    """t new query rows against rows [0, n_keys) of a KV cache that already holds their own (rotated) K / V rows.
+    q [t, Hkv, G, D] — a *view* (the grouped query part of the mixed QKV activation); k_cache / v_cache [cap, Hkv, D] views with
+    the same strides, cap >= n_keys.  Row i sits at position q_pos0 + i; keys [0, n_full) are visible to every row, key k >= n_full
+    sits at key_pos0 + (k - n_full) * key_pos_step and is visible iff that is <= the row's position.  Defaults: the appended rows
+    are the last t of the cache at positions q_pos0 .. (n_full = n_keys - t, key_pos0 = q_pos0).
+    Returns o [t, Hq, D] bf16 (and lse [Hq, t] fp32, natural log; -inf and a zero row where nothing is visible)."""
+    if q.dim() != 4 or k_cache.dim() != 3 or v_cache.dim() != 3:
+        raise ValueError("flash_attn_extend: q [t, Hkv, G, D], caches [cap, Hkv, D]")
+    t, Hkv, G, D = q.shape
+    if k_cache.shape[1:] != (Hkv, D) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
+        raise ValueError("flash_attn_extend: k / v cache views must be [cap, Hkv, D] with the same strides")
+    if q.stride(3) != 1 or k_cache.stride(2) != 1:
+        raise ValueError("head_dim must be contiguous")
+    n_keys = int(n_keys)
+    if n_keys > k_cache.shape[0]:
+        raise ValueError("n_keys exceeds the cache rows")
+    n_full = n_keys - t if n_full is None else int(n_full)
+    key_pos0 = int(q_pos0) if key_pos0 is None else int(key_pos0)
+    Hq = Hkv * G
+    o = torch.empty((t, Hq, D), dtype=BF16, device=q.device) if out is None else out
+    if tuple(o.shape) != (t, Hq, D) or o.stride(2) != 1:
+        raise ValueError("out must be [t, Hq, D] with a unit inner stride")
+    lse = torch.empty((Hq, t), dtype=torch.float32, device=q.device) if return_lse else None
+    h = _L.load()
+    p = AttnExtendParams()
+    p.q, p.q_row_stride, p.q_group_stride, p.q_head_stride = _dev(q, "q", BF16), q.stride(0), q.stride(1), q.stride(2)
+    p.k_cache, p.v_cache = _dev(k_cache, "k_cache", BF16), _dev(v_cache, "v_cache", BF16)
+    p.kv_row_stride, p.kv_group_stride = k_cache.stride(0), k_cache.stride(1)
+    p.out, p.out_row_stride, p.out_head_stride = _dev(o, "out", BF16), o.stride(0), o.stride(1)
+    p.lse = _opt(lse, "lse")
+    p.t, p.n_keys, p.n_full = t, n_keys, n_full
+    p.q_pos0, p.key_pos0, p.key_pos_step = int(q_pos0), key_pos0, int(key_pos_step)
+    p.n_q_heads, p.n_kv_heads, p.head_dim = Hq, Hkv, D
+    p.softmax_scale = float(softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D))
+    nbytes = h.vita_flash_attn_extend_workspace_bytes(t, Hq, n_keys) if t > 0 and n_keys > 0 else 0
+    if nbytes:
+        ws = _extend_workspace(nbytes, q.device)
+        p.workspace, p.workspace_bytes = _dev(ws, "workspace", torch.float32), nbytes
+    _L.check(h.vita_flash_attn_extend_fwd(C.byref(p), _stream()), "vita_flash_attn_extend_fwd")
     return (o, lse) if return_lse else o
 
 
