@@ -176,6 +176,15 @@ int vita_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void*
                    int64_t M, int64_t N, int64_t K, int epilogue, const void* bias,
                    const void* scale, const void* R, int64_t ldr, void* stream);
 
+/* vita_gemm_bf16 on M rows TAKEN OUT of a call over M_select >= M rows: the kernel is chosen as that call chooses it (the 256 x 256 or
+ * the 128 x 128 tile, by the tile count of M_select rows), so every row passes through the accumulation order it has there and comes out
+ * with the same bits.  M may be smaller than a tile and no multiple of it: rows behind M are neither read nor written.  For the per-row
+ * tail of a decoder layer on the rows a logit mask keeps (M/inference/text_generation/generation.py:123-205 keeps one row of a
+ * prefill; M/core/models/multimodal/gpt_vl_model.py:339-347 reads only those).  M_select < M: VITA_ERR_INVALID_ARG. */
+int vita_gemm_bf16_select(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                          int epilogue, const void* bias, const void* scale, const void* R, int64_t ldr, int64_t M_select,
+                          void* stream);
+
 /* The weight-gradient GEMM without transposes (r03): C[M, N] = A_t^T W_t, BOTH operands contraction-major — A_t [K, M] (row stride
  * lda), W_t [K, N] (ldw).  grad_weight = grad_output.t().matmul(total_input) (M/core/tensor_parallel/layers.py:522-523) is exactly this
  * with A_t = grad_output [tokens, out], W_t = total_input [tokens, in] as the forward left them: no vita_transpose_bf16 pass over
@@ -259,6 +268,16 @@ typedef struct {
 } vita_attn_params;
 
 int vita_flash_attn_fwd(const vita_attn_params* p, void* stream);
+
+/* The same attention for a WINDOW of query tiles: q_tiles (HOST, n_q_tiles distinct indices, any order, at most 32) names 256-row
+ * tiles of the query rows (tile t = rows 256 t .. 256 t + 255); only their workgroups are launched, heaviest first, and O (and lse)
+ * are written for their rows alone, at their usual addresses.  Each workgroup is the one vita_flash_attn_fwd runs for that tile — the
+ * same kernel, rows, key walk and masks — so those rows carry the bits of the full launch.  For the last decoder layer of a prefill
+ * whose logit mask keeps a few rows (the decode loop keeps one, M/inference/text_generation/generation.py:123-205): K / V of every row
+ * still exist, attention is needed for the kept rows only.  Plain causal geometry of one chunk (n_q_chunks = n_kv_chunks = 1),
+ * head_dim 128; anything else: VITA_ERR_UNSUPPORTED (the caller runs the full launch).  A tile out of range or listed twice:
+ * VITA_ERR_INVALID_ARG. */
+int vita_flash_attn_fwd_window(const vita_attn_params* p, const int32_t* q_tiles, int n_q_tiles, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Attention of t >= 1 NEW tokens behind a KV cache that already holds their rotated K / V rows (attn_extend.hip): a follow-up turn or

@@ -116,8 +116,9 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
   const int kvh = bid % p.n_kv_heads; bid /= p.n_kv_heads;
   const int hq = bid % G; bid /= G;
   const int n_q_tiles = p.n_q_chunks * p.tiles_per_q_chunk;
-  const int qt_order = bid % n_q_tiles;
-  const int b = bid / n_q_tiles;
+  const int n_launched = p.win_n ? p.win_n : n_q_tiles;          // windowed launch: only the listed tiles have workgroups
+  const int qt_order = p.win_n ? p.win_qt[bid % n_launched] : bid % n_launched;
+  const int b = bid / n_launched;
   const int head = kvh * G + hq;
   const int qc = p.q_order[qt_order / p.tiles_per_q_chunk];
   const int qti = p.tiles_per_q_chunk - 1 - qt_order % p.tiles_per_q_chunk;
@@ -528,7 +529,9 @@ extern "C" int vita_attn_merge(void* o_a, int64_t oa_row_stride, int64_t oa_head
   return vita_check_launch();
 }
 
-extern "C" int vita_flash_attn_fwd(const vita_attn_params* p, void* stream) {
+// win_tiles == nullptr: the full launch.  Otherwise n_win distinct 256-row query tiles of a plain causal single-chunk geometry: the grid
+// holds those tiles' workgroups only, each decoding to the workgroup the full launch runs for its tile (AttnArgs::win_qt)
+static int flash_attn_fwd_impl(const vita_attn_params* p, const int32_t* win_tiles, int n_win, void* stream) {
   if (!p || !p->q || !p->k || !p->v || !p->o) return VITA_ERR_INVALID_ARG;
   if (p->batch <= 0 || p->n_q_heads <= 0 || p->n_kv_heads <= 0 || p->chunk_len <= 0 ||
       p->n_q_chunks <= 0 || p->n_kv_chunks <= 0 || !p->q_chunk_gid || !p->kv_chunk_gid ||
@@ -573,9 +576,29 @@ extern "C" int vita_flash_attn_fwd(const vita_attn_params* p, void* stream) {
       const int t = a.q_order[j]; a.q_order[j] = a.q_order[j - 1]; a.q_order[j - 1] = t;
     }
   for (int i = 0; i < p->n_kv_chunks; ++i) { a.kv_gid[i] = p->kv_chunk_gid[i]; a.kv_row[i] = p->kv_chunk_row[i]; }
-  const int64_t nblocks = (int64_t)p->batch * p->n_q_heads * p->n_q_chunks * a.tiles_per_q_chunk;
+  int64_t nblocks = (int64_t)p->batch * p->n_q_heads * p->n_q_chunks * a.tiles_per_q_chunk;
   if (nblocks > 0x7fffffff) return VITA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
+  a.win_n = 0;
+  if (win_tiles) {
+    if (n_win <= 0) return VITA_ERR_INVALID_ARG;
+    if (!p->causal || p->n_q_chunks != 1 || p->n_kv_chunks != 1 || p->head_dim != 128 || n_win > kMaxWindowTiles) return VITA_ERR_UNSUPPORTED;
+    // heaviest (last) tile first, as the full launch orders them; position of tile t in that order = tiles - 1 - t
+    for (int i = 0; i < n_win; ++i) {
+      const int t = win_tiles[i];
+      if (t < 0 || t >= a.tiles_per_q_chunk) return VITA_ERR_INVALID_ARG;
+      int j = i;
+      for (; j > 0 && a.win_qt[j - 1] > a.tiles_per_q_chunk - 1 - t; --j) a.win_qt[j] = a.win_qt[j - 1];
+      a.win_qt[j] = a.tiles_per_q_chunk - 1 - t;
+    }
+    for (int i = 1; i < n_win; ++i)
+      if (a.win_qt[i] == a.win_qt[i - 1]) return VITA_ERR_INVALID_ARG;          // a tile listed twice
+    a.win_n = n_win;
+    nblocks = (int64_t)p->batch * p->n_q_heads * n_win;
+    // the kernel the full launch picks for this geometry, or none
+    if (vita_attn64_eligible(a, p->head_dim, true)) return vita_attn64_launch(a, nblocks, st);
+    return launch_attn<128, true>(a, nblocks, st);
+  }
   // d = 128 causal with whole 256-row / 64-key tiles: the 4 x 64-row in-wave-pipelined kernel (attn64.hip)
   if (vita_attn64_eligible(a, p->head_dim, p->causal != 0)) return vita_attn64_launch(a, nblocks, st);
   // d = 64 non-causal (the vision towers): the same structure at head size 64, ragged rows / keys (attn64v.hip)
@@ -583,4 +606,11 @@ extern "C" int vita_flash_attn_fwd(const vita_attn_params* p, void* stream) {
   if (p->head_dim == 128) return p->causal ? launch_attn<128, true>(a, nblocks, st) : launch_attn<128, false>(a, nblocks, st);
   if (p->head_dim == 96) return p->causal ? launch_attn<96, true>(a, nblocks, st) : launch_attn<96, false>(a, nblocks, st);
   return p->causal ? launch_attn<64, true>(a, nblocks, st) : launch_attn<64, false>(a, nblocks, st);
+}
+
+extern "C" int vita_flash_attn_fwd(const vita_attn_params* p, void* stream) { return flash_attn_fwd_impl(p, nullptr, 0, stream); }
+
+extern "C" int vita_flash_attn_fwd_window(const vita_attn_params* p, const int32_t* q_tiles, int n_q_tiles, void* stream) {
+  if (!q_tiles) return VITA_ERR_INVALID_ARG;
+  return flash_attn_fwd_impl(p, q_tiles, n_q_tiles, stream);
 }

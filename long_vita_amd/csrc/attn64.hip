@@ -104,8 +104,9 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   const int kvh = bid % p.n_kv_heads; bid /= p.n_kv_heads;
   const int hq = bid % G; bid /= G;
   const int n_q_tiles = p.n_q_chunks * p.tiles_per_q_chunk;
-  const int qt_order = bid % n_q_tiles;
-  const int b = bid / n_q_tiles;
+  const int n_launched = p.win_n ? p.win_n : n_q_tiles;          // windowed launch: only the listed tiles have workgroups
+  const int qt_order = p.win_n ? p.win_qt[bid % n_launched] : bid % n_launched;
+  const int b = bid / n_launched;
   const int head = kvh * G + hq;
   const int qc = p.q_order[qt_order / p.tiles_per_q_chunk];
   const int qti = p.tiles_per_q_chunk - 1 - qt_order % p.tiles_per_q_chunk;

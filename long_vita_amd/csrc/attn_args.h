@@ -4,6 +4,7 @@
 #include "vita_common.h"
 
 constexpr int kMaxChunks = 32;
+constexpr int kMaxWindowTiles = 32;      // query tiles one windowed launch may name (vita_flash_attn_fwd_window)
 
 struct AttnArgs {
   const bf16_t* q; int64_t q_bs, q_rs, q_hs, q_gs;   // q_gs: stride between kv groups' first query head
@@ -22,6 +23,10 @@ struct AttnArgs {
   int q_gid[kMaxChunks];
   int kv_gid[kMaxChunks];
   int64_t kv_row[kMaxChunks];
+  // windowed launch: the grid holds only win_n query tiles per (batch, head); win_qt[i] is the position the full launch's heaviest-first
+  // order gives tile i, so a workgroup decodes to exactly the workgroup the full launch runs there.  win_n == 0: every tile (the full launch)
+  int win_n;
+  int win_qt[kMaxWindowTiles];
 };
 
 // attn64.hip: true when the geometry qualifies (head_dim 128, causal, no packed segments, chunk_len % 256 == 0, whole chunks)

@@ -960,11 +960,13 @@ int launch_gemm_cfg(GemmArgs a, hipStream_t st) {
   return vita_check_launch();
 }
 
+// m_select: the row count the kernel is CHOSEN for (a.M for an ordinary call; vita_gemm_bf16_select: the M of the full call whose rows
+// these are, so that they pass through the same kernel — the same accumulation order — as they do there)
 template <int EPI>
-int launch_gemm(const GemmArgs& a, hipStream_t st) {
+int launch_gemm(const GemmArgs& a, int64_t m_select, hipStream_t st) {
   // the 256x256 tile needs enough tiles to fill 256 CUs with one workgroup each
   const int64_t bn_out = EPI == VITA_EPI_SWIGLU ? 128 : 256;
-  const int64_t big_tiles = ((a.M + 255) / 256) * ((a.N + bn_out - 1) / bn_out);
+  const int64_t big_tiles = ((m_select + 255) / 256) * ((a.N + bn_out - 1) / bn_out);
   const bool big = big_tiles >= 192;
   // VITA_GEMM_KERNEL (developer aid, read per launch): "w4" / "w8" force the large-problem kernel, "128" the small tile
   const char* kn = vita_dev_getenv("VITA_GEMM_KERNEL");
@@ -982,10 +984,8 @@ int launch_gemm(const GemmArgs& a, hipStream_t st) {
 
 }  // namespace
 
-extern "C" int vita_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C,
-                              int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
-                              const void* bias, const void* scale, const void* R, int64_t ldr,
-                              void* stream) {
+static int gemm_bf16_impl(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K,
+                          int epilogue, const void* bias, const void* scale, const void* R, int64_t ldr, int64_t m_select, void* stream) {
   if (!A || !W || !C || M < 0 || N <= 0 || K <= 0) return VITA_ERR_INVALID_ARG;
   if (K % BK) return VITA_ERR_UNSUPPORTED;
   if ((lda & 7) || (ldw & 7) || (ldc & 3)) return VITA_ERR_UNSUPPORTED;
@@ -1001,29 +1001,44 @@ extern "C" int vita_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t
   }
   hipStream_t st = (hipStream_t)stream;
   switch (epilogue) {
-    case VITA_EPI_NONE: return launch_gemm<VITA_EPI_NONE>(a, st);
+    case VITA_EPI_NONE: return launch_gemm<VITA_EPI_NONE>(a, m_select, st);
     case VITA_EPI_BIAS:
       if (!bias) return VITA_ERR_INVALID_ARG;
-      return launch_gemm<VITA_EPI_BIAS>(a, st);
-    case VITA_EPI_BIAS_GELU: return launch_gemm<VITA_EPI_BIAS_GELU>(a, st);
+      return launch_gemm<VITA_EPI_BIAS>(a, m_select, st);
+    case VITA_EPI_BIAS_GELU: return launch_gemm<VITA_EPI_BIAS_GELU>(a, m_select, st);
     case VITA_EPI_RESIDUAL:
       if (!R || (ldr & 3)) return VITA_ERR_INVALID_ARG;
-      return launch_gemm<VITA_EPI_RESIDUAL>(a, st);
+      return launch_gemm<VITA_EPI_RESIDUAL>(a, m_select, st);
     case VITA_EPI_BIAS_SCALE_RES:
       if (!R || !scale || (ldr & 3)) return VITA_ERR_INVALID_ARG;
-      return launch_gemm<VITA_EPI_BIAS_SCALE_RES>(a, st);
-    case VITA_EPI_SWIGLU: return launch_gemm<VITA_EPI_SWIGLU>(a, st);
+      return launch_gemm<VITA_EPI_BIAS_SCALE_RES>(a, m_select, st);
+    case VITA_EPI_SWIGLU: return launch_gemm<VITA_EPI_SWIGLU>(a, m_select, st);
     case VITA_EPI_BIAS2_GELU_TANH:
       if (!bias) return VITA_ERR_INVALID_ARG;
-      return launch_gemm<VITA_EPI_BIAS2_GELU_TANH>(a, st);
+      return launch_gemm<VITA_EPI_BIAS2_GELU_TANH>(a, m_select, st);
     case VITA_EPI_BIAS2_RES:
       if (!bias || !R || (ldr & 3)) return VITA_ERR_INVALID_ARG;
-      return launch_gemm<VITA_EPI_BIAS2_RES>(a, st);
+      return launch_gemm<VITA_EPI_BIAS2_RES>(a, m_select, st);
     case VITA_EPI_BIAS2_GELU:
       if (!bias) return VITA_ERR_INVALID_ARG;
-      return launch_gemm<VITA_EPI_BIAS2_GELU>(a, st);
+      return launch_gemm<VITA_EPI_BIAS2_GELU>(a, m_select, st);
     default: return VITA_ERR_INVALID_ARG;
   }
+}
+
+extern "C" int vita_gemm_bf16(const void* A, int64_t lda, const void* W, int64_t ldw, void* C,
+                              int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue,
+                              const void* bias, const void* scale, const void* R, int64_t ldr,
+                              void* stream) {
+  return gemm_bf16_impl(A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, scale, R, ldr, M, stream);
+}
+
+// M rows taken out of a call over M_select >= M rows: the kernel is chosen as for M_select rows (launch_gemm), the grid covers M rows
+extern "C" int vita_gemm_bf16_select(const void* A, int64_t lda, const void* W, int64_t ldw, void* C, int64_t ldc, int64_t M, int64_t N,
+                                     int64_t K, int epilogue, const void* bias, const void* scale, const void* R, int64_t ldr,
+                                     int64_t M_select, void* stream) {
+  if (M_select < M) return VITA_ERR_INVALID_ARG;
+  return gemm_bf16_impl(A, lda, W, ldw, C, ldc, M, N, K, epilogue, bias, scale, R, ldr, M_select, stream);
 }
 
 // C[M, N] = A_t^T W_t with both operands contraction-major (A_t [K, M], W_t [K, N]): the weight-gradient GEMM without transposes

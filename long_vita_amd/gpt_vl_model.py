@@ -71,6 +71,9 @@ class GPTVLModel:
         # cached calls that feed at least this many tokens (CP = 1, TP = 1) run ONE pass through the prefill layers with
         # ops.flash_attn_extend instead of one decode step per token (where the default comes from)
         self.extend_min_tokens = int(os.environ.get("VITA_EXTEND_MIN_TOKENS", str(EXTEND_MIN_TOKENS)))
+        # a prefill with a logit mask (CP = 1, TP = 1) runs the per-row tail of the LAST layer — attention, o-projection, MLP — only for
+        # the rows the mask keeps; 0 runs the full layer (tests, A / B)
+        self.trim_last_layer = bool(int(os.environ.get("VITA_TRIM_LAST_LAYER", "1")))
 
     # ---------------------------------------------------------------------------------------------
     @classmethod
@@ -119,11 +122,15 @@ class GPTVLModel:
         return ws
 
     def decoder_layer(self, h: torch.Tensor, lp: dict, cos, sin, ws, kv_dst: Optional[torch.Tensor] = None,
-                      cached_rows: Optional[int] = None) -> torch.Tensor:
+                      cached_rows: Optional[int] = None, keep: Optional[tuple] = None) -> torch.Tensor:
         """h [s, hidden] updated in place.  kv_dst [2, cap, groups, d]: this rank's cache shard for the
         layer; the rotated K and V rows of the local sequence are stored into rows [0, s).
         cached_rows = L (CP = 1): the s rows are NEW tokens behind L rows the shard already holds — their K / V go to rows
-        [L, L + s) and the attention runs over the L + s cache rows (ops.flash_attn_extend); everything else is the same layer."""
+        [L, L + s) and the attention runs over the L + s cache rows (ops.flash_attn_extend); everything else is the same layer.
+        keep = (idx int64 [n] on the device, [256-row query tiles that hold them]) on the LAST layer of a masked prefill (CP = 1,
+        TP = 1): K / V of every row are computed and cached as ever, attention runs for those tiles only and the per-row rest of the
+        layer for the n kept rows only, each with the arithmetic of the full layer; returns those rows [n, hidden] (h is left as the
+        layer found it).  A geometry whose attention takes no window runs the full layer and returns h."""
         c = self.cfg
         s = h.shape[0]
         cp = mpu.get_context_parallel_world_size()
@@ -140,6 +147,10 @@ class GPTVLModel:
             else:
                 kv_dst[0, row0: row0 + s].copy_(m5[0, :, :, c.qpg])
                 kv_dst[1, row0: row0 + s].copy_(m5[0, :, :, c.qpg + 1])
+        if keep is not None and not use_cp and cached_rows is None and training_utils.get_packed_segments() is None:
+            # no event pair: attn_events times full launches (bench.py's roofline divides a full layer's flops by their mean)
+            if ops.flash_attn(q5, m5[:, :, :, c.qpg], m5[:, :, :, c.qpg + 1], causal=True, out=ws["ctx"], q_tiles=keep[1]) is not None:
+                return self._layer_tail_rows(h, lp, ws, keep[0])
         ev = None
         if self.attn_events is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
@@ -174,6 +185,18 @@ class GPTVLModel:
         else:
             self._row_parallel(act, lp["fc2_w"], h, ws["x"])
         return h
+
+    def _layer_tail_rows(self, h: torch.Tensor, lp: dict, ws, idx: torch.Tensor) -> torch.Tensor:
+        """Everything of a layer behind its attention, for rows idx alone: o-projection + residual, RMSNorm, fc1 + SwiGLU, fc2 +
+        residual are per-row.  The GEMMs pick their kernel as for all s rows (select_rows), so each row has the full layer's bits."""
+        c = self.cfg
+        s = h.shape[0]
+        ctx = ops.row_gather(ws["ctx"].view(s, c.heads * c.head_dim), idx, check_bounds=False)      # idx comes from a mask over the s rows
+        rows = ops.row_gather(h, idx, check_bounds=False)
+        ops.gemm(ctx, lp["o_w"], ops.EPI_RESIDUAL, residual=rows, out=rows, select_rows=s)
+        x = ops.rmsnorm(rows, lp["ln2"], c.eps)
+        act = ops.gemm(x, lp["fc1_w"], ops.EPI_SWIGLU, select_rows=s)
+        return ops.gemm(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=rows, out=rows, select_rows=s)
 
     @staticmethod
     def _row_parallel(x: torch.Tensor, w: torch.Tensor, h: torch.Tensor, scratch: torch.Tensor) -> torch.Tensor:
@@ -223,16 +246,28 @@ class GPTVLModel:
         ws = self._workspace(s, h.device)
         if ip is not None:
             self._allocate_cache(ip, s, h.device)
+        # the kept rows are resolved HERE: the mask is an input, so the host read waits for nothing, and the last layer needs them on
+        # the host (a read in front of that layer would drain the queue of the layers before it)
+        idx = keep = None
+        if logit_mask is not None:
+            idx = ops.mask_to_index(logit_mask.transpose(0, 1).reshape(-1))
+            if (self.trim_last_layer and idx.numel() > 0 and not self.force_cp_path and mpu.get_context_parallel_world_size() == 1
+                    and mpu.get_tensor_model_parallel_world_size() == 1):
+                tiles = sorted({r // 256 for r in idx.tolist()})
+                if len(tiles) <= 32:                     # what one windowed attention launch names; more kept tiles: the full layer
+                    keep = (idx, tiles)
+        last = len(self.p["layers"]) - 1
+        out = h
         for li, lp in enumerate(self.p["layers"]):                                        # self.decoder(...) :299
             with tracing.range(f"prefill: layer {li}"):
-                self.decoder_layer(h, lp, cos, sin, ws, None if ip is None else ip.key_value_memory_dict[li + 1])
+                out = self.decoder_layer(h, lp, cos, sin, ws, None if ip is None else ip.key_value_memory_dict[li + 1],
+                                         keep=keep if li == last else None)
         if ip is not None:
             self._compact_cache(ip, s)
         tracing.push("prefill: final norm + masked head")
         # final RMSNorm is per-row, so norm only the rows the masked head keeps
         if logit_mask is not None:
-            idx = ops.mask_to_index(logit_mask.transpose(0, 1).reshape(-1))
-            rows = ops.row_gather(h, idx)
+            rows = out if out is not h else ops.row_gather(h, idx)       # the trimmed last layer hands back the kept rows themselves
             sel_mask = None
         else:
             rows, sel_mask = h, None

@@ -161,6 +161,7 @@ PROTOTYPES = {
     "vita_index_inverse": (_i, [_p, _l, _p, _p]),
     "vita_cp_src_tgt": (_i, [_p, _l, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
     "vita_gemm_bf16": (_i, [_p, _l, _p, _l, _p, _l, _l, _l, _l, _i, _p, _p, _p, _l, _p]),
+    "vita_gemm_bf16_select": (_i, [_p, _l, _p, _l, _p, _l, _l, _l, _l, _i, _p, _p, _p, _l, _l, _p]),
     "vita_gemm_bf16_tn": (_i, [_p, _l, _p, _l, _p, _l, _l, _l, _l, _p]),
     "vita_gemm_bf16_nn": (_i, [_p, _l, _p, _l, _p, _l, _l, _l, _l, _p]),
     "vita_gemm_tn_splitk_workspace_bytes": (C.c_size_t, [_l, _l, _i]),
@@ -170,6 +171,7 @@ PROTOTYPES = {
     "vita_colsum_bf16_ordered": (_i, [_p, _l, _p, _l, _i, _p, _p]),
     "vita_gemm_skinny_bf16": (_i, [_p, _l, _p, _l, _p, _l, _i, _l, _l, _i, _p]),
     "vita_flash_attn_fwd": (_i, [C.POINTER(AttnParams), _p]),
+    "vita_flash_attn_fwd_window": (_i, [C.POINTER(AttnParams), C.POINTER(C.c_int32), _i, _p]),
     "vita_flash_attn_extend_workspace_bytes": (C.c_size_t, [_l, _i, _l]),
     "vita_flash_attn_extend_fwd": (_i, [C.POINTER(AttnExtendParams), _p]),
     "vita_patchify14": (_i, [_p, _p, _l, _i, _i, _i, _p]),

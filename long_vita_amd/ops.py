@@ -304,9 +304,11 @@ def cp_src_tgt(hit_idx, tok_per_img, img_rank, indices_b, local_pos):
 # ------------------------------------------------------------------------------------------------
 def gemm(a: torch.Tensor, w: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
          scale: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None,
-         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+         out: Optional[torch.Tensor] = None, select_rows: Optional[int] = None) -> torch.Tensor:
     """out[M, N] = epilogue(a[M, K] @ w[N(or 2N), K]^T) — see VITA_EPI_* in include/vita_hip.h.
-    `a` may have a row stride (a.stride(0) >= K); w is [rows, K] contiguous like nn.Linear.weight."""
+    `a` may have a row stride (a.stride(0) >= K); w is [rows, K] contiguous like nn.Linear.weight.
+    select_rows = S >= M: the M rows are rows taken out of a call over S rows and come out with the bits that call gives them
+    (vita_gemm_bf16_select: the kernel is chosen as for S rows)."""
     if a.dim() != 2 or w.dim() != 2 or a.stride(1) != 1 or w.stride(1) != 1:
         raise ValueError("a and w must be 2-D with contiguous last dim")
     M, K = a.shape
@@ -331,9 +333,14 @@ def gemm(a: torch.Tensor, w: torch.Tensor, epilogue: int = EPI_NONE, bias: Optio
         if residual.shape != (M, N) or residual.stride(1) != 1:
             raise ValueError("residual has wrong shape")
         r_ptr, ldr = _dev(residual, "residual", BF16), residual.stride(0)
-    _L.check(_L.load().vita_gemm_bf16(_dev(a, "a", BF16), a.stride(0), _dev(w, "w", BF16), w.stride(0),
-                                      _dev(y, "out", BF16), y.stride(0), M, N, K, epilogue, _opt(bias, "bias", BF16),
-                                      _opt(scale, "scale", BF16), r_ptr, ldr, _stream()), "vita_gemm_bf16")
+    args = (_dev(a, "a", BF16), a.stride(0), _dev(w, "w", BF16), w.stride(0), _dev(y, "out", BF16), y.stride(0), M, N, K, epilogue,
+            _opt(bias, "bias", BF16), _opt(scale, "scale", BF16), r_ptr, ldr)
+    if select_rows is None:
+        _L.check(_L.load().vita_gemm_bf16(*args, _stream()), "vita_gemm_bf16")
+    else:
+        if select_rows < M:
+            raise ValueError("select_rows is the row count of the full call: at least M")
+        _L.check(_L.load().vita_gemm_bf16_select(*args, int(select_rows), _stream()), "vita_gemm_bf16_select")
     return y
 
 
@@ -494,9 +501,11 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: boo
                chunk_len: Optional[int] = None, q_chunk_gid: Optional[Sequence[int]] = None,
                kv_chunk_gid: Optional[Sequence[int]] = None, kv_chunk_row: Optional[Sequence[int]] = None,
                out: Optional[torch.Tensor] = None, return_lse: bool = False, seg_start: Optional[torch.Tensor] = None,
-               lse_out: Optional[torch.Tensor] = None):
+               lse_out: Optional[torch.Tensor] = None, q_tiles: Optional[Sequence[int]] = None):
     """q [B, Sq, Hq, D] or grouped [B, Sq, Hkv, G, D]; k/v [B, Sk, Hkv, D] — *views* (any batch / row /
     head / group stride, D contiguous).  Returns o [B, Sq, Hq, D] (contiguous unless `out` given).
+    q_tiles: only these 256-row query tiles are computed (vita_flash_attn_fwd_window: plain causal, one chunk, d = 128); the other
+    rows of o / lse are left as they were.  Returns None when the geometry takes no window (nothing was launched).
 
     Chunk geometry (zig-zag context parallelism): Sq = len(q_chunk_gid) * chunk_len local rows,
     kv chunk j starts at row kv_chunk_row[j] of k/v.  Defaults: one chunk, gid 0.
@@ -537,7 +546,14 @@ def flash_attn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, *, causal: boo
     p.softmax_scale = float(softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D))
     if seg_start is not None:           # packed sequences: int32 [rows], first row of each query row's segment
         p.q_seg_start = _dev(seg_start, "seg_start", torch.int32)
-    _L.check(_L.load().vita_flash_attn_fwd(C.byref(p), _stream()), "vita_flash_attn_fwd")
+    if q_tiles is not None:
+        tiles = (C.c_int32 * len(q_tiles))(*q_tiles)
+        rc = _L.load().vita_flash_attn_fwd_window(C.byref(p), tiles, len(q_tiles), _stream())
+        if rc == _L.VITA_ERR_UNSUPPORTED:
+            return None
+        _L.check(rc, "vita_flash_attn_fwd_window")
+    else:
+        _L.check(_L.load().vita_flash_attn_fwd(C.byref(p), _stream()), "vita_flash_attn_fwd")
     return (o, lse) if return_lse else o
 
 
