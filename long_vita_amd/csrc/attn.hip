@@ -34,37 +34,7 @@ __device__ unsigned long long g_attn_timing[16];
 constexpr int QTILE = 256;   // query rows per workgroup (8 waves x 32)
 constexpr int KVT = 64;      // keys per tile
 
-__device__ __forceinline__ float swap32_max(float x) {
-  const unsigned xi = __float_as_uint(x);
-  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float swap32_sum(float x) {
-  const unsigned xi = __float_as_uint(x);
-  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
-// LDS byte offset of K element block (row, 16-byte slot) ; row = key within tile
-template <int D>
-__device__ __forceinline__ int k_lds_off(int row, int slot) {
-  if (D == 128) return row * 256 + ((slot ^ (row & 15)) << 4);
-  else if (D == 96) return row * 192 + (((slot + ((row >> 2) & 3)) % 12) << 4);    // see the note on d = 96 below
-  else return row * 128 + ((slot ^ ((row >> 1) & 7)) << 4);
-}
-// d = 96 (r05: SigLIP's head size 72 zero-padded to 96 instead of 128): a row is 192 bytes = 12 slots = 3/4 of a bank period, so an XOR
-// swizzle does not fit.  K fragments (ds_read_b128, 16 consecutive rows per pass): 16-byte unit = (12 row + pslot) mod 16 with pslot =
-// (slot + (row >> 2 & 3)) mod 12 is a permutation of 0 .. 15 over 16 consecutive rows (12 = -4 mod 16: rows r, r + 1, r + 2, r + 3 start
-// 0, 12, 8, 4 units in; the +0 .. 3 rotation of rows r + 4 k fills each group of four; a wrap mod 12 moves a whole group by +4).
-// V^T fragments (ds_read_b64_tr_b16, 4 rows x 64 bytes per 32-lane pass): 192 = -64 mod 256, so rows r .. r + 3 already sit in four
-// different 64-byte windows of the bank period: no swizzle at all.
-// LDS byte offset of V (row, 32-byte chunk c, byte b within chunk)
-template <int D>
-__device__ __forceinline__ int v_lds_off(int row, int chunk, int b) {
-  if (D == 128) return row * 256 + ((chunk ^ ((row & 3) << 1)) << 5) + b;
-  else if (D == 96) return row * 192 + (chunk << 5) + b;
-  else return row * 128 + ((chunk ^ (row & 2)) << 5) + b;
-}
+// K tiles use attn_tile.h's frag layout (row = key within tile), V tiles its tr layout.
 
 // One kv tile position of the iteration space (all fields wave-uniform -> SGPRs).
 struct TileIt {
@@ -99,10 +69,6 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
   constexpr int QK_AHEAD = (VARIANT >> 1) & 3;          // 0 = compiler's own schedule
 
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K tile | V tile]
-  typedef __attribute__((address_space(3))) char lds_char;
-  typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-  typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
   // LDS byte address of the ring (32-bit); fragment reads use  VGPR(lane offset + slot base) + imm
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
 
@@ -111,17 +77,8 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
   const int hi = lane >> 5, l31 = lane & 31;
 
   // ---- work decomposition -------------------------------------------------------------------
-  const int G = p.n_q_heads / p.n_kv_heads;
-  int bid = blockIdx.x;
-  const int kvh = bid % p.n_kv_heads; bid /= p.n_kv_heads;
-  const int hq = bid % G; bid /= G;
-  const int n_q_tiles = p.n_q_chunks * p.tiles_per_q_chunk;
-  const int n_launched = p.win_n ? p.win_n : n_q_tiles;          // windowed launch: only the listed tiles have workgroups
-  const int qt_order = p.win_n ? p.win_qt[bid % n_launched] : bid % n_launched;
-  const int b = bid / n_launched;
-  const int head = kvh * G + hq;
-  const int qc = p.q_order[qt_order / p.tiles_per_q_chunk];
-  const int qti = p.tiles_per_q_chunk - 1 - qt_order % p.tiles_per_q_chunk;
+  const QTileId wg = decode_q_tile(p, blockIdx.x, p.tiles_per_q_chunk);
+  const int kvh = wg.kvh, hq = wg.hq, head = wg.head, b = wg.b, qc = wg.qc, qti = wg.qti;
   const int gq = p.q_gid[qc];
   const int q_rows_in_chunk = (qc == p.n_q_chunks - 1) ? p.q_valid : p.chunk_len;
   const int q_off_wg = qti * QTILE;                 // offset of this tile inside its chunk
@@ -150,18 +107,15 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
   // K fragment (A operand): row l31 (+32), 16-byte slot 2*ds + hi
   unsigned koff[DS];
 #pragma unroll
-  for (int ds = 0; ds < DS; ++ds) koff[ds] = k_lds_off<D>(l31, 2 * ds + hi);
+  for (int ds = 0; ds < DS; ++ds) koff[ds] = frag_off<D>(l31, 2 * ds + hi);
   // V^T fragment for O^T row block db: inside a 16-lane group, lane i supplies the 8-byte piece
   // (row i>>2, columns 4*(i&3)..) of a [4 keys][16 d] block; keys 16t + 4*hi' + {0..3} (+8)
   unsigned voff[DB];
-  {
-    const int g16 = lane >> 4, i16 = lane & 15;
-    const int key_l = 4 * (g16 >> 1) + (i16 >> 2);
+  const int key_l = tr_lane_row(lane);
 #pragma unroll
-    for (int db = 0; db < DB; ++db) {
-      const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
-      voff[db] = TILEB + v_lds_off<D>(key_l, col >> 4, (col & 15) * 2);
-    }
+  for (int db = 0; db < DB; ++db) {
+    const int col = tr_lane_col(lane, db);
+    voff[db] = TILEB + tr_off<D>(key_l, col >> 4, (col & 15) * 2);
   }
   // staging: this thread's LD_PER_THR 16-byte pieces of a tile -> global element offsets
   // (relative to the tile's first row, 32-bit) and LDS byte offsets (relative to the slot)
@@ -172,8 +126,8 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
     const int row = e / SLOTS, slot = e % SLOTS;
     g_koff[it] = (unsigned)(row * p.k_rs + slot * 8);
     g_voff[it] = (unsigned)(row * p.v_rs + slot * 8);
-    l_koff[it] = k_lds_off<D>(row, slot);
-    l_voff[it] = TILEB + v_lds_off<D>(row, slot >> 1, (slot & 1) << 4);
+    l_koff[it] = frag_off<D>(row, slot);
+    l_voff[it] = TILEB + tr_off<D>(row, slot >> 1, (slot & 1) << 4);
   }
 
   f32x16 o_acc[DB];
@@ -210,8 +164,6 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
   constexpr int PIECES = D96 ? 3 : TILEB / 1024 / 8;   // wave-instructions per operand per wave (d = 96: per wave, of ITS operand)
   constexpr int RPP = 1024 / ROWB;                      // tile rows per 1-KiB piece (d = 96: unused)
   const bool v_wave = D96 && wave >= 4;
-  typedef __attribute__((address_space(1))) const void gvoid;
-  typedef __attribute__((address_space(3))) void lvoid;
   unsigned dk_off[PIECES], dv_off[PIECES];             // per-lane source offsets (elements) inside a tile
   int d_row[PIECES], d_ks[PIECES], d_vs[PIECES];
 #pragma unroll
@@ -220,10 +172,8 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
     const int row = D96 ? unit / SLOTS : (wave * PIECES + q) * RPP + lane / SLOTS;   // tile row this lane fills
     const int ps = D96 ? unit % SLOTS : lane % SLOTS;           // physical 16-byte slot in the row
     // logical slot whose data must land at physical slot ps (inverse of the read swizzles)
-    d_ks[q] = (D == 128) ? (ps ^ (row & 15)) : D96 ? (ps + 12 - ((row >> 2) & 3)) % 12 : (ps ^ ((row >> 1) & 7));
-    d_vs[q] = (D == 128) ? ((((ps >> 1) ^ ((row & 3) << 1)) << 1) | (ps & 1))
-              : D96      ? ps
-                         : ((((ps >> 1) ^ (row & 2)) << 1) | (ps & 1));
+    d_ks[q] = frag_slot_inv<D>(row, ps);
+    d_vs[q] = tr_slot_inv<D>(row, ps);
     d_row[q] = row;
     dk_off[q] = (unsigned)(row * p.k_rs + d_ks[q] * 8);
     dv_off[q] = (unsigned)(row * p.v_rs + d_vs[q] * 8);
@@ -555,27 +505,27 @@ static int flash_attn_fwd_impl(const vita_attn_params* p, const int32_t* win_til
 
   AttnArgs a;
   a.q = (const bf16_t*)p->q; a.q_bs = p->q_batch_stride; a.q_rs = p->q_row_stride; a.q_hs = p->q_head_stride;
-  a.q_gs = p->q_group_stride ? p->q_group_stride : p->q_head_stride * (p->n_q_heads / p->n_kv_heads);
+  a.q_gs = vita_group_stride(p->q_group_stride, p->q_head_stride, p->n_q_heads / p->n_kv_heads);
   a.k = (const bf16_t*)p->k; a.k_bs = p->k_batch_stride; a.k_rs = p->k_row_stride; a.k_hs = p->k_head_stride;
   a.v = (const bf16_t*)p->v; a.v_bs = p->v_batch_stride; a.v_rs = p->v_row_stride; a.v_hs = p->v_head_stride;
   a.o = (bf16_t*)p->o; a.o_bs = p->o_batch_stride; a.o_rs = p->o_row_stride; a.o_hs = p->o_head_stride;
-  a.o_gs = p->o_group_stride ? p->o_group_stride : p->o_head_stride * (p->n_q_heads / p->n_kv_heads);
+  a.o_gs = vita_group_stride(p->o_group_stride, p->o_head_stride, p->n_q_heads / p->n_kv_heads);
   a.lse = p->lse;
   a.batch = p->batch; a.n_q_heads = p->n_q_heads; a.n_kv_heads = p->n_kv_heads;
   a.chunk_len = (int)p->chunk_len; a.q_valid = (int)p->q_valid; a.kv_valid = (int)p->kv_valid;
   a.n_q_chunks = p->n_q_chunks; a.n_kv_chunks = p->n_kv_chunks;
   a.tiles_per_q_chunk = (int)((p->chunk_len + QTILE - 1) / QTILE);
   a.n_q_rows = (int)((int64_t)(p->n_q_chunks - 1) * p->chunk_len + p->q_valid);
-  a.scale_log2e = p->softmax_scale * 1.44269504088896340736f;
+  a.scale_log2e = p->softmax_scale * LOG2E;
   a.seg_start = p->q_seg_start;
   if (p->q_seg_start && (p->n_q_chunks != 1 || p->n_kv_chunks != 1 || !p->causal || p->batch != 1)) return VITA_ERR_UNSUPPORTED;
-  for (int i = 0; i < p->n_q_chunks; ++i) { a.q_gid[i] = p->q_chunk_gid[i]; a.q_order[i] = i; }
+  vita_copy_chunk_tables(a, p);
+  for (int i = 0; i < p->n_q_chunks; ++i) a.q_order[i] = i;
   // heaviest (largest global chunk id) first
   for (int i = 1; i < p->n_q_chunks; ++i)
     for (int j = i; j > 0 && a.q_gid[a.q_order[j]] > a.q_gid[a.q_order[j - 1]]; --j) {
       const int t = a.q_order[j]; a.q_order[j] = a.q_order[j - 1]; a.q_order[j - 1] = t;
     }
-  for (int i = 0; i < p->n_kv_chunks; ++i) { a.kv_gid[i] = p->kv_chunk_gid[i]; a.kv_row[i] = p->kv_chunk_row[i]; }
   int64_t nblocks = (int64_t)p->batch * p->n_q_heads * p->n_q_chunks * a.tiles_per_q_chunk;
   if (nblocks > 0x7fffffff) return VITA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;

@@ -19,7 +19,7 @@
 //     the 400-instruction accumulator rescale (AGPR -> VGPR -> AGPR) leaves the steady state.  With exact maxima a 64-row
 //     wave hits it on ~20 % of the tiles of a 128K row (measured: 0.74 -> 0.90 PFLOP/s at 16K, 1.11 -> 1.19 at 128K)
 //   * K / V tiles HBM/L2 -> LDS by LDS-DMA (buffer_load ... lds: SGPR descriptor re-based per tile + the lane's 32-bit offset,
-//     no address VALU), separate K and V rings of two 16 KiB slots, one barrier per tile; attn.hip's swizzled layouts
+//     no address VALU), separate K and V rings of two 16 KiB slots, one barrier per tile; attn_tile.h's frag / tr layouts
 //     (conflict-free ds_read_b128 / ds_read_b64_tr_b16), the swizzle applied to the DMA's per-lane SOURCE address
 //   * masks: a tile of the diagonal chunk that reaches past the workgroup's first row is masked element-wise for every wave
 //     (tiles wholly past a wave's rows come out as exp2(-inf) = 0: no per-wave control flow in the pipeline)
@@ -34,22 +34,6 @@ constexpr int D = 128, KVT = 64, QTILE = 256, ROWB = D * 2, TILEB = KVT * ROWB; 
 constexpr int LDS_K = 0, LDS_V = 2 * TILEB;                                         // K ring [2] | V ring [2]
 constexpr int NF2 = 3;                                                               // P fragments of tile t+1 done in phase 2
 constexpr int THR = 8;                                                               // lazy running maximum, log2 units
-
-typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) void lvoid;
-
-__device__ __forceinline__ float swap32_max(float x) {
-  const unsigned xi = __float_as_uint(x);
-  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float swap32_sum(float x) {
-  const unsigned xi = __float_as_uint(x);
-  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
 
 // ---- filler schedule: units dealt to the 32 MFMA slots of a phase by cumulative weight ---------------------------------
 // phase 2 units: 0..31 max3 steps (weight 1), 32..33 running-maximum decision (weight 6), then 8 * NF2 exp half-units
@@ -77,14 +61,6 @@ constexpr SlotMap make_map1() {
   return m;
 }
 
-// One kv tile position of the iteration space (all fields wave-uniform -> SGPRs); c == n_kv_chunks: end.
-struct TileIt {
-  int c, j, n;        // chunk, tile inside chunk, tiles to visit in this chunk
-  int diag;           // chunk c is the query tile's own chunk
-  const char* kp;     // first K / V row of the tile (running pointers: one 64-bit add per tile, no multiplies in the loop)
-  const char* vp;
-};
-
 // One barrier per tile (rings of two slots).  (Rings of four slots, TWO tiles between barriers and the DMAs of tiles t+2 .. t+4 issued
 // at the start of a pair, were measured in r03 and r06: no gain.)
 // PACKED (r03): packed samples (p.seg_start: first key row of each query row's segment, non-decreasing; one chunk).  The workgroup
@@ -98,18 +74,9 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  // ---- work decomposition (attn.hip's: kv head = block id % n_kv_heads = the XCD for 8 kv heads; heaviest query tiles first) ----
-  const int G = p.n_q_heads / p.n_kv_heads;
-  int bid = blockIdx.x;
-  const int kvh = bid % p.n_kv_heads; bid /= p.n_kv_heads;
-  const int hq = bid % G; bid /= G;
-  const int n_q_tiles = p.n_q_chunks * p.tiles_per_q_chunk;
-  const int n_launched = p.win_n ? p.win_n : n_q_tiles;          // windowed launch: only the listed tiles have workgroups
-  const int qt_order = p.win_n ? p.win_qt[bid % n_launched] : bid % n_launched;
-  const int b = bid / n_launched;
-  const int head = kvh * G + hq;
-  const int qc = p.q_order[qt_order / p.tiles_per_q_chunk];
-  const int qti = p.tiles_per_q_chunk - 1 - qt_order % p.tiles_per_q_chunk;
+  // ---- work decomposition (decode_q_tile: kv head = block id % n_kv_heads = the XCD for 8 kv heads; heaviest query tiles first) ----
+  const QTileId wg = decode_q_tile(p, blockIdx.x, p.tiles_per_q_chunk);
+  const int kvh = wg.kvh, hq = wg.hq, head = wg.head, b = wg.b, qc = wg.qc, qti = wg.qti;
   const int gq = p.q_gid[qc];
   const int q_off_wg = qti * QTILE;                 // offset of this workgroup inside its chunk
   const int q_off = q_off_wg + wave * 64;           // this wave's first row inside the chunk
@@ -138,31 +105,28 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
 #pragma unroll
     for (int ds = 0; ds < 8; ++ds) asm volatile("" : "+a"(qf[qb][ds]));      // live in AGPRs from here on
 
-  // ---- LDS fragment offsets (attn.hip's layouts) ----------------------------------------------------------------------------
+  // ---- LDS fragment offsets (attn_tile.h: K frag layout, V tr layout) ---------------------------------------------------------
   unsigned koff[8], voff[4];
 #pragma unroll
-  for (int ds = 0; ds < 8; ++ds) koff[ds] = l31 * ROWB + (((2 * ds + hi) ^ (l31 & 15)) << 4);       // + 32 kb rows: immediate
-  {
-    const int g16 = lane >> 4, i16 = lane & 15, key_l = 4 * (g16 >> 1) + (i16 >> 2);
+  for (int ds = 0; ds < 8; ++ds) koff[ds] = frag_off<D>(l31, 2 * ds + hi);       // + 32 kb rows: immediate
+  const int key_l = tr_lane_row(lane);
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
-      voff[db] = key_l * ROWB + (((col >> 4) ^ ((key_l & 3) << 1)) << 5) + (col & 15) * 2;
-    }
+  for (int db = 0; db < 4; ++db) {
+    const int col = tr_lane_col(lane, db);
+    voff[db] = tr_off<D>(key_l, col >> 4, (col & 15) * 2);
   }
   // ---- LDS-DMA: wave w moves pieces 4w .. 4w+3 (1 KiB = 4 rows) of K and of V; swizzle on the SOURCE address ---------------
   unsigned dk_off[4], dv_off[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int row = (wave * 4 + q) * 4 + (lane >> 4), ps = lane & 15;
-    const int ks = ps ^ (row & 15);
-    const int vs = (((ps >> 1) ^ ((row & 3) << 1)) << 1) | (ps & 1);
+    const int ks = frag_slot_inv<D>(row, ps);
+    const int vs = tr_slot_inv<D>(row, ps);
     dk_off[q] = (unsigned)((row * p.k_rs + ks * 8) * 2);     // bytes inside the tile (64 rows x row stride < 2^32)
     dv_off[q] = (unsigned)((row * p.v_rs + vs * 8) * 2);
   }
   const char* kbase = (const char*)(p.k + (int64_t)b * p.k_bs + (int64_t)kvh * p.k_hs);
   const char* vbase = (const char*)(p.v + (int64_t)b * p.v_bs + (int64_t)kvh * p.v_hs);
-  const int k_tile_bytes = (int)(p.k_rs * 2 * KVT), v_tile_bytes = (int)(p.v_rs * 2 * KVT);
   // LDS address of this wave's first piece in K / V ring slot 0.  The descriptor is re-based on the tile's first row: no
   // 4 GiB limit on the K / V buffers, no address VALU.  `opaque` keeps the 16 piece addresses from being hoisted into 16 SGPRs.
   const unsigned lds_kw = lds0 + LDS_K + wave * 4096, lds_vw = lds0 + LDS_V + wave * 4096;
@@ -194,34 +158,9 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
     vita_lds_dma16(r, off[q], base + slot * TILEB + q * 1024);
   };
 
-  // ---- tile iterator -----------------------------------------------------------------------------------------------------------
-  const int tiles_per_chunk = p.chunk_len / KVT;
-  auto enter_chunk = [&](TileIt& t) __attribute__((always_inline)) {   // skip chunks with nothing to visit
-    while (t.c < p.n_kv_chunks) {
-      const int gk = p.kv_gid[t.c];
-      t.diag = gk == gq;
-      t.n = gk < gq ? tiles_per_chunk : (gk > gq ? 0 : q_off_wg / KVT + 4);
-      if (t.n > 0) {
-        const int64_t crow = p.kv_row[t.c] + (PACKED ? seg_j0 * KVT : 0);
-        t.kp = kbase + crow * p.k_rs * 2;
-        t.vp = vbase + crow * p.v_rs * 2;
-        t.j = PACKED ? seg_j0 : 0;                   // (t.n stays the absolute end: tiles seg_j0 .. t.n - 1)
-        return;
-      }
-      ++t.c;
-    }
-  };
-  auto advance = [&](TileIt& t) __attribute__((always_inline)) {
-    t.kp += k_tile_bytes;
-    t.vp += v_tile_bytes;
-    if (++t.j == t.n) { ++t.c; enter_chunk(t); }
-  };
-  int n_tiles = 0;                                   // a multiple of 4 (chunk_len % 256 == 0)
-  for (int c = 0; c < p.n_kv_chunks; ++c) {
-    const int gk = p.kv_gid[c];
-    n_tiles += gk < gq ? tiles_per_chunk : (gk > gq ? 0 : q_off_wg / KVT + 4);
-  }
-  if constexpr (PACKED) n_tiles -= seg_j0;           // even, >= 4: seg_start[row] <= row
+  // ---- tile iterator (attn_tile.h) ----------------------------------------------------------------------------------------------
+  const CausalTileWalk<PACKED, AttnArgs> walk(p, kbase, vbase, gq, q_off_wg, seg_j0);
+  const int n_tiles = walk.count();                  // a multiple of 4 (chunk_len % 256 == 0); PACKED: even, >= 4: seg_start[row] <= row
   if (n_tiles == 0) {
     // a launch over REMOTE chunks only (context parallelism: the rank's own chunks are attended to before the gather lands,
     // dot_product_attention.forward_cp): these rows see none of them -> O = 0, lse = -inf, the merge ignores this part
@@ -429,10 +368,9 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
 
   // ---- prologue: K(0), V(0), K(1) -> LDS; S(0); the start of its softmax -----------------------------------------------------
   TileIt cur;
-  cur.c = 0; cur.j = 0; cur.n = 0; cur.diag = 0; cur.kp = kbase; cur.vp = vbase;
-  enter_chunk(cur);
+  walk.begin(cur);
   TileIt nx1 = cur;
-  advance(nx1);
+  walk.advance(nx1);
   dma_k(cur, 0); dma_v(cur, 0);
   dma_k(nx1, 1);                                     // n_tiles >= 4
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -453,7 +391,7 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
     TileIt nx2 = nx1;
     // K(t+2) and V(t+1) go out one piece at a time inside the S phase (K(t) in that slot was last read before the previous barrier)
     spread_k = more_k;
-    if (more_k) { advance(nx2); rk_next = vita_make_rsrc_uniform(nx2.kp); spread_k_slot = par; }
+    if (more_k) { walk.advance(nx2); rk_next = vita_make_rsrc_uniform(nx2.kp); spread_k_slot = par; }
     rv_next = vita_make_rsrc_uniform(nx1.vp); spread_v = true; spread_v_slot = par ^ 1;
     qk_phase(par ^ 1, lds0 + LDS_K + (par ^ 1) * TILEB, true, par);
     masks(nx1, par ^ 1);

@@ -26,21 +26,6 @@ constexpr int NF2 = 3;                                                          
 constexpr int THR = 8;                                                               // lazy running maximum, log2 units
 constexpr int NS = 16;                                                               // MFMA slots per phase
 
-typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) char lds_char;
-
-__device__ __forceinline__ float swap32_max(float x) {
-  const unsigned xi = __float_as_uint(x);
-  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float swap32_sum(float x) {
-  const unsigned xi = __float_as_uint(x);
-  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-
 // ---- filler schedule: units dealt to the NS MFMA slots of a phase by cumulative weight (attn64.hip's, over 16 slots) ---------------
 // phase 2 units: 0..31 max3 steps (weight 2), 32..33 running-maximum decision (weight 12), then 8 * NF2 exp half-units
 // (half 0: two fma + two exp2: weight 8; half 1: two row-sum adds + one bf16 pack: weight 6); phase 1 units: 8 * (8 - NF2) exp half-units
@@ -111,25 +96,23 @@ __device__ __forceinline__ void fwd64v_body(const AttnArgs& p, const unsigned ld
 #pragma unroll
     for (int ds = 0; ds < 4; ++ds) asm volatile("" : "+a"(qf[qb][ds]));      // live in AGPRs from here on
 
-  // ---- LDS fragment offsets (attn.hip's d = 64 layouts: K slot ^ ((row >> 1) & 7), V 32-byte chunk ^ (row & 2)) -----------------------
+  // ---- LDS fragment offsets (attn_tile.h's d = 64 layouts: K frag, V tr) ------------------------------------------------------------------
   unsigned koff[4], voff[2];
 #pragma unroll
-  for (int ds = 0; ds < 4; ++ds) koff[ds] = l31 * ROWB + (((2 * ds + hi) ^ ((l31 >> 1) & 7)) << 4);    // + 32 kb rows: immediate
-  {
-    const int g16 = lane >> 4, i16 = lane & 15, key_l = 4 * (g16 >> 1) + (i16 >> 2);
+  for (int ds = 0; ds < 4; ++ds) koff[ds] = frag_off<D>(l31, 2 * ds + hi);    // + 32 kb rows: immediate
+  const int key_l = tr_lane_row(lane);
 #pragma unroll
-    for (int db = 0; db < 2; ++db) {
-      const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
-      voff[db] = key_l * ROWB + (((col >> 4) ^ (key_l & 2)) << 5) + (col & 15) * 2;
-    }
+  for (int db = 0; db < 2; ++db) {
+    const int col = tr_lane_col(lane, db);
+    voff[db] = tr_off<D>(key_l, col >> 4, (col & 15) * 2);
   }
   // ---- LDS-DMA: a tile = 8 pieces of 1 KiB = 8 rows each; wave w moves pieces 2w, 2w + 1 of K and of V; swizzle on the SOURCE ----------
   unsigned dk_off[PW], dv_off[PW];
 #pragma unroll
   for (int q = 0; q < PW; ++q) {
     const int row = (wave * PW + q) * 8 + (lane >> 3), ps = lane & 7;
-    const int ks = ps ^ ((row >> 1) & 7);
-    const int vs = (((ps >> 1) ^ (row & 2)) << 1) | (ps & 1);
+    const int ks = frag_slot_inv<D>(row, ps);
+    const int vs = tr_slot_inv<D>(row, ps);
     dk_off[q] = (unsigned)((row * p.k_rs + ks * 8) * 2);     // bytes inside the tile (64 rows x row stride < 2^31: checked on the host)
     dv_off[q] = (unsigned)((row * p.v_rs + vs * 8) * 2);
   }

@@ -1,9 +1,8 @@
 // Launch arguments of the flash-attention forward kernels (attn.hip: 8 waves x 32 rows, every geometry; attn64.hip: 4 waves x
 // 64 rows, d = 128 causal with whole 256-row / 64-key tiles).
 #pragma once
-#include "vita_common.h"
+#include "attn_tile.h"
 
-constexpr int kMaxChunks = 32;
 constexpr int kMaxWindowTiles = 32;      // query tiles one windowed launch may name (vita_flash_attn_fwd_window)
 
 struct AttnArgs {

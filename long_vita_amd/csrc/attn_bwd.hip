@@ -14,41 +14,18 @@
 //
 // One wave per SIMD (launch_bounds 256,1: 512 registers) — correctness-first structure; MFMA operand
 // conventions are those of attn.hip (v_mfma_f32_32x32x16_bf16, any consistent k-slot assignment).
-// LDS images: "frag" layout (16-byte slot ^ (row & 15), ds_read_b128 fragments) and "tr" layout
-// (32-byte chunk ^ 2*(row & 3), ds_read_b64_tr_b16 transposed fragments); tiles are staged with
-// the LDS-DMA, swizzles applied on the source address.
+// LDS images: attn_tile.h's "frag" layout (ds_read_b128 fragments) and "tr" layout (ds_read_b64_tr_b16
+// transposed fragments); tiles are staged with the LDS-DMA, swizzles applied on the source address.
 #include "attn_bwd_args.h"
 #include <stdlib.h>
 
 namespace {
 
-constexpr int kMaxChunks = kBwdMaxChunks;
 // r04: both kernels are templates on the head size HD = 128 (the decoder) or 64 (InternViT's attention: the ViT's backward through its
 // native head size instead of zero-padded d = 128 copies, stage 2 trains the encoder).  What depends on HD: bytes per row (ROWB), the
-// k-steps over d (HD / 16) and output blocks (HD / 32), rows per 1-KiB DMA piece, and the LDS swizzles below (a 128-byte row is half a
-// bank period, so the row bits that select the slot move up by one).
+// k-steps over d (HD / 16) and output blocks (HD / 32), rows per 1-KiB DMA piece, and the LDS layouts (attn_tile.h; r05 added HD = 96, SigLIP's 72 zero-padded).
 
-typedef __attribute__((address_space(3))) char lds_char;
-typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
-typedef __attribute__((address_space(1))) const void gvoid;
-typedef __attribute__((address_space(3))) void lvoid;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
-
-template <int HD> __device__ __forceinline__ int frag_key(int row) { return HD == 128 ? (row & 15) : ((row >> 1) & 7); }
-template <int HD> __device__ __forceinline__ int tr_key(int row) { return HD == 128 ? ((row & 3) << 1) : (((row >> 1) & 1) << 1); }
-// r05: HD = 96 (SigLIP's 72, zero-padded to 96 instead of 128).  A 192-byte row is 3/4 of a bank period and has 12 slots, so the XOR keys do
-// not apply: the fragment layout ROTATES the slot by (row >> 2) & 3 (mod 12), the transposed layout needs no swizzle (derivation: attn.hip).
-template <int HD> __device__ __forceinline__ int frag_slot(int row, int slot) {          // logical -> physical 16-byte slot
-  return HD == 96 ? (slot + ((row >> 2) & 3)) % 12 : (slot ^ frag_key<HD>(row));
-}
-template <int HD> __device__ __forceinline__ int frag_slot_inv(int row, int ps) {        // physical -> logical (the XOR forms are involutions)
-  return HD == 96 ? (ps + 12 - ((row >> 2) & 3)) % 12 : (ps ^ frag_key<HD>(row));
-}
-template <int HD> __device__ __forceinline__ int tr_chunk(int row, int chunk) { return HD == 96 ? chunk : (chunk ^ tr_key<HD>(row)); }
-template <int HD> __device__ __forceinline__ int frag_off(int row, int slot) { return row * (2 * HD) + (frag_slot<HD>(row, slot) << 4); }
-template <int HD> __device__ __forceinline__ int tr_off(int row, int chunk, int b) { return row * (2 * HD) + (tr_chunk<HD>(row, chunk) << 5) + b; }
 
 // DMA one 1-KiB piece (4 rows x 256 B) of a [rows][128] bf16 tile into LDS; tile = descriptor of its first row (wave-uniform),
 // rows_valid = rows that exist (later ones are clamped, masked afterwards); lane -> (row piece*4 + lane/16, physical 16-B slot
@@ -61,7 +38,7 @@ __device__ __forceinline__ unsigned dma_piece_voff(int64_t rs, int rows_valid, i
   const int unit = piece * 64 + lane;                      // 16-byte unit of the image this lane fills
   const int row = unit / LPR;
   const int ps = unit % LPR;
-  const int ls = tr ? ((tr_chunk<HD>(row, ps >> 1) << 1) | (ps & 1)) : frag_slot_inv<HD>(row, ps);
+  const int ls = tr ? tr_slot_inv<HD>(row, ps) : frag_slot_inv<HD>(row, ps);
   const int r = row < rows_valid ? row : rows_valid - 1;
   return (unsigned)(r * rs * 2 + ls * 16);
 }
@@ -83,9 +60,8 @@ __device__ __forceinline__ bf16x8 read_frag(unsigned tile, int row, int slot) {
 // lane's row inside its 16-lane group), 32 columns starting at 32*db
 template <int HD>
 __device__ __forceinline__ bf16x8 read_tr(unsigned tile, int lane, int row_base, int db) {
-  const int g16 = lane >> 4, i16 = lane & 15;
-  const int row = row_base + 4 * (g16 >> 1) + (i16 >> 2);
-  const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
+  const int row = row_base + tr_lane_row(lane);
+  const int col = tr_lane_col(lane, db);
   const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(tile + tr_off<HD>(row, col >> 4, (col & 15) * 2)));
   const s16x4 c = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(tile + tr_off<HD>(row + 8, col >> 4, (col & 15) * 2)));
   return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, c, 0, 1, 2, 3, 4, 5, 6, 7));
@@ -149,7 +125,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_kernel(BwdArgs p) {
       dof[ds] = *reinterpret_cast<const bf16x8*>(dp + ds * 16);
     }
   }
-  const float lse2 = p.lse[(int64_t)head * p.n_q_rows + q_row] * 1.44269504088896340736f;
+  const float lse2 = p.lse[(int64_t)head * p.n_q_rows + q_row] * LOG2E;
   const float dlt = p.delta[(int64_t)head * p.n_q_rows + q_row];
   // consume the loads here: the compiler then waits for them HERE and not at their first use inside the loop, where its
   // s_waitcnt vmcnt() would also wait for the LDS-DMA pieces in flight (issued from asm, it does not know about them)
@@ -469,7 +445,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_kernel(BwdArgs p) {
         const f32x4 l4 = *(lds_f32x4*)(uintptr_t)(stat + (8 * rg + 4 * hi) * 4);
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          pr[rg * 4 + j] = __builtin_amdgcn_exp2f(fmaf(s[rg * 4 + j], p.scale_log2e, -l4[j] * 1.44269504088896340736f));
+          pr[rg * 4 + j] = __builtin_amdgcn_exp2f(fmaf(s[rg * 4 + j], p.scale_log2e, -l4[j] * LOG2E));
       }
       if (need_mask || p.seg_start) {                    // wave-uniform: only steps on the diagonal, or packed sequences
 #pragma unroll
@@ -565,24 +541,23 @@ extern "C" int vita_flash_attn_bwd_parts(const vita_attn_bwd_params* p, int part
   BwdArgs a;
   const int G = p->n_q_heads / p->n_kv_heads;
   a.q = (const bf16_t*)p->q; a.q_rs = p->q_row_stride; a.q_hs = p->q_head_stride;
-  a.q_gs = p->q_group_stride ? p->q_group_stride : p->q_head_stride * G;
+  a.q_gs = vita_group_stride(p->q_group_stride, p->q_head_stride, G);
   a.k = (const bf16_t*)p->k; a.k_rs = p->k_row_stride; a.k_hs = p->k_head_stride;
   a.v = (const bf16_t*)p->v; a.v_rs = p->v_row_stride; a.v_hs = p->v_head_stride;
   a.d_o = (const bf16_t*)p->d_o; a.do_rs = p->do_row_stride; a.do_hs = p->do_head_stride;
   a.lse = p->lse; a.delta = p->delta;
   a.dq = (bf16_t*)p->dq; a.dq_rs = p->dq_row_stride; a.dq_hs = p->dq_head_stride;
-  a.dq_gs = p->dq_group_stride ? p->dq_group_stride : p->dq_head_stride * G;
+  a.dq_gs = vita_group_stride(p->dq_group_stride, p->dq_head_stride, G);
   a.dk = (bf16_t*)p->dk; a.dk_rs = p->dk_row_stride; a.dk_hs = p->dk_head_stride;
   a.dv = (bf16_t*)p->dv; a.dv_rs = p->dv_row_stride; a.dv_hs = p->dv_head_stride;
   a.n_q_heads = p->n_q_heads; a.n_kv_heads = p->n_kv_heads; a.head_dim = p->head_dim;
   a.chunk_len = (int)p->chunk_len; a.n_q_chunks = p->n_q_chunks; a.n_kv_chunks = p->n_kv_chunks;
   a.n_q_rows = (int)(p->n_q_chunks * p->chunk_len);
-  a.scale = p->softmax_scale; a.scale_log2e = p->softmax_scale * 1.44269504088896340736f;
+  a.scale = p->softmax_scale; a.scale_log2e = p->softmax_scale * LOG2E;
   a.seg_start = p->q_seg_start; a.seg_end = p->k_seg_end;
   if ((p->q_seg_start != nullptr) != (p->k_seg_end != nullptr)) return VITA_ERR_INVALID_ARG;
   if (p->q_seg_start && (p->n_q_chunks != 1 || p->n_kv_chunks != 1)) return VITA_ERR_UNSUPPORTED;
-  for (int i = 0; i < p->n_q_chunks; ++i) a.q_gid[i] = p->q_chunk_gid[i];
-  for (int i = 0; i < p->n_kv_chunks; ++i) { a.kv_gid[i] = p->kv_chunk_gid[i]; a.kv_row[i] = p->kv_chunk_row[i]; }
+  vita_copy_chunk_tables(a, p);
 
   hipStream_t st = (hipStream_t)stream;
   static std::atomic<unsigned long long> attr_set{0};

@@ -28,21 +28,9 @@ namespace {
 constexpr bool DMA_SPREAD = DQ64_DMA_SPREAD != 0;     // (0: the eight pieces of a tile in a burst at the top of the iteration, for A / B builds)
 
 constexpr int D = 128, KVT = 64, QTILE = 256, ROWB = D * 2, TILEB = KVT * ROWB;       // 16 KiB per image of a 64-key tile
-// r04: ONE image per K tile serves the fragment reads (S^T = K Q^T) and the transposed reads (dQ^T += K^T dS^T): 16-byte slots XOR-ed with
-// swz(row) = ((row & 3) << 2) | ((row >> 2) & 3) — conflict-free for both access patterns (attn_bwd_kv64.hip's header); r02-r03 staged
-// a second, differently swizzled K image (48 -> 32 KB of LDS-DMA per tile)
+// r04: ONE image per K tile serves the fragment reads (S^T = K Q^T) and the transposed reads (dQ^T += K^T dS^T): attn_tile.h's dual
+// layout, conflict-free for both access patterns; r02-r03 staged a second, differently swizzled K image (48 -> 32 KB of LDS-DMA per tile)
 constexpr int LDS_KF = 0, LDS_VF = 3 * TILEB, LDS_BYTES = 6 * TILEB;   // K [3] | V frag [3] = 96 KiB
-
-typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) char lds_char;
-
-struct TileIt {
-  int c, j, n;        // chunk, tile inside chunk, tiles to visit in this chunk; c == n_kv_chunks: end
-  int diag;           // chunk c is the query tile's own chunk
-  const char* kp;     // first K / V row of the tile
-  const char* vp;
-};
 
 // PACKED (r03): packed samples (p.seg_start, one chunk) — the workgroup starts at the tile of its first row's segment; halves that begin
 // before the segment of the wave's last row get a second arithmetic mask (key >= seg_start[row]), as in attn64.hip.
@@ -53,17 +41,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(BwdArgs p) {
   const int tid = threadIdx.x, lane = tid & 63, hi = lane >> 5, l31 = lane & 31;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 
-  const int G = p.n_q_heads / p.n_kv_heads;
-  const int tiles_per_chunk = p.chunk_len / QTILE;
-  int bid = blockIdx.x;
-  const int kvh = bid % p.n_kv_heads; bid /= p.n_kv_heads;
-  const int hq = bid % G; bid /= G;
-  const int n_qt = p.n_q_chunks * tiles_per_chunk;
-  const int qt_rev = n_qt - 1 - bid;                   // heaviest query tiles first
-  const int qc = qt_rev / tiles_per_chunk;
-  const int qti = qt_rev % tiles_per_chunk;
+  const QTileId wg = decode_q_tile(p, blockIdx.x, p.chunk_len / QTILE);     // heaviest query tiles first
+  const int kvh = wg.kvh, hq = wg.hq, head = wg.head, qc = wg.qc, qti = wg.qti;
   const int gq = p.q_gid[qc];
-  const int head = kvh * G + hq;
   const int q_off_wg = qti * QTILE;
   const int q_off = q_off_wg + wave * 64;
   const float scale_log2e = p.scale_log2e, scale = p.scale;
@@ -89,7 +69,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(BwdArgs p) {
         qf[qb][ds] = *reinterpret_cast<const bf16x8*>(qp + (int64_t)32 * qb * p.q_rs + ds * 16);
         dof[qb][ds] = *reinterpret_cast<const bf16x8*>(dp_ + (int64_t)32 * qb * p.do_rs + ds * 16);
       }
-      lse2[qb] = p.lse[(int64_t)head * p.n_q_rows + row0 + 32 * qb] * 1.44269504088896340736f;
+      lse2[qb] = p.lse[(int64_t)head * p.n_q_rows + row0 + 32 * qb] * LOG2E;
       dlt_s[qb] = p.delta[(int64_t)head * p.n_q_rows + row0 + 32 * qb] * scale;
     }
   }
@@ -101,32 +81,28 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(BwdArgs p) {
     asm volatile("" : "+v"(lse2[qb]), "+v"(dlt_s[qb]));
   }
 
-  // ---- LDS fragment offsets (attn.hip's layouts) -----------------------------------------------------------------------------------
-  auto swz = [](int row) { return ((row & 3) << 2) | ((row >> 2) & 3); };
+  // ---- LDS fragment offsets (attn_tile.h's dual layout) --------------------------------------------------------------------------
   unsigned koff[8], toff[4], toff8[4];               // toff8: the second transposed read, 8 keys further down
 #pragma unroll
-  for (int ds = 0; ds < 8; ++ds) koff[ds] = l31 * ROWB + (((2 * ds + hi) ^ swz(l31 & 15)) << 4);       // + 32 kb rows: immediate
-  {
-    const int g16 = lane >> 4, i16 = lane & 15, key_l = 4 * (g16 >> 1) + (i16 >> 2);
+  for (int ds = 0; ds < 8; ++ds) koff[ds] = dual_off(l31, 2 * ds + hi);       // + 32 kb rows: immediate
+  const int key_l = tr_lane_row(lane);
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
-      toff[db] = key_l * ROWB + (((col >> 3) ^ swz(key_l)) << 4) + (col & 7) * 2;
-      toff8[db] = (key_l + 8) * ROWB + (((col >> 3) ^ swz(key_l + 8)) << 4) + (col & 7) * 2;
-    }
+  for (int db = 0; db < 4; ++db) {
+    const int col = tr_lane_col(lane, db);
+    toff[db] = dual_off(key_l, col >> 3) + (col & 7) * 2;
+    toff8[db] = dual_off(key_l + 8, col >> 3) + (col & 7) * 2;
   }
   // ---- LDS-DMA: wave w moves pieces 4w .. 4w+3 (1 KiB = 4 rows) of each image; swizzles on the SOURCE address --------------------
   unsigned off_kf[4], off_vf[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int row = (wave * 4 + q) * 4 + (lane >> 4), ps = lane & 15;
-    const int fs = ps ^ swz(row & 15);
+    const int fs = dual_slot(row, ps);
     off_kf[q] = (unsigned)((row * p.k_rs + fs * 8) * 2);
     off_vf[q] = (unsigned)((row * p.v_rs + fs * 8) * 2);
   }
   const char* kbase = (const char*)(p.k + (int64_t)kvh * p.k_hs);
   const char* vbase = (const char*)(p.v + (int64_t)kvh * p.v_hs);
-  const int k_tile_bytes = (int)(p.k_rs * 2 * KVT), v_tile_bytes = (int)(p.v_rs * 2 * KVT);
   const unsigned lds_w = lds0 + wave * 4096;
   auto dma_kv = [&](const TileIt& t, int slot3) __attribute__((always_inline)) {                // K, V fragment images -> ring slot
     const vita_rsrc_t rk = vita_make_rsrc_uniform(t.kp), rv = vita_make_rsrc_uniform(t.vp);
@@ -148,34 +124,9 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(BwdArgs p) {
     else vita_lds_dma16(vita_make_rsrc_uniform(t.vp), off_vf[i - 4], base + LDS_VF + (i - 4) * 1024);
   };
 
-  // ---- tile iterator (as attn64.hip) ---------------------------------------------------------------------------------------------
-  const int kv_tiles_per_chunk = p.chunk_len / KVT;
-  auto enter_chunk = [&](TileIt& t) __attribute__((always_inline)) {
-    while (t.c < p.n_kv_chunks) {
-      const int gk = p.kv_gid[t.c];
-      t.diag = gk == gq;
-      t.n = gk < gq ? kv_tiles_per_chunk : (gk > gq ? 0 : q_off_wg / KVT + 4);
-      if (t.n > 0) {
-        const int64_t crow = p.kv_row[t.c] + (PACKED ? seg_j0 * KVT : 0);
-        t.kp = kbase + crow * p.k_rs * 2;
-        t.vp = vbase + crow * p.v_rs * 2;
-        t.j = PACKED ? seg_j0 : 0;                   // (t.n stays the absolute end)
-        return;
-      }
-      ++t.c;
-    }
-  };
-  auto advance = [&](TileIt& t) __attribute__((always_inline)) {
-    t.kp += k_tile_bytes;
-    t.vp += v_tile_bytes;
-    if (++t.j == t.n) { ++t.c; enter_chunk(t); }
-  };
-  int n_tiles = 0;                                   // a multiple of 4, >= 4 (chunk_len % 256 == 0, the diagonal chunk is present)
-  for (int c = 0; c < p.n_kv_chunks; ++c) {
-    const int gk = p.kv_gid[c];
-    n_tiles += gk < gq ? kv_tiles_per_chunk : (gk > gq ? 0 : q_off_wg / KVT + 4);
-  }
-  if constexpr (PACKED) n_tiles -= seg_j0;           // >= 4: seg_start[row] <= row
+  // ---- tile iterator (attn_tile.h) -----------------------------------------------------------------------------------------------
+  const CausalTileWalk<PACKED, BwdArgs> walk(p, kbase, vbase, gq, q_off_wg, seg_j0);
+  const int n_tiles = walk.count();                  // a multiple of 4, >= 4 (the diagonal chunk is present); PACKED: >= 4: seg_start[row] <= row
 
   // ---- state ---------------------------------------------------------------------------------------------------------------------
   f32x16 o[2][4];                                    // dQ^T[qb][db] (AGPRs)
@@ -309,12 +260,11 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(BwdArgs p) {
 
   // ---- prologue: tile 0 (all three images) and tile 1 (K, V) -> LDS; S^T / dP^T / P^T of half 0 -------------------------------------
   TileIt cur;
-  cur.c = 0; cur.j = 0; cur.n = 0; cur.diag = 0; cur.kp = kbase; cur.vp = vbase;
-  enter_chunk(cur);
+  walk.begin(cur);
   TileIt nx1 = cur;
-  advance(nx1);                                      // n_tiles >= 4
+  walk.advance(nx1);                                 // n_tiles >= 4
   TileIt nx2 = nx1;
-  advance(nx2);
+  walk.advance(nx2);
   dma_kv(cur, 0); dma_kv(nx1, 1);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -348,7 +298,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq64_kernel(BwdArgs p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     cur = nx1; nx1 = nx2;
-    if (has2) advance(nx2);
+    if (has2) walk.advance(nx2);
     const int tmp = s3; s3 = s3n; s3n = s3nn; s3nn = tmp;
     tpar ^= 1;
   };

@@ -1,8 +1,6 @@
 // Shared between attn_bwd.hip (the general backward kernels and the C entry point) and attn_bwd64.hip (the 64-rows-per-wave dQ kernel).
 #pragma once
-#include "vita_common.h"
-
-constexpr int kBwdMaxChunks = 32;
+#include "attn_tile.h"
 
 struct BwdArgs {
   const bf16_t* q; int64_t q_rs, q_hs, q_gs;        // query rows (rotated), grouped head addressing
@@ -19,9 +17,9 @@ struct BwdArgs {
   float scale, scale_log2e;
   const int* seg_start;   // packed sequences (single chunk): first row of each query row's segment, or null
   const int* seg_end;     // one past the last row of each key row's segment, or null
-  int q_gid[kBwdMaxChunks];
-  int kv_gid[kBwdMaxChunks];
-  int64_t kv_row[kBwdMaxChunks];
+  int q_gid[kMaxChunks];
+  int kv_gid[kMaxChunks];
+  int64_t kv_row[kMaxChunks];
 };
 
 // attn_bwd64.hip: dQ with 64 query rows per wave (causal, whole 256-row tiles, every query chunk also a key chunk)

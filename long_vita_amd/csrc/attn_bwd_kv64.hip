@@ -13,9 +13,8 @@
 //   * lse / delta belong to the TILE's rows here (they vary along the accumulator registers, not along lanes): each tile's 64 + 64
 //     values are staged next to its images and read as 4-float vectors right before the half that needs them;
 //   * images per tile (r04): IS_DK — Q and dO, ONE image each: the fragment reads (ds_read_b128, S and dP) and the transposed reads
-//     (ds_read_b64_tr_b16, dK^T += Q^T dS) of Q come from the same LDS image.  Its 16-byte slots are XOR-ed with
-//     swz(row) = ((row & 3) << 2) | ((row >> 2) & 3): 16 consecutive rows land in 16 different slots (fragment reads), and the
-//     four rows a 32-lane half of a transposed read touches land in four different 64-byte bank groups — both conflict-free, where
+//     (ds_read_b64_tr_b16, dK^T += Q^T dS) of Q come from the same LDS image: attn_tile.h's dual layout, whose static_asserts
+//     hold the argument that both reads are conflict-free, where
 //     r02-r03 staged a second, differently swizzled copy of the Q tile (48 -> 32 KB of LDS-DMA per tile, 8 -> 6 tiles of LDS);
 //     !IS_DK — Q fragment layout + dO transposed layout (two tensors).  Rings of 3 (2 for dO^T), LDS-DMA from inline asm, one barrier per tile.
 // Reference behaviour restated: the autograd of M/core/transformer/dot_product_attention.py:186-289 (flash-attn / TE backward).
@@ -25,13 +24,6 @@
 namespace {
 
 constexpr int D = 128, QT = 64, KTILE = 256, ROWB = D * 2, TILEB = QT * ROWB;           // 16 KiB per image of a 64-row query tile
-constexpr float LOG2E = 1.44269504088896340736f;
-
-typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) char lds_char;
-
 struct QTileIt {
   int hq, c, j, jend;   // query head of the group, query chunk, tile inside the chunk, one past the last tile; hq == G: end
   int diag;             // chunk c is the key block's own chunk
@@ -93,23 +85,20 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv64_kernel(BwdArgs p) {
       if (IS_DK) asm volatile("" : "+a"(vf[kb][ds]));
     }
 
-  // ---- LDS fragment offsets (attn.hip's layouts) ---------------------------------------------------------------------------------------
-  auto swz = [](int row) { return ((row & 3) << 2) | ((row >> 2) & 3); };      // the slot XOR of the dual-use image (header)
+  // ---- LDS fragment offsets (attn_tile.h: the dual layout; !IS_DK reads dO^T from its own tr-layout image) ------------------------------
   unsigned foff[8], toff[4], toff8[4];               // toff8: the second transposed read, 8 rows further down
 #pragma unroll
-  for (int ds = 0; ds < 8; ++ds) foff[ds] = l31 * ROWB + (((2 * ds + hi) ^ swz(l31 & 15)) << 4);       // + 32 qh rows: immediate
-  {
-    const int g16 = lane >> 4, i16 = lane & 15, row_l = 4 * (g16 >> 1) + (i16 >> 2);
+  for (int ds = 0; ds < 8; ++ds) foff[ds] = dual_off(l31, 2 * ds + hi);       // + 32 qh rows: immediate
+  const int row_l = tr_lane_row(lane);
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
-      if (IS_DK) {                                   // Q^T out of the fragment image
-        toff[db] = row_l * ROWB + (((col >> 3) ^ swz(row_l)) << 4) + (col & 7) * 2;
-        toff8[db] = (row_l + 8) * ROWB + (((col >> 3) ^ swz(row_l + 8)) << 4) + (col & 7) * 2;
-      } else {                                       // dO^T out of its own transposed-layout image (32-byte chunk ^ 2 (row & 3))
-        toff[db] = row_l * ROWB + (((col >> 4) ^ ((row_l & 3) << 1)) << 5) + (col & 15) * 2;
-        toff8[db] = toff[db] + 8 * ROWB;
-      }
+  for (int db = 0; db < 4; ++db) {
+    const int col = tr_lane_col(lane, db);
+    if (IS_DK) {                                   // Q^T out of the fragment image
+      toff[db] = dual_off(row_l, col >> 3) + (col & 7) * 2;
+      toff8[db] = dual_off(row_l + 8, col >> 3) + (col & 7) * 2;
+    } else {                                       // dO^T out of its own transposed-layout image
+      toff[db] = tr_off<D>(row_l, col >> 4, (col & 15) * 2);
+      toff8[db] = toff[db] + 8 * ROWB;
     }
   }
   // ---- LDS-DMA: wave w moves pieces 4w .. 4w+3 (1 KiB = 4 rows) of each image; swizzles on the SOURCE address ------------------------
@@ -117,8 +106,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_kv64_kernel(BwdArgs p) {
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int row = (wave * 4 + q) * 4 + (lane >> 4), ps = lane & 15;
-    const int fs = ps ^ swz(row & 15);
-    const int ts = (((ps >> 1) ^ ((row & 3) << 1)) << 1) | (ps & 1);
+    const int fs = dual_slot(row, ps);
+    const int ts = tr_slot_inv<D>(row, ps);
     off_qf[q] = (unsigned)((row * p.q_rs + fs * 8) * 2);
     off_qt[q] = (unsigned)((row * p.q_rs + ts * 8) * 2);
     off_df[q] = (unsigned)((row * p.do_rs + fs * 8) * 2);

@@ -11,7 +11,7 @@
 // ds_write_b128 / ds_read_b128 x 4 per lane, lanes consecutive: conflict-free), double-buffered, ONE workgroup barrier per half.
 // P reaches dS rounded to bf16 — as in the reference's own chain (scale_mask_softmax hands bf16 probabilities to the backward,
 // M/core/transformer/dot_product_attention.py:186-289); kv64 used the unrounded value there.
-// LDS images: ONE dual-use image per Q tile and per dO tile (slot XOR swz(row), attn_bwd_kv64.hip's header): A reads Q as fragments
+// LDS images: ONE dual-use image per Q tile and per dO tile (attn_tile.h's dual layout): A reads Q as fragments
 // and dO transposed, B reads dO as fragments and Q transposed — 32 KB of LDS-DMA per 64-row query tile, rings of four (r05; three in r04).
 // Pipeline per half u (32 query rows), 16-MFMA groups, one MFMA + its share of the arithmetic per slot:
 //     B: [16 dP MFMAs of half u + 1 || dS(u), k-step 0 (8 pairs, every other slot)]  [16 dK MFMAs of half u || dS(u), k-step 1 under the first 8]
@@ -46,14 +46,7 @@ namespace {
 constexpr int D = 128, QT = 64, KWG = 128, ROWB = D * 2, TILEB = QT * ROWB;             // 16 KiB per image of a 64-row query tile
 constexpr int NRING = 4;                                // Q / dO tile images in LDS: tiles t, t + 1 (read), t + 2 (landed or landing), t + 3 (just issued)
 constexpr int LDS_Q = 0, LDS_DO = NRING * TILEB, LDS_ST = 2 * NRING * TILEB, LDS_X = LDS_ST + NRING * 512, LDS_TOTAL = LDS_X + 2 * 2 * 4096;
-constexpr float LOG2E = 1.44269504088896340736f;
 constexpr int PF_NONE = 0, PF_FRAG = 1, PF_TR = 2;
-
-typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-typedef __attribute__((address_space(3))) const f32x4 lds_f32x4;
-typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
-typedef __attribute__((address_space(3))) u32x4 lds_u32x4;
-typedef __attribute__((address_space(3))) char lds_char;
 
 struct QTileIt {
   int hq, c, j, jlo;    // query head of the group, query chunk, tile inside the chunk, first tile of the chunk the key block reaches
@@ -93,26 +86,23 @@ __device__ __forceinline__ void kvp_body(const BwdArgs& p, const unsigned lds0, 
       for (int ds = 0; ds < 8; ++ds) asm volatile("" : "+a"(wf[kb][ds]));      // consumed (loads waited for) and pinned in AGPRs here
   };
 
-  // ---- LDS offsets of the dual-use images ----------------------------------------------------------------------------------------------
-  auto swz = [](int row) { return ((row & 3) << 2) | ((row >> 2) & 3); };
+  // ---- LDS offsets of the dual-use images (attn_tile.h) --------------------------------------------------------------------------------
   unsigned foff[8], toff[4], toff8[4];
 #pragma unroll
-  for (int ds = 0; ds < 8; ++ds) foff[ds] = l31 * ROWB + (((2 * ds + hi) ^ swz(l31 & 15)) << 4);       // + 32 qh rows: immediate
-  {
-    const int g16 = lane >> 4, i16 = lane & 15, row_l = 4 * (g16 >> 1) + (i16 >> 2);
+  for (int ds = 0; ds < 8; ++ds) foff[ds] = dual_off(l31, 2 * ds + hi);       // + 32 qh rows: immediate
+  const int row_l = tr_lane_row(lane);
 #pragma unroll
-    for (int db = 0; db < 4; ++db) {
-      const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
-      toff[db] = row_l * ROWB + (((col >> 3) ^ swz(row_l)) << 4) + (col & 7) * 2;
-      toff8[db] = (row_l + 8) * ROWB + (((col >> 3) ^ swz(row_l + 8)) << 4) + (col & 7) * 2;
-    }
+  for (int db = 0; db < 4; ++db) {
+    const int col = tr_lane_col(lane, db);
+    toff[db] = dual_off(row_l, col >> 3) + (col & 7) * 2;
+    toff8[db] = dual_off(row_l + 8, col >> 3) + (col & 7) * 2;
   }
   // ---- LDS-DMA: wave w moves pieces 4w .. 4w+3 (1 KiB = 4 rows) of both images; the swizzle goes on the SOURCE address -----------------
   unsigned off_q[4], off_do[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
     const int row = (wave * 4 + q) * 4 + (lane >> 4), ps = lane & 15;
-    const int fs = ps ^ swz(row & 15);
+    const int fs = dual_slot(row, ps);
     off_q[q] = (unsigned)((row * p.q_rs + fs * 8) * 2);
     off_do[q] = (unsigned)((row * p.do_rs + fs * 8) * 2);
   }

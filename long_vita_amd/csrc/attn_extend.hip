@@ -20,7 +20,7 @@
 // Reference behaviour restated: H/models/long_vita_qwen2_intern/modeling_long_vita.py:150-202 (q_len > 1 behind a DynamicCache:
 // cache_position = arange(past_seen, past_seen + s), causal mask over past + new keys) and the cached decode loop
 // M/inference/text_generation/generation.py:127-131 fed more than one token.
-#include "vita_common.h"
+#include "attn_tile.h"
 
 namespace {
 
@@ -45,19 +45,7 @@ struct ExtArgs {
   float scale_log2e;
 };
 
-__device__ __forceinline__ float swap32_max(float x) {
-  const unsigned xi = __float_as_uint(x);
-  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
-  return fmaxf(__uint_as_float(r[0]), __uint_as_float(r[1]));
-}
-__device__ __forceinline__ float swap32_sum(float x) {
-  const unsigned xi = __float_as_uint(x);
-  auto r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
-  return __uint_as_float(r[0]) + __uint_as_float(r[1]);
-}
-// the LDS layouts of attn.hip at d = 128
-__device__ __forceinline__ int k_lds_off(int row, int slot) { return row * 256 + ((slot ^ (row & 15)) << 4); }
-__device__ __forceinline__ int v_lds_off(int row, int chunk, int b) { return row * 256 + ((chunk ^ ((row & 3) << 1)) << 5) + b; }
+// K tiles in attn_tile.h's frag layout, V tiles in its tr layout, at d = 128
 
 // last visible key of query row i (-1: none)
 __device__ __forceinline__ int last_visible_key(const ExtArgs& p, int i) {
@@ -86,9 +74,6 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
   constexpr int RPP = 1024 / ROWB;           // tile rows per piece
 
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K tile | V tile]
-  typedef __attribute__((address_space(3))) char lds_char;
-  typedef __attribute__((address_space(3))) const bf16x8 lds_bf16x8;
-  typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -129,16 +114,13 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
   // ---- per-lane LDS read offsets ---------------------------------------------------------------------------------------------------
   unsigned koff[DS];
 #pragma unroll
-  for (int ds = 0; ds < DS; ++ds) koff[ds] = k_lds_off(l31, 2 * ds + hi);
+  for (int ds = 0; ds < DS; ++ds) koff[ds] = frag_off<D>(l31, 2 * ds + hi);
   unsigned voff[DB];
-  {
-    const int g16 = lane >> 4, i16 = lane & 15;
-    const int key_l = 4 * (g16 >> 1) + (i16 >> 2);
+  const int key_l = tr_lane_row(lane);
 #pragma unroll
-    for (int db = 0; db < DB; ++db) {
-      const int col = 32 * db + 16 * (g16 & 1) + 4 * (i16 & 3);
-      voff[db] = TILEB + v_lds_off(key_l, col >> 4, (col & 15) * 2);
-    }
+  for (int db = 0; db < DB; ++db) {
+    const int col = tr_lane_col(lane, db);
+    voff[db] = TILEB + tr_off<D>(key_l, col >> 4, (col & 15) * 2);
   }
 
   f32x16 o_acc[DB];
@@ -152,16 +134,14 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
   const bf16_t* vbase = p.v + (int64_t)kvh * p.kv_gs;
 
   // ---- LDS-DMA: wave w issues pieces q = 0 .. PIECES - 1 of K and of V; the bank swizzle is applied to the SOURCE address ----------
-  typedef __attribute__((address_space(1))) const void gvoid;
-  typedef __attribute__((address_space(3))) void lvoid;
   unsigned dk_off[PIECES], dv_off[PIECES];
   int d_row[PIECES], d_ks[PIECES], d_vs[PIECES];
 #pragma unroll
   for (int q = 0; q < PIECES; ++q) {
     const int row = (wave * PIECES + q) * RPP + lane / SLOTS;   // tile row this lane fills
     const int ps = lane % SLOTS;                                // physical 16-byte slot in the row
-    d_ks[q] = ps ^ (row & 15);
-    d_vs[q] = (((ps >> 1) ^ ((row & 3) << 1)) << 1) | (ps & 1);
+    d_ks[q] = frag_slot_inv<D>(row, ps);
+    d_vs[q] = tr_slot_inv<D>(row, ps);
     d_row[q] = row;
     dk_off[q] = (unsigned)(row * p.kv_rs + d_ks[q] * 8);
     dv_off[q] = (unsigned)(row * p.kv_rs + d_vs[q] * 8);
@@ -430,7 +410,7 @@ extern "C" int vita_flash_attn_extend_fwd(const vita_attn_extend_params* p, void
   const int64_t key_tiles = (p->n_keys + KVT - 1) / KVT;
   a.tiles_per_split = (int)((key_tiles + a.n_splits - 1) / a.n_splits);
   a.quant_m = extend_splits(p->t, p->n_q_heads, p->n_keys, false) > 1;      // by shape, whatever the developer switch forces
-  a.scale_log2e = p->softmax_scale * 1.44269504088896340736f;
+  a.scale_log2e = p->softmax_scale * LOG2E;
   const int64_t n_rec = (int64_t)p->n_q_heads * p->t;
   a.pm = a.pl = a.po = nullptr;
   if (a.n_splits > 1) {
