@@ -59,6 +59,32 @@ int vita_logit_postprocess(void* logits, int64_t ld, int64_t rows, int64_t cols,
 int vita_logit_postprocess_bwd(const void* y, int64_t ldy, void* grad, int64_t ldg, int64_t rows, int64_t cols,
                                float multiplier_scale, float softcapping, void* stream);
 
+/* Token choice on the device: repetition penalty, then greedy arg-max or temperature / top-k / top-p sampling, in the order
+ * transformers' `generate` applies its processors for the checkpoint's generation config
+ * (H/models/long_vita_qwen2_intern/generation_config.json:4-12: repetition_penalty 1.05, temperature 0.7, top_k 20, top_p 0.8;
+ * tools/inference_long_vita.py:820-826,868 loads it, turns do_sample off and calls model.generate).  fp32 on the bf16 logits:
+ *   x = float(logit);  seen[id] && penalty != 1:  x = x < 0 ? x * penalty : x / penalty
+ *   !do_sample: token = arg-max x (equal maxima: the lowest id), kept = 1; temperature / top_k / top_p are ignored
+ *   do_sample:  x /= temperature;  0 < top_k < cols keeps x >= (k-th largest x), every tie with it included;  0 < top_p < 1 keeps, of
+ *     what is left, a token iff the softmax mass of all tokens with a STRICTLY higher score is < top_p (equal scores stay or go
+ *     together; at least one token stays);  token = the first kept token, in ascending id, whose inclusive mass prefix exceeds
+ *     u * (kept mass);  kept = the number of kept tokens.  Masses are exp(x - max) as 2^-40 fixed point: sums are exact, the result
+ *     is bit-reproducible.
+ *   mark_chosen && seen: seen[token] = 1 after the choice.
+ * One row of `seen` is `cols` bytes; the workspace (16-byte aligned) holds the fp32 scores.  cols, ld % 8 == 0; logits 16-byte aligned;
+ * cols <= 2^23 (the 64-bit mass sums cannot overflow), else VITA_ERR_UNSUPPORTED.
+ * vita_token_seen_mark: seen[ids[i]] = 1; an id outside [0, vocab) sets *err_flag (may be NULL) and writes nothing. */
+int vita_token_seen_mark(const int64_t* ids, int64_t n, uint8_t* seen, int64_t vocab, int32_t* err_flag, void* stream);
+/* H/models/long_vita_qwen2_intern/generation_config.json:4-12; tools/inference_long_vita.py:820-826,868 */
+int64_t vita_select_token_workspace_bytes(int64_t rows, int64_t cols);
+/* H/models/long_vita_qwen2_intern/generation_config.json:4-12; tools/inference_long_vita.py:820-826,868 */
+int vita_select_token(const void* logits /* bf16 [rows, ld] */, int64_t ld, int64_t rows, int64_t cols,
+                      uint8_t* seen /* [rows, cols] bytes, may be NULL */, float repetition_penalty,
+                      int do_sample, float temperature, int top_k, float top_p,
+                      const float* u /* [rows] uniforms in [0,1), device; NULL iff !do_sample */,
+                      int64_t* token_out /* [rows] */, int32_t* kept_out /* [rows], may be NULL */,
+                      int mark_chosen, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * RoPE.  Replaces M/core/models/common/embeddings/rotary_pos_embedding.py:84-122 (table),
  * :181-204 (apply_rotary_pos_emb_bshd) and apex fused_apply_rotary_pos_emb (:248-252).

@@ -140,7 +140,7 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
                                                     do_sample=False, top_k=0, top_p=0.0, temperature=1.0,
                                                     use_eod_token_for_early_termination=True, external_inputs=None,
                                                     *, use_kv_cache=True, logit_mask=True, termination_id=None,
-                                                    reference_compat=False):
+                                                    reference_compat=False, token_selector=None):
     """Generator with the reference's contract (:33-280): `tokens` [1, max_sequence_length] holds the prompt
     (length lengths[0]) followed by padding and is filled in place; yields (tokens[:, :ctx+1], lengths,
     output_log_probs) per generated token.  args.use_kv_cache / args.logit_mask / the tokenizer's eod are keyword
@@ -149,7 +149,10 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
     use_kv_cache=False is the reference's CP behaviour: the whole buffer is re-prefilled for every token
     (:127-135).  use_kv_cache=True prefills once — under CP on the prompt padded to _cp_prefill_length — and then
     feeds one token per step to the sharded cache; every CP rank gets identical logits, so there is no
-    sync_output on those steps."""
+    sync_output on those steps.
+
+    token_selector(last_token_logits [1, V], context_length) -> [1] token ids, when given, replaces _sample_strategy (the device-side
+    choice with a repetition penalty, hf_adaptor.py); None: nothing changes."""
     from .inference_params import ForwardStep
     batch_size, max_sequence_length = tokens.shape
     if batch_size != 1:
@@ -205,8 +208,11 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
                 last_token_logits = logits[:, -1, :] if block is None else logits[:, block, :]
             else:
                 last_token_logits = logits[:, context_length - 1, :]
-        _, new_sample = _sample_strategy(last_token_logits, do_sample=do_sample, top_k=top_k, top_p=top_p,
-                                         temperature=temperature)
+        if token_selector is not None:
+            new_sample = token_selector(last_token_logits, context_length).view(-1)
+        else:
+            _, new_sample = _sample_strategy(last_token_logits, do_sample=do_sample, top_k=top_k, top_p=top_p,
+                                             temperature=temperature)
         started = lengths <= context_length
         tokens[started, context_length] = new_sample[started]
         if return_output_log_probs:

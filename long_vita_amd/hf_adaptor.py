@@ -24,13 +24,14 @@ as transformers' `Cache` is; `labels` raises (training goes through pretrain_lon
 from __future__ import annotations
 
 import json
+import math
 import os
 import types
 from typing import Optional
 
 import torch
 
-from . import checkpoint, generation, gpt_vl_model, lib, vision
+from . import checkpoint, generation, gpt_vl_model, lib, ops, vision
 from .inference_params import ForwardStep
 
 
@@ -59,6 +60,57 @@ def configs_from_hf(config):
                                ln_eps=_get(v, "layer_norm_eps", 1e-6), proj_ln_eps=1e-5,           # torch.nn.LayerNorm default, resampler_projector.py:17
                                llm_hidden=hidden)
     return gcfg, vcfg
+
+
+def _config_items(gc):
+    if isinstance(gc, dict):
+        return dict(gc)
+    return dict(gc.to_dict()) if hasattr(gc, "to_dict") else dict(vars(gc))
+
+
+# generation-config keys that change which token is chosen and that this path does not implement: name -> "has its default value"
+_REFUSED_KEYS = {
+    "num_beams": lambda v: v <= 1, "num_beam_groups": lambda v: v <= 1, "num_return_sequences": lambda v: v <= 1,
+    "no_repeat_ngram_size": lambda v: v <= 0, "encoder_no_repeat_ngram_size": lambda v: v <= 0, "penalty_alpha": lambda v: v == 0,
+    "min_p": lambda v: v == 0, "typical_p": lambda v: v >= 1, "epsilon_cutoff": lambda v: v <= 0, "eta_cutoff": lambda v: v <= 0,
+    "encoder_repetition_penalty": lambda v: v == 1, "bad_words_ids": lambda v: not v, "suppress_tokens": lambda v: not v,
+    "begin_suppress_tokens": lambda v: not v, "sequence_bias": lambda v: not v, "force_words_ids": lambda v: not v,
+    "constraints": lambda v: not v, "guidance_scale": lambda v: v <= 1, "min_length": lambda v: v <= 0,
+    "min_new_tokens": lambda v: v <= 0, "exponential_decay_length_penalty": lambda v: not v, "renormalize_logits": lambda v: not v,
+    "dola_layers": lambda v: not v, "watermarking_config": lambda v: not v,
+}
+
+
+def selection_params(gc, do_sample=None):
+    """The effective (repetition_penalty, do_sample, temperature, top_k, top_p) of a generation config (an object or the dict of
+    generation_config.json; H/models/long_vita_qwen2_intern/generation_config.json:4-12), `do_sample` overriding the config's as the
+    argument of generate() does (tools/inference_long_vita.py:820-826 sets it to False).  Pure host code.  A key that changes the choice
+    of tokens and that the HIP path does not implement raises NotImplementedError when it is set to anything but its default: the path
+    answers as transformers would, or not at all.  Keys that do not bear on the choice (bos_token_id, transformers_version,
+    chat_format, max_window_size, ...) pass."""
+    items = _config_items(gc)
+    bad = []
+    for name, value in items.items():
+        if value is None:
+            continue
+        if name.startswith("forced_"):
+            bad.append(name)
+        elif name in _REFUSED_KEYS and not _REFUSED_KEYS[name](value):
+            bad.append(name)
+    if bad:
+        raise NotImplementedError("generation config keys the HIP path does not implement (they change the choice of tokens): "
+                                  + ", ".join(f"{n}={items[n]!r}" for n in sorted(bad)))
+
+    def positive(name):                                  # None / absent: the default 1.0; anything else must be what the C entry accepts
+        v = items.get(name)
+        v = 1.0 if v is None else float(v)
+        if not (v > 0.0 and math.isfinite(v)):
+            raise ValueError(f"{name} must be a positive finite number, got {items.get(name)!r}")
+        return v
+
+    penalty, temperature = positive("repetition_penalty"), positive("temperature")
+    sample = bool(items.get("do_sample", False)) if do_sample is None else bool(do_sample)
+    return penalty, sample, temperature, int(items.get("top_k") or 0), float(items.get("top_p") or 0.0)
 
 
 class HipCache:
@@ -96,6 +148,7 @@ class LongVITAForCausalLM:
             max_new_tokens=20, do_sample=False, use_cache=True, top_k=0, top_p=0.0, temperature=1.0, eos_token_id=eos,
             pad_token_id=_get(config, "pad_token_id"))
         self.cache_headroom = 4096          # rows a forward(use_cache=True) prefill leaves for generated tokens (generate() sizes it exactly)
+        self.device_select = True           # penalty / sampling on the device (ops.select_token); False or VITA_DEVICE_SELECT=0: _sample_strategy
 
     # -- construction ---------------------------------------------------------------------------------
     @classmethod
@@ -253,31 +306,64 @@ class LongVITAForCausalLM:
             raise ValueError("generate(inputs=[1, S] token ids) — the Long-VITA path runs batch 1")
         gc = generation_config or self.generation_config
         n_new = max_new_tokens if max_new_tokens is not None else (_get(gc, "max_new_tokens") or 20)
-        do_sample = _get(gc, "do_sample", False) if do_sample is None else do_sample
+        penalty, do_sample, temperature, top_k, top_p = selection_params(gc, do_sample)
         eos = eos_token_id if eos_token_id is not None else _get(gc, "eos_token_id")
         eos = set() if eos is None else set(eos) if isinstance(eos, (list, tuple, set)) else {int(eos)}
         ids = ids.to(self.device)
         s = ids.shape[1]
+        select = None
+        if penalty != 1.0 or do_sample:
+            if self.device_select and os.environ.get("VITA_DEVICE_SELECT", "1") != "0":
+                select = self._device_selector(ids, n_new, penalty, do_sample, temperature, top_k, top_p)
+            elif penalty != 1.0:
+                raise NotImplementedError("repetition_penalty needs the device selection (model.device_select / VITA_DEVICE_SELECT)")
+        kw = dict(do_sample=do_sample, top_k=top_k if do_sample else 0, top_p=top_p if do_sample else 0.0, temperature=temperature)
         if past_key_values is not None or return_dict_in_generate:
-            return self._generate_cached(ids, images, image_indices, past_key_values, n_new, eos, bool(do_sample), gc, return_dict_in_generate)
+            return self._generate_cached(ids, images, image_indices, past_key_values, n_new, eos, kw, select, return_dict_in_generate)
         pad = _get(gc, "pad_token_id")
         tokens = torch.full((1, s + n_new), 0 if pad is None else int(pad), dtype=torch.long, device=self.device)
         tokens[:, :s] = ids
         lengths = torch.tensor([s], dtype=torch.long, device=self.device)
         out = tokens[:, :s]
         loop = generation.generate_tokens_probs_and_return_on_first_stage(
-            self.model, tokens, lengths, do_sample=bool(do_sample), top_k=int(_get(gc, "top_k", 0) or 0) if do_sample else 0,
-            top_p=float(_get(gc, "top_p", 0.0) or 0.0) if do_sample else 0.0, temperature=float(_get(gc, "temperature", 1.0) or 1.0),
-            external_inputs=self._external_inputs(images, image_indices), use_kv_cache=bool(_get(gc, "use_cache", True)), logit_mask=True,
-            termination_id=None)
+            self.model, tokens, lengths, external_inputs=self._external_inputs(images, image_indices),
+            use_kv_cache=bool(_get(gc, "use_cache", True)), logit_mask=True, termination_id=None,
+            token_selector=None if select is None else (lambda logits, context_length: select(logits)), **kw)
         for out, _, _ in loop:
             if int(out[0, -1]) in eos:
                 break
         return out.clone()
 
-    def _generate_cached(self, ids, images, image_indices, cache, n_new, eos, do_sample, gc, return_dict):
+    def _device_selector(self, ids, n_new, penalty, do_sample, temperature, top_k, top_p):
+        """The per-token choice on the device.  The byte map of tokens already in the row starts from the WHOLE `ids` (the prompt with its
+        image placeholders and every earlier turn: what transformers hands its processors as input_ids) and every chosen token is marked
+        by the kernel itself.  All uniforms are drawn up front (torch.manual_seed reproduces a run) and, under context parallelism
+        over torch.distributed, taken from the first rank of the CP group, so that every rank chooses the same token.  CP ranks
+        simulated as threads of one process have no process group to share them through: sampling there raises (greedy, with or
+        without a penalty, needs no uniforms and runs)."""
+        from . import parallel_state as mpu
+        seen = torch.zeros(1, self.model.cfg.vocab, dtype=torch.uint8, device=self.device)
+        ops.token_seen_mark_(seen, ids)
+        u = None
+        if do_sample:
+            u = torch.rand(max(n_new, 1), device=self.device)
+            if mpu.get_context_parallel_world_size() > 1 and not torch.distributed.is_initialized():
+                raise NotImplementedError("sampling under context parallelism needs torch.distributed to share the uniforms between the ranks")
+            if mpu.get_context_parallel_world_size() > 1:
+                group = mpu.get_context_parallel_group()
+                torch.distributed.broadcast(u, src=torch.distributed.get_global_rank(group, 0) if group is not None else 0, group=group)
+        step = [0]
+
+        def select(logits):                              # [1, V] bf16 -> [1] int64
+            j = step[0]
+            step[0] += 1
+            return ops.select_token(logits, seen=seen, repetition_penalty=penalty, do_sample=do_sample, temperature=temperature,
+                                    top_k=top_k, top_p=top_p, u=u[j:j + 1] if do_sample else None, mark_chosen=True)
+        return select
+
+    def _generate_cached(self, ids, images, image_indices, cache, n_new, eos, kw, select, return_dict):
         """The decode loop over forward(past_key_values=): the uncached part of `ids` in one call (a prefill without a cache, an extend
-        step behind one), then single-token steps; sampling and the stopping rule are the loop's above."""
+        step behind one), then single-token steps; the token choice (`select`: the device selector, or None) and the stopping rule are the loop's above."""
         s = ids.shape[1]
         if cache is not None and not isinstance(cache, HipCache):
             raise TypeError("past_key_values must come from this model's own forward(use_cache=True) / generate(return_dict_in_generate=True)")
@@ -290,11 +376,9 @@ class LongVITAForCausalLM:
         else:
             out = self.forward(input_ids=ids, images=images, image_indices=image_indices, use_cache=True, num_logits_to_keep=1)
         cache = out.past_key_values
-        kw = dict(do_sample=do_sample, top_k=int(_get(gc, "top_k", 0) or 0) if do_sample else 0,
-                  top_p=float(_get(gc, "top_p", 0.0) or 0.0) if do_sample else 0.0, temperature=float(_get(gc, "temperature", 1.0) or 1.0))
         seq = ids
         for j in range(n_new):
-            _, tok = generation._sample_strategy(out.logits[:, -1, :], **kw)
+            tok = select(out.logits[:, -1, :]) if select is not None else generation._sample_strategy(out.logits[:, -1, :], **kw)[1]
             seq = torch.cat([seq, tok.view(1, 1)], dim=1)
             if int(tok[0]) in eos or j + 1 == n_new:
                 break

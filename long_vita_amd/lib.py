@@ -149,6 +149,9 @@ PROTOTYPES = {
     "vita_layernorm_fwd": (_i, [_p, _p, _p, _p, _l, _i, _f, _p]),
     "vita_logit_postprocess": (_i, [_p, _l, _l, _l, _f, _f, _p]),
     "vita_logit_postprocess_bwd": (_i, [_p, _l, _p, _l, _l, _l, _f, _f, _p]),
+    "vita_token_seen_mark": (_i, [_p, _l, _p, _l, _p, _p]),
+    "vita_select_token_workspace_bytes": (_l, [_l, _l]),
+    "vita_select_token": (_i, [_p, _l, _l, _l, _p, _f, _i, _f, _i, _f, _p, _p, _p, _i, _p, _l, _p]),
     "vita_rope_table": (_i, [_p, _p, _p, _p, _l, _i, _p]),
     "vita_rope_cos_sin": (_i, [_p, _l, _p, _p, _l, _i, _p]),
     "vita_rope_apply": (_i, [_p, _l, _i, _i, _l, _l, _p, _p, _i, _p]),

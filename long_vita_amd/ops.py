@@ -1159,6 +1159,52 @@ def logit_postprocess_bwd_(y: torch.Tensor, grad: torch.Tensor, multiplier_scale
     return grad
 
 
+def token_seen_mark_(seen: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """seen[ids[i]] = 1 on one row of the byte map `seen` ([V] or [1, V] uint8) that select_token reads; ids int64, any shape."""
+    if seen.dtype != torch.uint8 or not seen.is_contiguous() or seen.numel() != seen.shape[-1]:
+        raise ValueError("seen must be one contiguous row of uint8")
+    if ids.dtype != torch.int64:
+        raise ValueError("ids must be int64")
+    ids = ids.reshape(-1).contiguous()
+    if ids.numel() == 0:
+        return seen
+    flag = _err_flag(seen.device)
+    _L.check(_L.load().vita_token_seen_mark(_dev(ids, "ids"), ids.numel(), _dev(seen, "seen"), seen.shape[-1], _dev(flag, "flag"),
+                                            _stream()), "vita_token_seen_mark")
+    if int(flag.item()):
+        raise IndexError("vita_token_seen_mark: token id out of range")
+    return seen
+
+
+def select_token(logits: torch.Tensor, *, seen: Optional[torch.Tensor] = None, repetition_penalty: float = 1.0, do_sample: bool = False,
+                 temperature: float = 1.0, top_k: int = 0, top_p: float = 0.0, u: Optional[torch.Tensor] = None,
+                 mark_chosen: bool = False, return_kept: bool = False):
+    """The next token of every row of bf16 logits [rows, V], chosen on the device (include/vita_hip.h: vita_select_token): the
+    repetition penalty on the ids set in the byte map `seen` [rows, V], then the arg-max, or temperature / top-k / top-p sampling with
+    the uniforms `u` [rows] (fp32, device).  mark_chosen sets the chosen id in `seen`.  Returns [rows] int64 (and the number of kept
+    tokens per row, int32, with return_kept).  Nothing here synchronises with the host."""
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be [rows, V] with unit column stride")
+    rows, cols = logits.shape
+    ptr = _dev(logits, "logits", BF16)
+    if seen is not None and (seen.dtype != torch.uint8 or tuple(seen.shape) != (rows, cols) or not seen.is_contiguous()):
+        raise ValueError("seen must be contiguous uint8 [rows, V]")
+    if do_sample and (u is None or u.dtype != torch.float32 or u.numel() != rows or not u.is_contiguous()):
+        raise ValueError("do_sample needs u: contiguous fp32 [rows] uniforms in [0, 1)")
+    h = _L.load()
+    token = torch.empty(rows, dtype=torch.int64, device=logits.device)
+    kept = torch.empty(rows, dtype=torch.int32, device=logits.device) if return_kept else None
+    if rows == 0:
+        return (token, kept) if return_kept else token
+    nbytes = h.vita_select_token_workspace_bytes(rows, cols)
+    ws = _workspace(nbytes, logits.device)
+    _L.check(h.vita_select_token(ptr, logits.stride(0) if rows > 1 else max(logits.stride(0), cols), rows, cols, _opt(seen, "seen"),
+                                 float(repetition_penalty), int(bool(do_sample)), float(temperature), int(top_k), float(top_p),
+                                 _opt(u, "u") if do_sample else None, _dev(token, "token"), _opt(kept, "kept"), int(bool(mark_chosen)),
+                                 _dev(ws, "workspace"), max(nbytes, 4), _stream()), "vita_select_token")
+    return (token, kept) if return_kept else token
+
+
 def add(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = bf16(a + b) (out may alias a): one pass, no copy of either operand."""
     if a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous():
