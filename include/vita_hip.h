@@ -643,6 +643,49 @@ int vita_decode_attn_merge(const void* part_m, const void* part_l, const void* p
                            int64_t part_ml_stride, int64_t part_o_stride, int heads, int head_dim, void* out_m, void* out_l, void* out_o,
                            void* out_bf16, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Beam search on a shared-prefix KV cache (CP = 1, TP = 1, 2 .. 8 beams).  Replaces the per-step work of
+ * beam_search_and_return_on_first_stage, M/inference/text_generation/generation.py:283-471, which repeats the prompt
+ * beam_size times, prefills the copies and keeps one cache per copy: here the prompt is prefilled and cached once, the
+ * weights and the prompt's K / V are streamed once per step for all beams, and reordering the beams moves no K / V.
+ *
+ * vita_gemv_rows_bf16: y[b][N] = epilogue(W[N,K] . norm?(x[b][K])) for b < rows <= 8 (x, y, R through their row strides
+ *   ldx, ldy, ldr in elements); every weight row is read once for all input rows.  The epilogues of vita_gemv_bf16; bias per
+ *   output, residual R per row.  gamma != NULL: x[b] is RMS-normalised first (gamma [K], eps).  Row b has the bits of
+ *   vita_gemv_bf16 on row b, with gamma of vita_rmsnorm_fwd followed by vita_gemv_bf16.  rows > 8: VITA_ERR_UNSUPPORTED.
+ * vita_beam_attn_fwd: the contexts out [n_beams][n_q_heads][128] (bf16, dense) of the beams' query rows (row b at
+ *   q + b * q_row_stride, head j of kv group g at + g * q_group_stride + j * q_head_stride: read in place from the mixed QKV rows).
+ *   Beam b sees the prefix rows [0, prefix_len) of k_cache / v_cache (the cache shard of the prompt, strides as for
+ *   vita_flash_attn_extend_fwd; read once per kv group for all beams; rows behind prefix_len are never read) and its own
+ *   generated tokens in the tail caches k_tail / v_tail [tail_cap][n_beams][n_kv_heads][128] (dense): the key of step s < n_gen
+ *   is row s * n_beams + ancestry[b * tail_cap + s] (int32, device).  Every table entry is clamped into [0, n_beams) before it
+ *   forms an address; steps >= n_gen and slots no beam names are never read.  The prefix pass (key splits), the tail pass and
+ *   one merge exchange un-normalised fp32 partials through the workspace (vita_beam_attn_workspace_bytes, 16-byte aligned);
+ *   no intermediate context is rounded to bf16.  n_q_heads / n_kv_heads <= 8, head_dim 128.
+ * vita_beam_candidates: bf16 logits [rows][ld] (cols valid columns), fp32 beam_scores [rows]: x = logit / temperature,
+ *   score = x - max - log(sum exp(x - max)) + beam_scores[row] in fp32; idx_out / score_out [n_out] = the n_out best of all
+ *   rows * cols, as flat index row * cols + col, by descending score, equal scores by ascending flat index.  rows = 1 is the
+ *   reference's first step (:369-370, :455-456).  n_out <= 16, rows <= 16.  A temperature that is not positive and finite, or
+ *   n_out > rows * cols: VITA_ERR_INVALID_ARG; cols > 2^23: VITA_ERR_UNSUPPORTED.  Nothing is launched on a refusal.
+ * M/inference/text_generation/generation.py:283-471 */
+int vita_gemv_rows_bf16(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, void* y, int64_t ldy, int64_t N,
+                        int64_t K, int epilogue, const void* bias, const void* R, int64_t ldr, const void* gamma, float eps,
+                        void* stream);
+/* M/inference/text_generation/generation.py:283-471 */
+size_t vita_beam_attn_workspace_bytes(int n_beams, int n_q_heads, int64_t prefix_len);
+/* M/inference/text_generation/generation.py:283-471 */
+int vita_beam_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                       const void* k_cache, const void* v_cache, int64_t kv_row_stride, int64_t kv_group_stride,
+                       int64_t prefix_len, const void* k_tail, const void* v_tail, int64_t tail_cap,
+                       const int32_t* ancestry, int n_beams, int n_gen, int n_q_heads, int n_kv_heads, int head_dim,
+                       float softmax_scale, void* out, void* workspace, size_t workspace_bytes, void* stream);
+/* M/inference/text_generation/generation.py:283-471 */
+int64_t vita_beam_candidates_workspace_bytes(int64_t rows, int64_t cols);
+/* M/inference/text_generation/generation.py:283-471 */
+int vita_beam_candidates(const void* logits /* bf16 [rows, ld] */, int64_t ld, int64_t rows, int64_t cols,
+                         const float* beam_scores /* [rows] */, float temperature, int n_out, int64_t* idx_out /* [n_out] */,
+                         float* score_out /* [n_out] */, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* out[n] = bf16(a[n] + b[n]) (n % 8 == 0): the residual add that follows the tensor-parallel all-reduce of a
  * row-parallel linear's output (RowParallelLinear + bias_dropout_add, TP > 1 only; at TP = 1 the add is the GEMM's
  * RESIDUAL epilogue).

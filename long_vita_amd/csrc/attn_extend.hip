@@ -42,6 +42,7 @@ struct ExtArgs {
   int64_t q_pos0, key_pos0, key_pos_step;
   int n_splits, tiles_per_split;
   int quant_m;                   // running max kept on integers (log2 domain): see sm_pv_phase
+  int partial_out;               // write the fp32 partials even with one split (the beam step merges them with its tail partial)
   float scale_log2e;
 };
 
@@ -292,7 +293,7 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
   const float l_tot = swap32_sum(l_run);
   if (!live) return;
   const int head = kvh * G + my_hq;
-  if (p.n_splits == 1) {
+  if (p.n_splits == 1 && !p.partial_out) {
     const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
     bf16_t* op = p.o + (int64_t)my_row * p.o_rs + (int64_t)head * p.o_hs;
 #pragma unroll
@@ -372,6 +373,158 @@ int extend_splits(int64_t t, int n_q_heads, int64_t n_keys, bool allow_override 
 
 bool extend_shape_ok(int64_t t, int n_q_heads, int64_t n_keys) { return t > 0 && n_q_heads > 0 && n_keys > 0; }
 
+// ---- beam search (M/inference/text_generation/generation.py:283-471): the B beams of one request share the prompt --------------------
+// Query row b = beam b.  The prefix rows [0, L) of the cache shard are common to all beams: flash_extend_kernel<true> runs with t = B,
+// n_full = n_keys = L — every key visible to every row, the (beam, head) pairs of a kv group stacked on the MFMA rows — so a workgroup
+// reads each prefix K / V tile once for all beams, and leaves its fp32 partials.  A beam's own generated tokens live in the tail cache
+// [tail_cap][B][kv groups][128]: step s of slot j is row s * B + j, and beam b's key of step s is slot anc[b][s].  beam_tail_kernel
+// (VALU, decode_attn_partial_kernel's lane layout: 16 lanes per 256-byte row, 4 rows per wave instruction, 4 row loads in flight)
+// gives one workgroup to each (beam, kv group) and writes one more partial, part index n_splits; extend_merge_kernel folds all of them.
+// Every table entry is clamped into [0, B) before it forms an address.
+constexpr int kBeamMax = 8;
+constexpr int kBeamMaxSplits = kMaxSplits - 1;          // extend_merge_kernel: one lane per part, the tail partial is one of them
+
+template <int QPG>
+__global__ __launch_bounds__(256) void beam_tail_kernel(const bf16_t* __restrict__ q, int64_t q_rs, int64_t q_gs, int64_t q_hs,
+                                                        const bf16_t* __restrict__ kt, const bf16_t* __restrict__ vt,
+                                                        const int* __restrict__ anc, int64_t tail_cap, int B, int n_gen,
+                                                        float scale_log2, float* __restrict__ pm, float* __restrict__ pl,
+                                                        float* __restrict__ po, int64_t part_base) {
+  constexpr int ITS = 4;                                  // K / V row loads in flight per lane
+  constexpr int kWaveKeys = ITS * 4;
+  __shared__ float wm[4][QPG], wl[4][QPG];
+  __shared__ float wo[4][QPG][D];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int sub = lane & 15, kq = lane >> 4;
+  const int b = blockIdx.x, g = blockIdx.y, G = gridDim.y;
+  const int64_t rec0 = part_base + (int64_t)g * QPG * B + b;          // record of head h: rec0 + h * B
+  if (n_gen <= 0) {                                       // no generated token yet: the merge's neutral element
+    if (t < QPG) { pm[rec0 + (int64_t)t * B] = -1.0e30f; pl[rec0 + (int64_t)t * B] = 0.f; }
+    if (t < D)
+      for (int h = 0; h < QPG; ++h) po[(rec0 + (int64_t)h * B) * D + t] = 0.f;
+    return;
+  }
+  unsigned qp[QPG][4];
+#pragma unroll
+  for (int h = 0; h < QPG; ++h) {
+    const u32x4 qv = *reinterpret_cast<const u32x4*>(q + b * q_rs + g * q_gs + h * q_hs + sub * 8);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) qp[h][j] = qv[j];
+  }
+  float mrun[QPG], lrun[QPG], acc[QPG][8];
+#pragma unroll
+  for (int h = 0; h < QPG; ++h) {
+    mrun[h] = -INFINITY;
+    lrun[h] = 0.f;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[h][i] = 0.f;
+  }
+  const int64_t slot_stride = (int64_t)G * D, step_stride = (int64_t)B * slot_stride;
+  const int* my_anc = anc + (int64_t)b * tail_cap;
+  const int64_t goff = (int64_t)g * D + sub * 8;
+
+  for (int key0 = wave * kWaveKeys; key0 < n_gen; key0 += 4 * kWaveKeys) {
+    u32x4 kr[ITS], vr[ITS];
+#pragma unroll
+    for (int it = 0; it < ITS; ++it) {
+      const int key = key0 + it * 4 + kq;
+      kr[it] = u32x4{0u, 0u, 0u, 0u};
+      vr[it] = u32x4{0u, 0u, 0u, 0u};
+      if (key < n_gen) {
+        int slot = my_anc[key];
+        slot = slot < 0 ? 0 : (slot >= B ? B - 1 : slot);            // a corrupt table gives wrong numbers, never a stray address
+        const int64_t off = (int64_t)key * step_stride + (int64_t)slot * slot_stride + goff;
+        kr[it] = *reinterpret_cast<const u32x4*>(kt + off);
+        vr[it] = *reinterpret_cast<const u32x4*>(vt + off);
+      }
+    }
+    float p[QPG][ITS];
+#pragma unroll
+    for (int h = 0; h < QPG; ++h) {
+      float tm = -INFINITY;
+#pragma unroll
+      for (int it = 0; it < ITS; ++it) {
+        float sv = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) sv = dot2_bf16(qp[h][j], kr[it][j], sv);
+        sv = row16_allreduce_sum(sv) * scale_log2;
+        sv = (key0 + it * 4 + kq < n_gen) ? sv : -INFINITY;
+        p[h][it] = sv;
+        tm = fmaxf(tm, sv);
+      }
+      tm = fmaxf(tm, __shfl_xor(tm, 16));
+      tm = fmaxf(tm, __shfl_xor(tm, 32));                  // finite: key0 < n_gen
+      const float mnew = fmaxf(mrun[h], tm);
+      const float alpha = __builtin_amdgcn_exp2f(mrun[h] - mnew);        // exp2(-inf) = 0 on the first tile
+      mrun[h] = mnew;
+      float ls = 0.f;
+#pragma unroll
+      for (int it = 0; it < ITS; ++it) {
+        p[h][it] = __builtin_amdgcn_exp2f(p[h][it] - mnew);
+        ls += p[h][it];
+      }
+      lrun[h] = lrun[h] * alpha + ls;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[h][i] *= alpha;
+    }
+#pragma unroll
+    for (int it = 0; it < ITS; ++it) {
+      float vf[8];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) { vf[2 * i] = bf16lo_to_f32(vr[it][i]); vf[2 * i + 1] = bf16hi_to_f32(vr[it][i]); }
+#pragma unroll
+      for (int h = 0; h < QPG; ++h)
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[h][i] += p[h][it] * vf[i];
+    }
+  }
+#pragma unroll
+  for (int h = 0; h < QPG; ++h) {
+    float l = lrun[h];
+    l += __shfl_xor(l, 16);
+    l += __shfl_xor(l, 32);
+    if (lane == 0) { wm[wave][h] = mrun[h]; wl[wave][h] = l; }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      float v = acc[h][i];
+      v += __shfl_xor(v, 16);
+      v += __shfl_xor(v, 32);
+      if (kq == 0) wo[wave][h][sub * 8 + i] = v;
+    }
+  }
+  __syncthreads();
+  if (t < D) {
+#pragma unroll
+    for (int h = 0; h < QPG; ++h) {
+      const float M = fmaxf(fmaxf(wm[0][h], wm[1][h]), fmaxf(wm[2][h], wm[3][h]));   // finite: wave 0 had a tile
+      float L = 0.f, O = 0.f;
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        const float f = (wm[w][h] == -INFINITY) ? 0.f : __builtin_amdgcn_exp2f(wm[w][h] - M);
+        L += wl[w][h] * f;
+        O += wo[w][h][t] * f;
+      }
+      po[(rec0 + (int64_t)h * B) * D + t] = O;
+      if (t == 0) { pm[rec0 + (int64_t)h * B] = M; pl[rec0 + (int64_t)h * B] = L; }
+    }
+  }
+}
+
+// key splits of the prefix pass: extend_splits' rule for t = B rows (a function of the shapes only), at most kBeamMaxSplits
+int beam_splits(int n_beams, int n_q_heads, int64_t prefix_len) {
+  int splits = extend_splits(n_beams, n_q_heads, prefix_len, false);
+  if (splits > kBeamMaxSplits) {
+    const int64_t key_tiles = (prefix_len + KVT - 1) / KVT;
+    const int64_t per = (key_tiles + kBeamMaxSplits - 1) / kBeamMaxSplits;
+    splits = (int)((key_tiles + per - 1) / per);
+  }
+  return splits;
+}
+
+bool beam_shape_ok(int n_beams, int n_q_heads, int64_t prefix_len) {
+  return n_beams >= 1 && n_beams <= kBeamMax && n_q_heads > 0 && prefix_len > 0 && prefix_len <= 0x7fffffffLL - 256;
+}
+
 }  // namespace
 
 extern "C" size_t vita_flash_attn_extend_workspace_bytes(int64_t t, int n_q_heads, int64_t n_keys) {
@@ -410,6 +563,7 @@ extern "C" int vita_flash_attn_extend_fwd(const vita_attn_extend_params* p, void
   const int64_t key_tiles = (p->n_keys + KVT - 1) / KVT;
   a.tiles_per_split = (int)((key_tiles + a.n_splits - 1) / a.n_splits);
   a.quant_m = extend_splits(p->t, p->n_q_heads, p->n_keys, false) > 1;      // by shape, whatever the developer switch forces
+  a.partial_out = 0;
   a.scale_log2e = p->softmax_scale * LOG2E;
   const int64_t n_rec = (int64_t)p->n_q_heads * p->t;
   a.pm = a.pl = a.po = nullptr;
@@ -436,5 +590,82 @@ extern "C" int vita_flash_attn_extend_fwd(const vita_attn_extend_params* p, void
   if (rc != VITA_OK || a.n_splits == 1) return rc;
   hipLaunchKernelGGL(extend_merge_kernel, dim3((unsigned)((n_rec + 3) / 4)), dim3(256), 0, st, a.pm, a.pl, a.po, a.n_splits, n_rec, a.t,
                      a.o, a.o_rs, a.o_hs, a.lse);
+  return vita_check_launch();
+}
+
+extern "C" size_t vita_beam_attn_workspace_bytes(int n_beams, int n_q_heads, int64_t prefix_len) {
+  if (!beam_shape_ok(n_beams, n_q_heads, prefix_len)) return 0;
+  return (size_t)(beam_splits(n_beams, n_q_heads, prefix_len) + 1) * (size_t)n_q_heads * (size_t)n_beams * (D + 2) * sizeof(float);
+}
+
+extern "C" int vita_beam_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                                  const void* k_cache, const void* v_cache, int64_t kv_row_stride, int64_t kv_group_stride,
+                                  int64_t prefix_len, const void* k_tail, const void* v_tail, int64_t tail_cap,
+                                  const int32_t* ancestry, int n_beams, int n_gen, int n_q_heads, int n_kv_heads, int head_dim,
+                                  float softmax_scale, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!q || !k_cache || !v_cache || !out || !workspace) return VITA_ERR_INVALID_ARG;
+  if (n_beams < 1 || n_q_heads <= 0 || n_kv_heads <= 0 || n_q_heads % n_kv_heads || prefix_len <= 0) return VITA_ERR_INVALID_ARG;
+  if (n_gen < 0 || tail_cap < 0 || n_gen > tail_cap || (n_gen > 0 && (!k_tail || !v_tail || !ancestry))) return VITA_ERR_INVALID_ARG;
+  if (!(softmax_scale > 0.f) || !(softmax_scale < INFINITY) || kv_row_stride <= 0) return VITA_ERR_INVALID_ARG;
+  const int qpg = n_q_heads / n_kv_heads;
+  if (head_dim != D || qpg > 8 || !beam_shape_ok(n_beams, n_q_heads, prefix_len)) return VITA_ERR_UNSUPPORTED;
+  const int64_t strides[] = {q_row_stride, q_group_stride, q_head_stride, kv_row_stride, kv_group_stride};
+  for (int64_t s : strides)
+    if (s & 7) return VITA_ERR_UNSUPPORTED;            // 16-byte vector loads / LDS-DMA pieces
+  if (kv_row_stride * KVT > 0x7fffffffLL) return VITA_ERR_UNSUPPORTED;   // 32-bit lane offsets inside a tile
+  const uintptr_t bases = (uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out | (uintptr_t)k_tail |
+                          (uintptr_t)v_tail | (uintptr_t)workspace;
+  if (bases & 15) return VITA_ERR_UNSUPPORTED;
+  if ((uintptr_t)ancestry & 3) return VITA_ERR_UNSUPPORTED;
+
+  ExtArgs a;
+  a.q = (const bf16_t*)q; a.q_rs = q_row_stride; a.q_gs = q_group_stride; a.q_hs = q_head_stride;
+  a.k = (const bf16_t*)k_cache; a.v = (const bf16_t*)v_cache; a.kv_rs = kv_row_stride; a.kv_gs = kv_group_stride;
+  a.o = (bf16_t*)out; a.o_rs = (int64_t)n_q_heads * D; a.o_hs = D;
+  a.lse = nullptr;
+  a.t = n_beams; a.G = qpg; a.n_kv_heads = n_kv_heads;
+  a.n_q_tiles = 1;                                              // B * qpg <= 64 stacked rows: one query tile
+  a.n_keys = (int)prefix_len; a.n_full = (int)prefix_len;       // every prefix key is visible to every beam
+  a.q_pos0 = 0; a.key_pos0 = 0; a.key_pos_step = 1;
+  a.n_splits = beam_splits(n_beams, n_q_heads, prefix_len);
+  const int64_t key_tiles = (prefix_len + KVT - 1) / KVT;
+  a.tiles_per_split = (int)((key_tiles + a.n_splits - 1) / a.n_splits);
+  a.quant_m = 1;                                                // the partials are always merged: see sm_pv_phase
+  a.partial_out = 1;
+  a.scale_log2e = softmax_scale * LOG2E;
+  const int64_t n_rec = (int64_t)n_q_heads * n_beams;
+  const int n_parts = a.n_splits + 1;
+  const size_t need = (size_t)n_parts * (size_t)n_rec * (D + 2) * sizeof(float);
+  if (workspace_bytes < need) return VITA_ERR_INVALID_ARG;
+  a.po = (float*)workspace;                                     // [parts][heads][B][128], then m and l [parts][heads][B]
+  a.pm = a.po + (int64_t)n_parts * n_rec * D;
+  a.pl = a.pm + (int64_t)n_parts * n_rec;
+
+  constexpr int lds = 2 * 2 * KVT * D * 2;
+  static std::atomic<unsigned long long> attr_set{0};
+  vita_device_once(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_extend_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  });
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(flash_extend_kernel<true>, dim3((unsigned)(n_kv_heads * a.n_splits)), dim3(512), lds, st, a);
+  int rc = vita_check_launch();
+  if (rc != VITA_OK) return rc;
+  const dim3 tgrid((unsigned)n_beams, (unsigned)n_kv_heads);
+  const float sl2 = softmax_scale * LOG2E;
+  const int64_t part_base = (int64_t)a.n_splits * n_rec;
+#define VITA_BEAM_TAIL(Q)                                                                                                         \
+  case Q:                                                                                                                         \
+    hipLaunchKernelGGL(beam_tail_kernel<Q>, tgrid, dim3(256), 0, st, a.q, a.q_rs, a.q_gs, a.q_hs, (const bf16_t*)k_tail,           \
+                       (const bf16_t*)v_tail, (const int*)ancestry, tail_cap, n_beams, n_gen, sl2, a.pm, a.pl, a.po, part_base);  \
+    break;
+  switch (qpg) {
+    VITA_BEAM_TAIL(1) VITA_BEAM_TAIL(2) VITA_BEAM_TAIL(3) VITA_BEAM_TAIL(4) VITA_BEAM_TAIL(5) VITA_BEAM_TAIL(6) VITA_BEAM_TAIL(7)
+    VITA_BEAM_TAIL(8)
+  }
+#undef VITA_BEAM_TAIL
+  rc = vita_check_launch();
+  if (rc != VITA_OK) return rc;
+  hipLaunchKernelGGL(extend_merge_kernel, dim3((unsigned)((n_rec + 3) / 4)), dim3(256), 0, st, a.pm, a.pl, a.po, n_parts, n_rec,
+                     a.t, a.o, a.o_rs, a.o_hs, (float*)nullptr);
   return vita_check_launch();
 }

@@ -21,11 +21,6 @@ __device__ __forceinline__ float dot8(const u32x4 a, const u32x4 b) {
   return s;
 }
 
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float dot2_bf16(unsigned a, unsigned b, float c) {      // a.lo*b.lo + a.hi*b.hi + c, fp32
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
-}
-
 constexpr int kGemvRows = 1;
 
 // ---- y[N] = epilogue(W[N,K] . norm(x)[K]) : one wave per output, 16-byte pieces of the W row per lane ----
@@ -101,6 +96,119 @@ void launch_gemv(const void* x, const void* W, int64_t ldw, void* y, int64_t N, 
                      (const bf16_t*)gamma, eps);
 }
 
+// ---- y[b][N] = epilogue(W[N,K] . norm(x[b])[K]) for b < rows <= 8: the beam-search step (generation.py:283-471) -----------------
+// One wave owns NOUT outputs and reads each of their weight rows ONCE for all input rows.  Every (row, output) pair keeps an
+// accumulator of its own that walks K exactly as gemv_kernel does — the same per-lane stride, dot8, wave_reduce_sum and rounding
+// chain — so row b has the bits of vita_gemv_bf16 on row b.  NORM: the sum of squares is added in vita_rmsnorm_fwd's order (lane
+// stride 64 over the 16-byte vectors, pair by pair), so the normalised row has the bits of vita_rmsnorm_fwd.  R = rows rounded up
+// to 2, 4 or 8: the surplus rows recompute row rows - 1 and are not stored.
+template <int EPI, bool NORM, int R>
+__global__ __launch_bounds__(256) void gemv_rows_kernel(const bf16_t* __restrict__ x, int64_t ldx, int rows,
+                                                        const bf16_t* __restrict__ W, int64_t ldw, bf16_t* __restrict__ y,
+                                                        int64_t ldy, int64_t N, int64_t K, const bf16_t* __restrict__ bias,
+                                                        const bf16_t* __restrict__ Res, int64_t ldr,
+                                                        const bf16_t* __restrict__ gamma, float eps) {
+  constexpr int NOUT = (EPI == VITA_EPI_SWIGLU || R == 8) ? 2 : 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t n0 = ((int64_t)blockIdx.x * 4 + wave) * NOUT;
+  if (n0 >= N) return;
+  const int nvec = (int)(K >> 3);
+  const u32x4* xr[R];
+#pragma unroll
+  for (int b = 0; b < R; ++b) xr[b] = reinterpret_cast<const u32x4*>(x + (int64_t)(b < rows ? b : rows - 1) * ldx);
+  const u32x4* gr = reinterpret_cast<const u32x4*>(gamma);
+  float rstd[R];
+#pragma unroll
+  for (int b = 0; b < R; ++b) rstd[b] = 1.f;
+  if (NORM) {
+#pragma unroll
+    for (int b = 0; b < R; ++b) {
+      float ss = 0.f;
+      for (int v = lane; v < nvec; v += 64) {
+        const u32x4 xv = xr[b][v];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float a = bf16lo_to_f32(xv[j]), c = bf16hi_to_f32(xv[j]);
+          ss += a * a + c * c;
+        }
+      }
+      ss = wave_reduce_sum(ss);
+      rstd[b] = rsqrtf(ss / (float)(int)K + eps);
+    }
+  }
+  const u32x4* w0[NOUT];
+  const u32x4* w1[NOUT];
+  float a0[NOUT][R], a1[NOUT][R];
+#pragma unroll
+  for (int r = 0; r < NOUT; ++r) {
+    const int64_t n = (n0 + r < N) ? n0 + r : N - 1;                          // clamp: tail outputs recompute output N-1
+    w0[r] = reinterpret_cast<const u32x4*>(W + n * ldw);
+    w1[r] = reinterpret_cast<const u32x4*>(W + (n + N) * ldw);                // SWIGLU: the "up" row
+#pragma unroll
+    for (int b = 0; b < R; ++b) { a0[r][b] = 0.f; a1[r][b] = 0.f; }
+  }
+#pragma unroll 2
+  for (int v = lane; v < nvec; v += 64) {
+    u32x4 xv[R];
+    u32x4 gv = u32x4{0u, 0u, 0u, 0u};
+    if (NORM) gv = gr[v];
+#pragma unroll
+    for (int b = 0; b < R; ++b) {
+      xv[b] = xr[b][v];
+      if (NORM) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          xv[b][j] = pack_bf16x2(bf16_round(bf16lo_to_f32(xv[b][j]) * rstd[b]) * bf16lo_to_f32(gv[j]),
+                                 bf16_round(bf16hi_to_f32(xv[b][j]) * rstd[b]) * bf16hi_to_f32(gv[j]));
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < NOUT; ++r) {
+      const u32x4 wv0 = w0[r][v];
+      u32x4 wv1 = wv0;
+      if (EPI == VITA_EPI_SWIGLU) wv1 = w1[r][v];
+#pragma unroll
+      for (int b = 0; b < R; ++b) {
+        a0[r][b] += dot8(xv[b], wv0);
+        if (EPI == VITA_EPI_SWIGLU) a1[r][b] += dot8(xv[b], wv1);
+      }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < NOUT; ++r) {
+#pragma unroll
+    for (int b = 0; b < R; ++b) {
+      const float s0 = wave_reduce_sum(a0[r][b]);
+      const float s1 = (EPI == VITA_EPI_SWIGLU) ? wave_reduce_sum(a1[r][b]) : 0.f;
+      const int64_t n = n0 + r;
+      if (lane != 0 || n >= N || b >= rows) continue;
+      float o = s0;
+      if (EPI == VITA_EPI_BIAS) o += bf16_to_f32(bias[n]);
+      if (EPI == VITA_EPI_RESIDUAL) o = bf16_round(o) + bf16_to_f32(Res[(int64_t)b * ldr + n]);
+      if (EPI == VITA_EPI_SWIGLU) {                     // same rounding chain as the GEMM epilogue
+        const float g = bf16_round(s0), u = bf16_round(s1);
+        o = bf16_round(g / (1.0f + __expf(-g))) * u;
+      }
+      y[(int64_t)b * ldy + n] = f32_to_bf16(o);
+    }
+  }
+}
+
+template <int EPI, bool NORM>
+void launch_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, void* y, int64_t ldy, int64_t N, int64_t K,
+                      const void* bias, const void* R, int64_t ldr, const void* gamma, float eps, hipStream_t st) {
+#define VITA_GEMV_ROWS(RR)                                                                                                      \
+  {                                                                                                                             \
+    constexpr int NOUT = (EPI == VITA_EPI_SWIGLU || RR == 8) ? 2 : 4;                                                           \
+    const int64_t waves = (N + NOUT - 1) / NOUT;                                                                                \
+    hipLaunchKernelGGL((gemv_rows_kernel<EPI, NORM, RR>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, (const bf16_t*)x, \
+                       ldx, rows, (const bf16_t*)W, ldw, (bf16_t*)y, ldy, N, K, (const bf16_t*)bias, (const bf16_t*)R, ldr,     \
+                       (const bf16_t*)gamma, eps);                                                                              \
+  }
+  if (rows <= 2) VITA_GEMV_ROWS(2) else if (rows <= 4) VITA_GEMV_ROWS(4) else VITA_GEMV_ROWS(8)
+#undef VITA_GEMV_ROWS
+}
+
 // ---- RoPE of the new token's q and k heads (in place in the mixed qkv row) + append of its K / V to the cache ----
 __global__ __launch_bounds__(256) void rope_append_kernel(bf16_t* __restrict__ mixed, int groups, int qpg, int head_dim,
                                                           const bf16_t* __restrict__ cos_tab,
@@ -138,19 +246,6 @@ __global__ __launch_bounds__(256) void rope_append_kernel(bf16_t* __restrict__ m
 //   16 lanes — exactly the lanes that need p for their 8 output dims in P.V, so scores never leave
 //   registers.  The waves' (m, l, O) are merged through LDS once at the end.
 constexpr int kDecKeys = 128;        // key granularity of a split (host side: ops.DECODE_KEYS_PER_TILE)
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-  const int r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false);
-  return v + __int_as_float(r);
-}
-__device__ __forceinline__ float row16_allreduce_sum(float v) {   // row_ror:8,4,2,1 inside each 16-lane row
-  v = dpp_add<0x128>(v);
-  v = dpp_add<0x124>(v);
-  v = dpp_add<0x122>(v);
-  v = dpp_add<0x121>(v);
-  return v;
-}
 
 template <int QPG>
 __global__ __launch_bounds__(256, 2) void decode_attn_partial_kernel(
@@ -349,6 +444,28 @@ extern "C" int vita_gemv_bf16(const void* x, const void* W, int64_t ldw, void* y
     case VITA_EPI_SWIGLU: launch_gemv<VITA_EPI_SWIGLU, false>(x, W, ldw, y, N, K, bias, R, nullptr, 0.f, st); break;
     default: return VITA_ERR_UNSUPPORTED;
   }
+  return vita_check_launch();
+}
+
+extern "C" int vita_gemv_rows_bf16(const void* x, int64_t ldx, int rows, const void* W, int64_t ldw, void* y, int64_t ldy, int64_t N,
+                                   int64_t K, int epilogue, const void* bias, const void* R, int64_t ldr, const void* gamma,
+                                   float eps, void* stream) {
+  if (!x || !W || !y || N <= 0 || K <= 0 || rows <= 0) return VITA_ERR_INVALID_ARG;
+  if (rows > 8 || (K & 7) || (ldw & 7) || (ldx & 7) || ldx < K || ldy < N) return VITA_ERR_UNSUPPORTED;
+  if ((epilogue == VITA_EPI_BIAS && !bias) || (epilogue == VITA_EPI_RESIDUAL && (!R || ldr < N))) return VITA_ERR_INVALID_ARG;
+  if (gamma && !(eps >= 0.f)) return VITA_ERR_INVALID_ARG;
+  if (((uintptr_t)x | (uintptr_t)W | (uintptr_t)gamma) & 15) return VITA_ERR_UNSUPPORTED;      // 16-byte vector loads
+  hipStream_t st = (hipStream_t)stream;
+#define VITA_GR(E)                                                                                         \
+  case E:                                                                                                  \
+    if (gamma) launch_gemv_rows<E, true>(x, ldx, rows, W, ldw, y, ldy, N, K, bias, R, ldr, gamma, eps, st); \
+    else launch_gemv_rows<E, false>(x, ldx, rows, W, ldw, y, ldy, N, K, bias, R, ldr, nullptr, 0.f, st);    \
+    break;
+  switch (epilogue) {
+    VITA_GR(VITA_EPI_NONE) VITA_GR(VITA_EPI_BIAS) VITA_GR(VITA_EPI_RESIDUAL) VITA_GR(VITA_EPI_SWIGLU)
+    default: return VITA_ERR_UNSUPPORTED;
+  }
+#undef VITA_GR
   return vita_check_launch();
 }
 

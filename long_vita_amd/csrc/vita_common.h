@@ -71,6 +71,24 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* red) {
   return t;
 }
 
+// ---- the VALU attention kernels' q.k (decode.hip, the beam tail of attn_extend.hip): 16 lanes share one 256-byte K row -------------
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float dot2_bf16(unsigned a, unsigned b, float c) {      // a.lo*b.lo + a.hi*b.hi + c, fp32
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
+}
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+  const int r = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false);
+  return v + __int_as_float(r);
+}
+__device__ __forceinline__ float row16_allreduce_sum(float v) {   // row_ror:8,4,2,1 inside each 16-lane row
+  v = dpp_add<0x128>(v);
+  v = dpp_add<0x124>(v);
+  v = dpp_add<0x122>(v);
+  v = dpp_add<0x121>(v);
+  return v;
+}
+
 // RoPE (non-interleaved halves), bf16 rounding chain of rotary_pos_embedding.py:200-203 — shared by rope.hip and decode.hip
 // rotate one pair of 8-wide vectors (x1 = first half, x2 = second half) with cos/sin vectors.
 // ---- store of one 32 x 32 accumulator block of a "row per lane" epilogue (attention O, dQ, dK, dV) --------------------------------------

@@ -7,6 +7,7 @@ which IS the measured unit of the prefill metric).
   sync_output (all-gather of the masked logits + un-zig-zag)          :542-566
   last-token pick                                                     :179-205
   generate_tokens_probs_and_return_on_first_stage (the loop itself)   :33-280
+  beam_search_and_return_on_first_stage (beam search, CP = 1 / TP = 1) :283-471
 """
 from __future__ import annotations
 
@@ -222,3 +223,153 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
         if (use_eod_token_for_early_termination and termination_id is not None
                 and bool((new_sample == termination_id).all())):
             break
+
+
+# ------------------------------------------------------------------------------------------------
+# beam search on a shared-prefix KV cache (:283-471)
+# ------------------------------------------------------------------------------------------------
+BEAM_MIN, BEAM_MAX = 2, 8
+
+
+class BeamHypotheses:
+    """The finished hypotheses of one request — Megatron's beam_utils.BeamHypotheses, which :315 builds and :389-401, :431-436
+    use, restated.  A hypothesis scores sum_logprobs / length ** length_penalty.  At most num_beams are kept: one more is taken
+    while there is room or when it beats the worst kept score, and the worst one then leaves; worst_score follows what is kept.
+    is_done: the set is full and no open beam can still beat its worst member — the best open sum of log-probs, scored at the
+    current length, is not above worst_score."""
+
+    def __init__(self, num_beams: int, length_penalty: float = 1.0, early_stopping: bool = False):
+        self.num_beams, self.length_penalty, self.early_stopping = num_beams, length_penalty, early_stopping
+        self.beams = []                    # (score, hypothesis)
+        self.worst_score = 1e9
+
+    def __len__(self):
+        return len(self.beams)
+
+    def add(self, hyp, sum_logprobs, length: int):
+        score = sum_logprobs / length ** self.length_penalty
+        if len(self) < self.num_beams or score > self.worst_score:
+            self.beams.append((score, hyp))
+            if len(self) > self.num_beams:
+                ranked = sorted((s, i) for i, (s, _) in enumerate(self.beams))
+                del self.beams[ranked[0][1]]
+                self.worst_score = ranked[1][0]
+            else:
+                self.worst_score = min(score, self.worst_score)
+
+    def is_done(self, best_sum_logprobs, cur_len: int) -> bool:
+        if len(self) < self.num_beams:
+            return False
+        if self.early_stopping:
+            return True
+        return self.worst_score >= best_sum_logprobs / cur_len ** self.length_penalty
+
+
+def beam_search_and_return_on_first_stage(model, tokens=None, lengths=0, beam_size=0, do_sample=False, stop_token=None,
+                                          num_return_gen=1, length_penalty=1, top_k=0, top_p=0.0, temperature=1.0, *,
+                                          termination_id=None, external_inputs=None, logit_mask=True, reference_compat=False,
+                                          max_position_embeddings=None):
+    """Generator with the reference's contract (:283-451).  `tokens` [1, S] holds the prompt (length lengths[0]) and padding; the
+    final length is S, or max_position_embeddings when that is smaller (:298-299); a prompt that leaves no room raises (:309-310).
+    Per step it yields (tokens[:num_return_gen, :ctx + 1], lengths, scores[:num_return_gen]) — the live beams, best first,
+    tokens [beam_size, S] int64, lengths [beam_size, 1], scores [beam_size, 1] fp32 sums of log-probs (:427) — and it returns
+    (tokens [n, S], lengths, scores [n]): the hypotheses sorted by their length-penalised score, n = min(num_return_gen, kept)
+    (:435-451).  args.eos_id / the tokenizer's eod (:303-306) is the keyword termination_id; stop_token is accepted and unused,
+    as in the reference.
+
+    One step (:345-407): the last position's logits, / temperature, log-softmax, + the beams' scores; the 2 * beam_size best
+    of all beam_size * vocab continuations (of row 0 alone on the first step, where every beam is the same prompt, :369-370);
+    walked best first: an end token files the beam's tokens as a hypothesis of length ctx + 1 - prompt when it ranks inside the
+    first beam_size, and is skipped otherwise; anything else becomes a live beam, until beam_size are live.  Then the is_done
+    test against the best candidate's score, the reorder of tokens and scores, and swap_key_value_dict(the beams' parents).
+    A loop that ends without is_done adds the open beams as hypotheses (:430-433).
+
+    What differs from the reference: the prompt is prefilled ONCE at batch 1 (the reference repeats it beam_size times, :326)
+    and InferenceParams.begin_beams turns that cache into the beams' shared prefix; every later step is one [beam_size, 1] call
+    of the model; the candidates come from vita_beam_candidates (no sort of the whole vocabulary) and reach the host in one
+    copy.  external_inputs feed the prefill (the reference's ForwardStep gets none here, :313).  Not built — each raises
+    NotImplementedError: do_sample=True (:462-469), the filter branch top_k > 1 and 0 < top_p <= 1 (:360-363), CP or TP > 1."""
+    from . import ops
+    from .inference_params import ForwardStep
+    if do_sample:
+        raise NotImplementedError("beam search with do_sample=True (multinomial candidates) is not built")
+    if top_k > 1 and 0.0 < top_p <= 1.0:
+        raise NotImplementedError("beam search over top-k / top-p filtered logits is not built")
+    if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1:
+        raise NotImplementedError("beam search is built for CP = 1 and TP = 1")
+    if tokens is None or tokens.dim() != 2 or tokens.size(0) != 1:
+        raise ValueError("beam search runs batch 1")                                       # :295-296
+    if not BEAM_MIN <= beam_size <= BEAM_MAX:
+        raise ValueError(f"beam_size must be {BEAM_MIN} .. {BEAM_MAX}")
+    prompt_length = int(lengths.reshape(-1)[0].item())
+    final_sequence_length = tokens.size(1)
+    if max_position_embeddings is not None:
+        final_sequence_length = min(final_sequence_length, int(max_position_embeddings))
+    if prompt_length >= final_sequence_length:
+        raise ValueError("context length + tokens_to_generate too large")                 # :309-310
+    B, dev = beam_size, tokens.device
+    forward_step = ForwardStep(model, 1, final_sequence_length, external_inputs=None)
+    ip = forward_step.inference_params
+    beam_hyp = BeamHypotheses(B, length_penalty)
+    done = False
+    with torch.no_grad():
+        tokens = tokens.repeat(B, 1)
+        lengths = lengths.reshape(-1).repeat(B, 1)
+        scores = torch.zeros(B, 1, dtype=torch.float32, device=dev)
+        position_ids = torch.arange(tokens.size(1), dtype=torch.long, device=dev)[None]
+        context_length = prompt_length
+        for context_length in range(prompt_length, final_sequence_length):
+            first = context_length == prompt_length
+            if first:                          # the prompt, once, at batch 1
+                tokens_in, pos_in = tokens[:1, :context_length], position_ids[:, :context_length]
+                ip.prefill_valid_tokens = context_length
+                ip.external_inputs = external_inputs if external_inputs else None
+                if logit_mask:
+                    ip.logit_mask, _ = build_logit_mask(tokens_in, context_length, reference_compat)
+                logits = forward_step(tokens_in, pos_in, None)
+                ip.logit_mask = None
+                ip.begin_beams(B, final_sequence_length - prompt_length, device=dev)
+            else:                              # one token per beam, all at position context_length - 1
+                logits = forward_step(tokens[:, context_length - 1: context_length],
+                                      position_ids[:, context_length - 1: context_length].expand(B, 1), None)
+            last = logits[:, -1, :]
+            if last.dtype != torch.bfloat16:
+                last = last.to(torch.bfloat16)
+            if last.stride(-1) != 1:
+                last = last.contiguous()
+            vocab_size = last.size(-1)
+            rows = last[:1] if first else last                                               # :369-372, :455-458
+            idx, val = ops.beam_candidates(rows, scores.view(-1)[: rows.size(0)].contiguous(), 2 * B, temperature)
+            both = torch.stack([idx.to(torch.float64), val.to(torch.float64)]).cpu()         # the step's one copy to the host
+            flat, best_scores = [int(v) for v in both[0].tolist()], [float(v) for v in both[1].tolist()]
+            next_beams = []                                                                  # :380-399
+            for rank, (f, beam_score) in enumerate(zip(flat, best_scores)):
+                beam_id, token_id = divmod(f, vocab_size)
+                if termination_id is not None and token_id == termination_id:
+                    if rank >= B:              # an end token outside the first beam_size candidates is not a hypothesis
+                        continue
+                    beam_hyp.add(tokens[beam_id].clone(), beam_score, context_length + 1 - prompt_length)
+                else:
+                    next_beams.append((token_id, beam_score, beam_id))
+                if len(next_beams) == B:
+                    break
+            if len(next_beams) != B:
+                raise RuntimeError("fewer live continuations than beams (the vocabulary is smaller than 2 * beam_size?)")
+            if beam_hyp.is_done(max(best_scores), context_length + 1 - prompt_length):       # :401-402
+                done = True
+            best_batches = torch.tensor([b[2] for b in next_beams], dtype=torch.long, device=dev)   # :404-407
+            tokens = tokens[best_batches, :]
+            tokens[:, context_length] = torch.tensor([b[0] for b in next_beams], dtype=torch.long, device=dev)
+            scores = torch.tensor([b[1] for b in next_beams], dtype=torch.float32, device=dev).unsqueeze(1)
+            if done:
+                break
+            ip.swap_key_value_dict(best_batches)                                             # :419-422
+            yield tokens[:num_return_gen, : context_length + 1], lengths, scores[:num_return_gen]
+        if not done:                                                                         # :430-433
+            for beam_id in range(B):
+                beam_hyp.add(tokens[beam_id].clone(), float(scores[beam_id, 0]), context_length + 1 - prompt_length)
+        ranked = sorted(beam_hyp.beams, key=lambda x: x[0], reverse=True)                    # :435-441
+        n = min(num_return_gen, len(ranked))
+        out_scores = torch.tensor([ranked[i][0] for i in range(n)], dtype=torch.float32, device=dev)
+        out_tokens = torch.stack([ranked[i][1] for i in range(n)], dim=0)
+    return out_tokens, lengths, out_scores

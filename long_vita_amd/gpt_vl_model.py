@@ -224,6 +224,8 @@ class GPTVLModel:
             if hasattr(ip, "use_kv_cache") and not ip.use_kv_cache:                                  # :285-286
                 ip = None
         if ip is not None and ip.key_value_memory_dict:
+            if getattr(ip, "beams", None) is not None:
+                return self._beam_forward(input_ids, position_ids, ip)
             return self._decode_forward(input_ids, position_ids, ip)
         if decoder_input is None:                                                         # :252-277
             if external_inputs:
@@ -557,3 +559,51 @@ class GPTVLModel:
         if bool(torch.isnan(logits.float().sum())):                                       # as the prefill (gpt_vl_model.py:393-396)
             raise ValueError("found NaN in local forward logits calculation")
         return logits.transpose(0, 1).contiguous()
+
+    def _beam_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], ip) -> torch.Tensor:
+        """One beam-search step (M/inference/text_generation/generation.py:330-345 with beam_size rows): tokens [B, 1], every row
+        at the same position, behind the prompt that was prefilled and cached ONCE (ip.begin_beams).  The weights and the prompt's
+        K / V are streamed once for all B rows: RMSNorm folded into the multi-row GEMVs, RoPE of the B rows, their K / V stored as
+        one contiguous block at tail step n_gen, ops.beam_attn over the shared prefix and each beam's own steps, then the head for
+        B rows.  CP = 1 and TP = 1; the fused C layer entries and the captured token step stay batch 1.  Returns [B, 1, vocab]."""
+        c = self.cfg
+        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1:
+            raise NotImplementedError("the beam step is built for CP = 1 and TP = 1")
+        B = ip.beams
+        if tuple(input_ids.shape) != (B, 1):
+            raise ValueError(f"the beam step takes tokens [{B}, 1]")
+        if not 1 <= B <= ops.BEAM_MAX:
+            raise ValueError(f"1 .. {ops.BEAM_MAX} beams")
+        step = ip.beam_n_gen
+        if step >= ip.beam_ancestry.shape[1]:
+            raise RuntimeError("the beams' tail cache is full (max_sequence_length reached)")
+        if position_ids is None:
+            position = torch.full((1,), ip.sequence_len_offset, dtype=torch.long, device=input_ids.device)
+        else:
+            position = position_ids.reshape(-1)[:1]
+        ip._graph = None
+        ip.consumed_tokens = 1
+        ws = self._ws.get(("beam", B))
+        if ws is None:
+            e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=input_ids.device)  # noqa: E731
+            ws = self._ws[("beam", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn)}
+        h = ops.row_gather(self.p["embed"], input_ids[:, 0].contiguous())                 # [B, hidden]
+        cos, sin = ops.rope_table(position.expand(B).contiguous(), self.rotary_pos_emb.inv_freq)
+        L = ip.beam_prefix_len
+        for li, lp in enumerate(self.p["layers"]):
+            kv, tail = ip.key_value_memory_dict[li + 1], ip.beam_tails[li + 1]
+            qkv = ops.gemv_rows(h, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], eps=c.eps)
+            ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, None, 1)
+            m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
+            tail[0, step].copy_(m4[:, :, c.qpg])
+            tail[1, step].copy_(m4[:, :, c.qpg + 1])
+            ctx = ops.beam_attn(m4[:, :, : c.qpg], kv[0], kv[1], L, tail[0], tail[1], ip.beam_ancestry, step + 1, out=ws["ctx"])
+            ops.gemv_rows(ctx.view(B, -1), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+            act = ops.gemv_rows(h, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], eps=c.eps)
+            ops.gemv_rows(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+        ip.beam_n_gen = step + 1
+        ip.decode_steps += 1
+        rows = ops.rmsnorm(h, self.p["final_ln"], c.eps)
+        logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)   # <= 16 rows: vita_gemm_skinny_bf16
+        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)   # as the token step (no-op at 0 / 0)
+        return logits.contiguous()                                                        # [B, 1, vocab]: the rows are the beams

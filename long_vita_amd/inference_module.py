@@ -227,10 +227,13 @@ def request_tensors(prompt_ids: Sequence[int], tokens_to_generate: int, tokenize
 
 def generate(model, prompt_ids: Sequence[int], tokens_to_generate: int, tokenizer, image_processor=None, *, do_sample=False,
              top_k=0, top_p=0.0, temperature=1.0, return_output_log_probs=False, use_kv_cache=True, logit_mask=True,
-             termination_id=None, reference_compat=False, per_rank_loading=True, **media):
+             termination_id=None, reference_compat=False, per_rank_loading=True, num_beams=1, length_penalty=1.0,
+             num_return_sequences=1, **media):
     """The request -> token stream chain of MegatronModuleForCausalLM.generate (module.py:270-402) for one prompt: request_tensors
     on every rank (with per_rank_loading each CP rank builds only its own frames; nothing is broadcast), then the decode loop.
-    Yields what generate_tokens_probs_and_return_on_first_stage yields."""
+    Yields what generate_tokens_probs_and_return_on_first_stage yields.  num_beams > 1 routes to the beam search instead, as
+    module.py:372-384 does (length_penalty, num_return_sequences -> num_return_gen): yields what beam_search_and_return_on_first_stage
+    yields, and the generator's return value is its sorted hypotheses."""
     from . import generation, parallel_state as mpu
     cp = mpu.get_context_parallel_world_size()
     kw = dict(media)
@@ -242,6 +245,11 @@ def generate(model, prompt_ids: Sequence[int], tokens_to_generate: int, tokenize
     tokens, lengths, ext = request_tensors(prompt_ids, tokens_to_generate, tokenizer, image_processor, **kw)
     if termination_id is None:
         termination_id = getattr(tokenizer, "eos_token_id", None)
+    if num_beams > 1:
+        return (yield from generation.beam_search_and_return_on_first_stage(
+            model, tokens=tokens, lengths=lengths, beam_size=num_beams, do_sample=do_sample, top_k=top_k, top_p=top_p,
+            temperature=temperature, length_penalty=length_penalty, num_return_gen=num_return_sequences,
+            termination_id=termination_id, external_inputs=ext, logit_mask=logit_mask, reference_compat=reference_compat))
     yield from generation.generate_tokens_probs_and_return_on_first_stage(
         model, tokens, lengths, return_output_log_probs=return_output_log_probs, do_sample=do_sample, top_k=top_k, top_p=top_p,
         temperature=temperature, external_inputs=ext, use_kv_cache=use_kv_cache, logit_mask=logit_mask,

@@ -35,9 +35,43 @@ class InferenceParams:
         self.local_len = 0                   # valid rows in this rank's shard
         self.decode_steps = 0                # generated tokens appended so far (owner = decode_steps % CP)
         self.consumed_tokens = None          # set by the model: global tokens consumed by the last forward
+        # beam state (begin_beams): None = the batch-1 path
+        self.beams = None
+        self.beam_n_gen = 0
+        self.beam_prefix_len = 0
+        self.beam_tails = {}
+        self.beam_ancestry = None
+
+    def begin_beams(self, beams: int, tail_cap: int, device=None):
+        """Turn the batch-1 cache of a prefilled prompt into the shared prefix of `beams` beams (beam search,
+        M/inference/text_generation/generation.py:283-471; CP = 1).  The shard's rows [0, local_len) stay where they are,
+        read-only and common to every beam.  The beams' own tokens go to a tail cache per layer,
+        beam_tails[layer_number] = [2, tail_cap, beams, kv_groups, head_dim]: step s of slot j.  beam_ancestry[b, s]
+        (int32, device) names the slot that holds beam b's key of step s; column s is the identity until step s has
+        been reordered.  beam_n_gen counts the steps stored."""
+        if not 1 <= beams or tail_cap < 1:
+            raise ValueError("begin_beams: beams >= 1 and tail_cap >= 1")
+        self.beams, self.beam_n_gen, self.beam_prefix_len = int(beams), 0, self.local_len
+        self.beam_tails = {}
+        if self.key_value_memory_dict:
+            kv = next(iter(self.key_value_memory_dict.values()))
+            device = kv.device
+            buf = torch.empty(len(self.key_value_memory_dict), 2, tail_cap, beams, kv.shape[2], kv.shape[3], dtype=kv.dtype, device=device)
+            self.beam_tails = {ln: buf[i] for i, ln in enumerate(self.key_value_memory_dict)}
+        self.beam_ancestry = torch.arange(beams, dtype=torch.int32, device=device)[:, None].repeat(1, tail_cap).contiguous()
 
     def swap_key_value_dict(self, batch_idx):
-        """Beam search reorders the batch dimension of the cache; the Long-VITA path runs batch 1."""
+        """Beam search reorders the batch dimension of the cache (generation.py:419-422).  With beam state (begin_beams) the
+        new beam j continues old beam batch_idx[j]: a row gather of the ancestry table over the steps stored so far — no K / V
+        moves.  Without it the Long-VITA path runs batch 1."""
+        if self.beams is not None:
+            if len(batch_idx) != self.beams:
+                raise ValueError(f"swap_key_value_dict: {self.beams} beam indices expected")
+            n = self.beam_n_gen
+            if n > 0:
+                idx = torch.as_tensor(batch_idx, dtype=torch.int64, device=self.beam_ancestry.device)
+                self.beam_ancestry[:, :n] = self.beam_ancestry[idx, :n]
+            return
         if len(batch_idx) != 1 or int(batch_idx[0]) != 0:
             raise NotImplementedError("the sharded cache holds batch 1")
 
@@ -48,6 +82,7 @@ class InferenceParams:
         self.prefill_valid_tokens = None
         self.local_len = 0
         self.decode_steps = 0
+        self.beams, self.beam_n_gen, self.beam_prefix_len, self.beam_tails, self.beam_ancestry = None, 0, 0, {}, None
 
 
 class ForwardStep:

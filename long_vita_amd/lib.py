@@ -236,6 +236,12 @@ PROTOTYPES = {
     "vita_cp_attn_fwd": (_i, [_p, C.POINTER(CpAttnParams), _p]),
     "vita_cp_attn_bwd": (_i, [_p, C.POINTER(CpAttnParams), _p, _p, _p, _p, _p, _p]),
     "vita_decode_attn_merge": (_i, [_p, _p, _p, _i, _l, _l, _i, _i, _p, _p, _p, _p, _p]),
+    # beam search on a shared-prefix cache (generation.py:283-471)
+    "vita_gemv_rows_bf16": (_i, [_p, _l, _i, _p, _l, _p, _l, _l, _l, _i, _p, _p, _l, _p, _f, _p]),
+    "vita_beam_attn_workspace_bytes": (C.c_size_t, [_i, _i, _l]),
+    "vita_beam_attn_fwd": (_i, [_p, _l, _l, _l, _p, _p, _l, _l, _l, _p, _p, _l, _p, _i, _i, _i, _i, _i, _f, _p, _p, C.c_size_t, _p]),
+    "vita_beam_candidates_workspace_bytes": (_l, [_l, _l]),
+    "vita_beam_candidates": (_i, [_p, _l, _l, _l, _p, _f, _i, _p, _p, _p, _l, _p]),
 }
 
 _lock = threading.Lock()

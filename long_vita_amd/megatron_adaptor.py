@@ -38,7 +38,8 @@ LanguageModelEmbedding, ColumnParallelLinear and the spec leaves are `torch.nn.M
 signatures, Parameters under Megatron's names and autograd (layers.py, language_model_embedding.py, autograd_fns.py).
 Targets of the reference that stay Megatron-resident (not arithmetic of this path): TransformerConfig (:96-97, extra
 dataclass fields), ensure_directory_exists, tokenisation, beam search, the pipelining forward steps (identical to
-upstream), parse_args, build_tokenizer.  `tests/test_cpu_host.py` checks every name registered here against the reference's own call sites
+upstream), parse_args, build_tokenizer.  Beam search has a HIP path that is opt-in: register_beam_search() below (CP = 1, TP = 1,
+no sampling); without that call it stays with the reference.  `tests/test_cpu_host.py` checks every name registered here against the reference's own call sites
 (fixture adaptor_targets.pt).
 
 Megatron-LM is not installable in the build container, so the registration is
@@ -104,6 +105,34 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
         temperature=temperature, use_eod_token_for_early_termination=use_eod_token_for_early_termination,
         external_inputs=external_inputs, use_kv_cache=bool(args.use_kv_cache), logit_mask=bool(args.logit_mask),
         termination_id=termination_id, reference_compat=not getattr(args, "vita_fix_cp_logit_block", False))
+
+
+BEAM_SEARCH_TARGET = "megatron.inference.text_generation.generation.beam_search_and_return_on_first_stage"
+
+
+def beam_search_and_return_on_first_stage(model, tokens=None, lengths=0, beam_size=0, do_sample=False, stop_token=None,
+                                          num_return_gen=1, length_penalty=1, top_k=0, top_p=0.0, temperature=1.0):
+    """The reference's signature (M/inference/text_generation/generation.py:283-291).  What it reads from Megatron's globals
+    (:292-306: args.max_position_embeddings, args.eos_id or tokenizer.eod) becomes keyword arguments of
+    long_vita_amd.generation's beam search (CP = 1, TP = 1, no sampling: it raises NotImplementedError otherwise)."""
+    from megatron.training import get_args, get_tokenizer
+
+    from . import generation
+    args = get_args()
+    termination_id = args.eos_id if hasattr(args, "eos_id") else get_tokenizer().eod
+    return generation.beam_search_and_return_on_first_stage(
+        model, tokens=tokens, lengths=lengths, beam_size=beam_size, do_sample=do_sample, stop_token=stop_token,
+        num_return_gen=num_return_gen, length_penalty=length_penalty, top_k=top_k, top_p=top_p, temperature=temperature,
+        termination_id=termination_id, logit_mask=bool(getattr(args, "logit_mask", True)),
+        reference_compat=not getattr(args, "vita_fix_cp_logit_block", False),
+        max_position_embeddings=getattr(args, "max_position_embeddings", None))
+
+
+def register_beam_search(create_dummy: bool = False) -> None:
+    """Opt in: register the HIP beam search on BEAM_SEARCH_TARGET (call before apply_patches / exe_adaptation).  It is NOT one
+    of _targets(): without this call beam search stays with the reference, whose sampling and filter branches and CP / TP > 1
+    this path does not build."""
+    aspm.register_patch(BEAM_SEARCH_TARGET, beam_search_and_return_on_first_stage, create_dummy=create_dummy)
 
 
 def _targets():

@@ -1117,6 +1117,100 @@ def decode_attn_merge(pm: torch.Tensor, pl: torch.Tensor, po: torch.Tensor, fina
     return buf
 
 
+# ------------------------------------------------------------------------------------------------
+# beam search on a shared-prefix KV cache (M/inference/text_generation/generation.py:283-471)
+# ------------------------------------------------------------------------------------------------
+BEAM_MAX = 8
+
+
+def gemv_rows(x: torch.Tensor, w: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+              residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None,
+              eps: float = 1e-6) -> torch.Tensor:
+    """y[b] = epilogue(W . norm?(x[b])) for the rows of x [rows <= 8, K]: every weight row is read once for all of them, and row b
+    has the bits of gemv(x[b]) (with gamma: of rmsnorm(x[b], gamma, eps) followed by gemv).  residual [rows, N], out [rows, N]
+    (unit inner stride; out may alias residual)."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("gemv_rows: x must be [rows, K] with a unit inner stride")
+    rows, K = x.shape
+    if w.shape[1] != K:
+        raise RuntimeError(f"supplied weight's shape is {tuple(w.shape)}, K = {K} expected")
+    N = w.shape[0] // 2 if epilogue == EPI_SWIGLU else w.shape[0]
+    y = torch.empty(rows, N, dtype=BF16, device=x.device) if out is None else out
+    if tuple(y.shape) != (rows, N) or y.stride(1) != 1:
+        raise ValueError("gemv_rows: out must be [rows, N] with a unit inner stride")
+    if residual is not None and (tuple(residual.shape) != (rows, N) or residual.stride(1) != 1):
+        raise ValueError("gemv_rows: residual must be [rows, N] with a unit inner stride")
+    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
+        raise ValueError("gemv_rows: gamma must be contiguous [K]")
+    _L.check(_L.load().vita_gemv_rows_bf16(_dev(x, "x", BF16), x.stride(0), rows, _dev(w, "w", BF16), w.stride(0), _dev(y, "out", BF16),
+                                           y.stride(0), N, K, epilogue, _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
+                                           residual.stride(0) if residual is not None else 0, _opt(gamma, "gamma", BF16), float(eps),
+                                           _stream()), "vita_gemv_rows_bf16")
+    return y
+
+
+def beam_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, prefix_len: int, k_tail: torch.Tensor,
+              v_tail: torch.Tensor, ancestry: torch.Tensor, n_gen: int, softmax_scale: Optional[float] = None,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The contexts [B, Hq, D] of B beams.  q [B, Hkv, G, D] — a view into the mixed QKV rows; k_cache / v_cache [cap, Hkv, D] views
+    whose rows [0, prefix_len) every beam sees (read once for all of them); k_tail / v_tail [tail_cap, B, Hkv, D] contiguous, the
+    beams' generated tokens: beam b's key of step s < n_gen is k_tail[s, ancestry[b, s]] (ancestry int32 [B, tail_cap] on the
+    device; entries are clamped into [0, B) by the kernel)."""
+    if q.dim() != 4 or k_cache.dim() != 3 or k_tail.dim() != 4:
+        raise ValueError("beam_attn: q [B, Hkv, G, D], caches [cap, Hkv, D], tails [tail_cap, B, Hkv, D]")
+    B, Hkv, G, D = q.shape
+    if k_cache.shape[1:] != (Hkv, D) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
+        raise ValueError("beam_attn: k / v cache views must be [cap, Hkv, D] with the same strides")
+    if q.stride(3) != 1 or k_cache.stride(2) != 1:
+        raise ValueError("head_dim must be contiguous")
+    prefix_len, n_gen = int(prefix_len), int(n_gen)
+    if prefix_len > k_cache.shape[0]:
+        raise ValueError("prefix_len exceeds the cache rows")
+    tail_cap = k_tail.shape[0]
+    if tuple(k_tail.shape) != (tail_cap, B, Hkv, D) or v_tail.shape != k_tail.shape or not k_tail.is_contiguous() or not v_tail.is_contiguous():
+        raise ValueError("beam_attn: tails must be contiguous [tail_cap, B, Hkv, D]")
+    if ancestry.dtype != torch.int32 or tuple(ancestry.shape) != (B, tail_cap) or not ancestry.is_contiguous():
+        raise ValueError("beam_attn: ancestry must be contiguous int32 [B, tail_cap]")
+    if n_gen > tail_cap:
+        raise ValueError("n_gen exceeds the tail capacity")
+    Hq = Hkv * G
+    o = torch.empty((B, Hq, D), dtype=BF16, device=q.device) if out is None else out
+    if tuple(o.shape) != (B, Hq, D) or not o.is_contiguous():
+        raise ValueError("out must be contiguous [B, Hq, D]")
+    h = _L.load()
+    nbytes = h.vita_beam_attn_workspace_bytes(B, Hq, prefix_len)
+    ws = _extend_workspace(max(nbytes, 16), q.device)
+    _L.check(h.vita_beam_attn_fwd(_dev(q, "q", BF16), q.stride(0), q.stride(1), q.stride(2), _dev(k_cache, "k_cache", BF16),
+                                  _dev(v_cache, "v_cache", BF16), k_cache.stride(0), k_cache.stride(1), prefix_len,
+                                  _dev(k_tail, "k_tail", BF16), _dev(v_tail, "v_tail", BF16), tail_cap, _dev(ancestry, "ancestry"),
+                                  B, n_gen, Hq, Hkv, D, float(softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)),
+                                  _dev(o, "out", BF16), _dev(ws, "workspace", torch.float32), nbytes, _stream()), "vita_beam_attn_fwd")
+    return o
+
+
+def beam_candidates(logits: torch.Tensor, beam_scores: torch.Tensor, n_out: int, temperature: float = 1.0, cols: Optional[int] = None):
+    """The n_out best continuations of bf16 logits [rows, ld] (cols valid columns): score = log_softmax(logits / temperature) +
+    beam_scores[row] in fp32.  Returns (flat index row * cols + col int64 [n_out], score fp32 [n_out]) on the device, by descending
+    score, equal scores by ascending index.  Nothing here synchronises with the host."""
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be [rows, V] with unit column stride")
+    rows = logits.shape[0]
+    cols = logits.shape[1] if cols is None else int(cols)
+    if cols > logits.shape[1]:
+        raise ValueError("cols exceeds the row length")
+    if beam_scores.dtype != torch.float32 or beam_scores.numel() != rows or not beam_scores.is_contiguous():
+        raise ValueError("beam_scores must be contiguous fp32 [rows]")
+    h = _L.load()
+    idx = torch.empty(n_out, dtype=torch.int64, device=logits.device)
+    score = torch.empty(n_out, dtype=torch.float32, device=logits.device)
+    nbytes = h.vita_beam_candidates_workspace_bytes(rows, cols)
+    ws = _workspace(max(nbytes, 16), logits.device)
+    _L.check(h.vita_beam_candidates(_dev(logits, "logits", BF16), max(logits.stride(0), cols), rows, cols,
+                                    _dev(beam_scores, "beam_scores"), float(temperature), int(n_out), _dev(idx, "idx"),
+                                    _dev(score, "score"), _dev(ws, "workspace"), max(nbytes, 16), _stream()), "vita_beam_candidates")
+    return idx, score
+
+
 def unpack_partials(gathered: torch.Tensor, heads: int, d: int):
     """gathered [n, H*d + 2H] fp32 (decode_attn_merge packed messages) -> strided (m, l, o) views."""
     n = gathered.shape[0]
