@@ -12,12 +12,20 @@
 //     from builtin MFMAs in VGPR form (this file is compiled with -mllvm -amdgpu-mfma-vgpr-form=1) so the softmax reads it
 //     without accumulator moves; -fno-slp-vectorize keeps the fp32 softmax math out of v_pk_* (it shares the matrix datapath)
 //   * phase 1: 32 MFMAs  S(t+1) = K(t+1) Q^T  ||  exp2 / row sum / bf16 pack of the last 8 - NF2 P fragments of tile t
-//     phase 2: 32 MFMAs  O += V(t)^T P(t)^T   ||  row maxima of tile t+1, the running-maximum decision, its first NF2 fragments
-//     the VALU work is dealt to the MFMA slots by weight; sched_barrier(0) after every slot keeps the order
-//   * LAZY running maximum: the maximum (and with it O and l) only moves when some row of the wave exceeds it by more than
-//     2^THR (THR = 8), so P <= 2^8 instead of <= 1 — bf16 / fp32 have the range, the relative rounding of P is unchanged — and
-//     the 400-instruction accumulator rescale (AGPR -> VGPR -> AGPR) leaves the steady state.  With exact maxima a 64-row
-//     wave hits it on ~20 % of the tiles of a 128K row (measured: 0.74 -> 0.90 PFLOP/s at 16K, 1.11 -> 1.19 at 128K)
+//     phase 2: 32 MFMAs  O += V(t)^T P(t)^T   ||  the first NF2 P fragments of tile t+1
+//     NF2 = 4: one exp half-unit behind every MFMA, two fma + two exp2 behind the even ones, two adds + one pack behind the odd
+//     ones; sched_barrier(0) in front of and behind every MFMA keeps the order (left alone, the scheduler hoists a slot's filler
+//     in front of its MFMA and two MFMAs issue back to back)
+//   * OPTIMISTIC running maximum (r12) on top of the LAZY one (r02: the maximum, and with it O and l, only moves when some row of
+//     the wave exceeds it by more than 2^THR, THR = 8, so P <= 2^8 instead of <= 1 — bf16 / fp32 have the range, the relative
+//     rounding of P is unchanged — and the 400-instruction accumulator rescale leaves the steady state).  Tile 0 gets its true row
+//     maxima in the prologue; from then on the steady state takes NO maxima: a tile is exponentiated against the running maximum
+//     as it stands, and ONE compare per row block and tile, on the row sum that is computed anyway, accepts it: l_tile <= 2^THR
+//     proves every p <= 2^THR, which is all the lazy rule asks.  Only a tile that fails takes its true maxima, out of line, and
+//     applies the lazy rule to them; if the maxima move, l and the accumulators are rescaled and the tile is exponentiated again.
+//     The maxima move exactly when and where they did with 32 max3 steps, two swaps and a decision on every tile: the results
+//     are bit-identical to that kernel's.  Same-box A / B against it: 128K 145.7 -> 135.0 ms, 32K 9.24 -> 8.71, 16K 2.40 -> 2.25
+//     (profiles/r12_attn_optimistic_ab.txt)
 //   * K / V tiles HBM/L2 -> LDS by LDS-DMA (buffer_load ... lds: SGPR descriptor re-based per tile + the lane's 32-bit offset,
 //     no address VALU), separate K and V rings of two 16 KiB slots, one barrier per tile; attn_tile.h's frag / tr layouts
 //     (conflict-free ds_read_b128 / ds_read_b64_tr_b16), the swizzle applied to the DMA's per-lane SOURCE address
@@ -32,32 +40,27 @@ namespace {
 
 constexpr int D = 128, KVT = 64, QTILE = 256, ROWB = D * 2, TILEB = KVT * ROWB;     // 16 KiB per K (or V) tile
 constexpr int LDS_K = 0, LDS_V = 2 * TILEB;                                         // K ring [2] | V ring [2]
-constexpr int NF2 = 3;                                                               // P fragments of tile t+1 done in phase 2
+constexpr int NF2 = 4;                                                               // P fragments of tile t+1 done in phase 2
 constexpr int THR = 8;                                                               // lazy running maximum, log2 units
+constexpr float ACCEPT_MAX = (float)(1 << THR);                                      // a lane's row sum <= 2^THR: none of its p exceeds 2^THR
 
-// ---- filler schedule: units dealt to the 32 MFMA slots of a phase by cumulative weight ---------------------------------
-// phase 2 units: 0..31 max3 steps (weight 1), 32..33 running-maximum decision (weight 6), then 8 * NF2 exp half-units
-// (half 0: two fma + two exp2, half 1: two row-sum adds + one bf16 pack); phase 1 units: 8 * (8 - NF2) exp half-units
+// ---- filler schedule: the 64 exp half-units of a tile dealt to the 2 x 32 MFMA slots by cumulative issue cost -------------------
+// half 0: two fma + two exp2 (1 + 1 + 2 + 2), half 1: two row-sum adds + one bf16 pack (3).  Phase 2 (P V of tile t) carries half-units
+// 0 .. 8 NF2 - 1 of tile t+1, phase 1 (S of tile t+1) half-units 8 NF2 .. 63 of tile t.  A unit goes to the slot its weight's midpoint
+// falls in; with NF2 = 4 that is ONE half-unit per slot, half 0 behind the even MFMAs and half 1 behind the odd ones: no gap
+// holds more than 24 cycles of VALU issue, and the gaps in front of the even MFMAs (LDS reads, DMA pieces) hold 12.
 struct SlotMap { int first[33]; };
-constexpr int unit_w2(int u) { return u < 32 ? 2 : (u < 34 ? 12 : ((u & 1) ? 6 : 8)); }
-constexpr SlotMap make_map2() {
+constexpr int half_w(int h) { return (h & 1) ? 3 : 6; }
+constexpr SlotMap make_map(int h0, int n) {
   SlotMap m{};
-  const int n = 34 + 8 * NF2;
   int tot = 0;
-  for (int u = 0; u < n; ++u) tot += unit_w2(u);
+  for (int u = 0; u < n; ++u) tot += half_w(h0 + u);
   int acc = 0, u = 0;
   for (int s = 0; s < 32; ++s) {
     m.first[s] = u;
-    const int lim = (tot * (s + 1) + 31) / 32;
-    while (u < n && acc + unit_w2(u) <= lim) { acc += unit_w2(u); ++u; }
+    while (u < n && (2 * acc + half_w(h0 + u)) * 32 <= 2 * tot * (s + 1)) { acc += half_w(h0 + u); ++u; }
   }
   m.first[32] = n;
-  return m;
-}
-constexpr SlotMap make_map1() {
-  SlotMap m{};
-  const int n = 8 * (8 - NF2);
-  for (int s = 0; s <= 32; ++s) m.first[s] = (n * s) / 32;
   return m;
 }
 
@@ -66,7 +69,8 @@ constexpr SlotMap make_map1() {
 // PACKED (r03): packed samples (p.seg_start: first key row of each query row's segment, non-decreasing; one chunk).  The workgroup
 // starts at the (even) tile of its first row's segment, and a tile that begins before the segment of the wave's LAST row gets a
 // second arithmetic mask (key >= seg_start[row]); rows whose segment starts later see such tiles as all-masked: P = 0, the running
-// maximum stays at its initial -1e30 and the first visible tile rescales the (zero) state by exp2(-1e30 - m) = 0.
+// maximum stays at its initial -1e30; its first visible key then gives exp2(s + 1e30) = inf, the tile fails the acceptance and the
+// rare path rescales the (zero) state by exp2(-1e30 - m) = 0.
 template <bool PACKED>
 __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -190,15 +194,15 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
     for (int db = 0; db < 4; ++db) asm volatile("" : "+a"(o[qb][db]));
   f32x16 sb[2][2][2];                                // S^T[parity][qb][kb]: key 32 kb + (r & 3) + 8 (r >> 2) + 4 hi
   unsigned pk[2][2][4][4];                           // packed P^T[parity][qb][frag f][4 dwords]; frag f = regs 8 (f & 1) .. of kb = f >> 1
-  float m_run[2] = {-1.0e30f, -1.0e30f}, l_run[2] = {0.f, 0.f}, m_neg[2], alpha[2] = {1.f, 1.f}, mxc[4];
+  float m_run[2] = {-1.0e30f, -1.0e30f}, l_run[2] = {0.f, 0.f}, m_neg[2];
   // r04: the 32 probabilities a lane holds of a tile are summed into l_tile first and folded into l_run ONCE per tile.  Adding them one
   // by one stagnates on very long rows: beyond ~2 M visible keys l_run's ulp reaches the size of a single p (p ~ 2^-8 of the row
   // maximum, l_run ~ 5e4 -> ulp 4e-3), the small ones are rounded away and O / l comes out too large — 1.5e-2 at 13 M keys
   // (tools/bench_maxseq.py: one CP = 8 rank at S = 16.8 M); a tile's partial sum is 32 x larger than its terms
   float l_tile[2] = {0.f, 0.f};
-  float ea = 0.f, eb = 0.f, mx0_keep = 0.f;
+  float ea = 0.f, eb = 0.f;
 
-  constexpr SlotMap MAP1 = make_map1(), MAP2 = make_map2();
+  constexpr SlotMap MAP1 = make_map(8 * NF2, 64 - 8 * NF2), MAP2 = make_map(0, 8 * NF2);
 
   // exp half-units (64 per tile): h -> fragment g = h >> 3 (need order of P V: g = 2 f + qb), element pair pr = (h >> 1) & 3;
   // half 0: the two fma + exp2 of the pair, half 1: row sum, bf16 pack (an exp2 result is never consumed by the next instruction)
@@ -211,34 +215,27 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
       l_tile[qb] += ea;
       l_tile[qb] += eb;
       pk[par][qb][f][pr] = pack_bf16x2(ea, eb);
-      if (h == 55 || h == 63) {                      // the last half-unit of block qb (fragments g = 6 / 7): fold the tile's sum
-        l_run[qb] += l_tile[qb];
-        l_tile[qb] = 0.f;
-      }
-      asm volatile("" :: "v"(pk[par][qb][f][pr]), "v"(l_tile[qb]), "v"(l_run[qb]));            // computed HERE (no sinking past the phase)
+      asm volatile("" :: "v"(pk[par][qb][f][pr]), "v"(l_tile[qb]));                            // computed HERE (no sinking past the phase)
     }
   };
-  // the running-maximum decision of a tile: unit 32 keeps block 0's maximum, unit 33 decides for both blocks with ONE
-  // wave-uniform flag (grow = some row exceeds its running maximum by more than 2^THR; the first tile always grows)
-  auto max_unit = [&](int par, int u) __attribute__((always_inline)) {
-    if (u < 32) {                                    // max3 steps: four chains (qb, kb): chain c = u & 3, step u >> 2
-      const int c = u & 3, st = u >> 2, qb2 = c >> 1, kb2 = c & 1, r = 2 * st;
-      const float a = sb[par][qb2][kb2][r], bb = sb[par][qb2][kb2][r + 1];
-      mxc[c] = st == 0 ? fmaxf(a, bb) : fmaxf(fmaxf(a, bb), mxc[c]);
-    } else if (u == 32) {
-      mx0_keep = swap32_max(fmaxf(mxc[0], mxc[1])) * scale_log2e;
-    } else {
-      const float mx1 = swap32_max(fmaxf(mxc[2], mxc[3])) * scale_log2e;
-      const bool grow = __any((mx1 > m_run[1] + (float)THR) || (mx0_keep > m_run[0] + (float)THR));
+  // true row maxima of S(par) (after the masks), log2 units.  Only the prologue (tile 0) and the slow path of `accept` come here.
+  auto row_max = [&](int par, float* mx) __attribute__((always_inline)) {
 #pragma unroll
-      for (int qb2 = 0; qb2 < 2; ++qb2) {
-        const float mb = qb2 ? mx1 : mx0_keep;
-        const float m_new = grow ? fmaxf(m_run[qb2], mb) : m_run[qb2];
-        alpha[qb2] = __builtin_amdgcn_exp2f(m_run[qb2] - m_new);
-        m_run[qb2] = m_new;
-        m_neg[qb2] = -m_new;
-        l_run[qb2] *= alpha[qb2];
-      }
+    for (int qb = 0; qb < 2; ++qb) {
+      float m = fmaxf(sb[par][qb][0][0], sb[par][qb][1][0]);
+#pragma unroll
+      for (int r = 1; r < 16; ++r) m = fmaxf(fmaxf(sb[par][qb][0][r], sb[par][qb][1][r]), m);
+      mx[qb] = swap32_max(m) * scale_log2e;
+    }
+  };
+  // the running maxima move up to mx; returns alpha = exp2(old - new) per row block
+  auto raise_max = [&](const float* mx, float* alpha) __attribute__((always_inline)) {
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      const float m_new = fmaxf(m_run[qb], mx[qb]);
+      alpha[qb] = __builtin_amdgcn_exp2f(m_run[qb] - m_new);
+      m_run[qb] = m_new;
+      m_neg[qb] = -m_new;
     }
   };
   auto k_frag = [&](unsigned kslot, int i) __attribute__((always_inline)) {        // i = 2 ds + kb
@@ -263,12 +260,13 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
 #pragma unroll
     for (int s = 0; s < 32; ++s) {
       const int i = s >> 1, qb = s & 1, ds = i >> 1, kb = i & 1;
-      if (fill && (s & 3) == 1) {                    // pieces 0 .. 3 of K behind MFMAs 1, 5, 9, 13; of V behind 17, 21, 25, 29
-        const int q = s >> 2;
+      if (fill && (s & 3) == 2) {                    // pieces 0 .. 3 of K in front of MFMAs 2, 6, 10, 14; of V in front of 18, 22, 26, 30:
+        const int q = s >> 2;                        // the gaps that carry a sum-and-pack half-unit (12 cycles of VALU issue)
         if (q < 4) { if (spread_k) dma_piece(rk_next, dk_off, lds_kw, spread_k_slot, q); }
         else if (spread_v) dma_piece(rv_next, dv_off, lds_vw, spread_v_slot, q - 4);
       }
       if (qb == 0 && i + 2 < 16) kr[(i + 2) & 3] = k_frag(kslot, i + 2);
+      if (fill) __builtin_amdgcn_sched_barrier(0);   // DMA piece and K reads in FRONT of the slot's MFMA: they share the gap of the slot before
       if (ds == 0) {
         f32x16 z;
 #pragma unroll
@@ -278,6 +276,7 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
         sb[dst][qb][kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kr[i & 3], qf[qb][ds], sb[dst][qb][kb], 0, 0, 0);
       }
       if (fill) {
+        __builtin_amdgcn_sched_barrier(0);           // the slot's filler goes BEHIND its MFMA
 #pragma unroll
         for (int u = MAP1.first[s]; u < MAP1.first[s + 1]; ++u) exp_half(par, 8 * NF2 + u);
         __builtin_amdgcn_sched_barrier(0);
@@ -289,7 +288,7 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
 #pragma unroll
     for (int u = 8 * NF2; u < 64; ++u) exp_half(par, u);
   };
-  // O += V(vslot)^T P(par)^T  ||  (has_next) maxima / running-maximum decision of tile par ^ 1 and its first NF2 fragments
+  // O += V(vslot)^T P(par)^T  ||  (has_next) the first NF2 fragments of tile par ^ 1
   auto pv_phase = [&](int par, unsigned vslot, bool has_next) __attribute__((always_inline)) {
     bf16x8 vr[4];
     vr[0] = v_frag(vslot, 0); vr[1] = v_frag(vslot, 1);
@@ -300,12 +299,10 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
       const u32x4 pw = {pk[par][qb][t][0], pk[par][qb][t][1], pk[par][qb][t][2], pk[par][qb][t][3]};
       const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
       asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(o[qb][db]) : "v"(vr[i & 3]), "v"(pf));
+      __builtin_amdgcn_sched_barrier(0);             // the slot's filler goes BEHIND its MFMA (left alone, half 0 is hoisted in front of it)
       if (has_next) {
 #pragma unroll
-        for (int u = MAP2.first[s]; u < MAP2.first[s + 1]; ++u) {
-          if (u < 34) max_unit(par ^ 1, u);
-          else exp_half(par ^ 1, u - 34);
-        }
+        for (int u = MAP2.first[s]; u < MAP2.first[s + 1]; ++u) exp_half(par ^ 1, u);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -342,20 +339,43 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
         }
     }
   };
-  // O *= alpha (rare: only when a running maximum moved); every P V MFMA that precedes it has been issued
-  auto rescale_o = [&]() __attribute__((always_inline)) {
-    if (!__all(alpha[0] == 1.0f && alpha[1] == 1.0f)) {
-      // (the accumulators are operands of the wait: the compiler may not read them above it)
-      asm volatile("s_nop 15\n\ts_nop 15" : "+a"(o[0][0]), "+a"(o[0][1]), "+a"(o[0][2]), "+a"(o[0][3]), "+a"(o[1][0]), "+a"(o[1][1]), "+a"(o[1][2]), "+a"(o[1][3]));                       // asm MFMA -> accumulator read
+  // Acceptance of tile `par`, after its last exp half-unit and before its P V phase.  The half-units used the running maxima as they
+  // stood (OPTIMISTIC: no maxima are taken in the steady state).  Probabilities are non-negative, so a lane's sum l_tile <= 2^THR
+  // proves each of its 32 p <= 2^THR: the lazy rule (move the maxima when some row of the wave exceeds its own by more than 2^THR)
+  // would have left the tile alone, and it is accepted as it is.  A lane that fails (inf included: a row still at -1e30 meeting its
+  // first visible key) sends the whole wave out of line: true maxima from S(par), which is intact up to here, and the lazy rule
+  // itself.  If no row exceeds its maximum by 2^THR (a sum of many p, none of them large) the tile stands as computed.  Otherwise
+  // the RARE path: the maxima move, l and O *= alpha (every P V MFMA of the tile before has been issued), all 64 half-units again.
+  // The maxima therefore move on exactly the tiles, and to exactly the values, of the lazy rule: results are bit for bit its results.
+  auto accept = [&](int par) __attribute__((always_inline)) {
+    if (__builtin_expect(__any(!(l_tile[0] <= ACCEPT_MAX) || !(l_tile[1] <= ACCEPT_MAX)), 0)) {
+      float mx[2];
+      row_max(par, mx);
+      if (__any((mx[1] > m_run[1] + (float)THR) || (mx[0] > m_run[0] + (float)THR))) {
+        float alpha[2];
+        raise_max(mx, alpha);
+        // (the accumulators are operands of the wait: the compiler may not read them above it)
+        asm volatile("s_nop 15\n\ts_nop 15" : "+a"(o[0][0]), "+a"(o[0][1]), "+a"(o[0][2]), "+a"(o[0][3]), "+a"(o[1][0]), "+a"(o[1][1]), "+a"(o[1][2]), "+a"(o[1][3]));                       // asm MFMA -> accumulator read
 #pragma unroll
-      for (int qb = 0; qb < 2; ++qb)
+        for (int qb = 0; qb < 2; ++qb) {
+          l_run[qb] *= alpha[qb];
+          l_tile[qb] = 0.f;
 #pragma unroll
-        for (int db = 0; db < 4; ++db) {
+          for (int db = 0; db < 4; ++db) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) o[qb][db][r] *= alpha[qb];
-          asm volatile("" : "+a"(o[qb][db]));
+            for (int r = 0; r < 16; ++r) o[qb][db][r] *= alpha[qb];
+            asm volatile("" : "+a"(o[qb][db]));
+          }
         }
-      asm volatile("s_nop 7" ::: "memory");                                     // accumulator write -> asm MFMA read
+        asm volatile("s_nop 7" ::: "memory");                                     // accumulator write -> asm MFMA read
+#pragma unroll
+        for (int h = 0; h < 64; ++h) exp_half(par, h);
+      }
+    }
+#pragma unroll
+    for (int qb = 0; qb < 2; ++qb) {
+      l_run[qb] += l_tile[qb];
+      l_tile[qb] = 0.f;
     }
   };
   auto needs_mask = [&](const TileIt& t) __attribute__((always_inline)) { return t.diag && t.j * KVT + KVT - 1 > q_off_wg; };
@@ -378,12 +398,13 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   qk_phase(0, lds0 + LDS_K, false, 0);
   __syncthreads();                                  // every wave has read K(0): its ring slot may be refilled
   masks(cur, 0);
-#pragma unroll
-  for (int u = 0; u < 34 + 8 * NF2; ++u) {
-    if (u < 34) max_unit(0, u);
-    else exp_half(0, u - 34);
+  {
+    float mx0[2], alpha0[2];                         // tile 0 gets its true maxima (O and l are zero: nothing to rescale)
+    row_max(0, mx0);
+    raise_max(mx0, alpha0);
   }
-  // (O is zero: no rescale for tile 0)
+#pragma unroll
+  for (int u = 0; u < 8 * NF2; ++u) exp_half(0, u);
 
   // ---- main loop: two tiles per trip (the S / P buffer parity is a compile-time constant); n_tiles is a multiple of 4 ----------
   // full(par): `cur` sits in buffer par; K(t+2) -> K ring slot par, V(t+1) -> V ring slot par ^ 1; S(t+1) -> buffer par ^ 1
@@ -394,9 +415,9 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
     if (more_k) { walk.advance(nx2); rk_next = vita_make_rsrc_uniform(nx2.kp); spread_k_slot = par; }
     rv_next = vita_make_rsrc_uniform(nx1.vp); spread_v = true; spread_v_slot = par ^ 1;
     qk_phase(par ^ 1, lds0 + LDS_K + (par ^ 1) * TILEB, true, par);
+    accept(par);
     masks(nx1, par ^ 1);
     pv_phase(par, lds0 + LDS_V + par * TILEB, true);
-    rescale_o();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     nx1 = nx2;
@@ -407,6 +428,7 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   }
   full(0, false);
   finish_sm(1);                                      // last tile: the rest of its softmax, then P V
+  accept(1);
   pv_phase(1, lds0 + LDS_V + TILEB, false);
 
   // ---- epilogue: O[row][head][d] = O^T / l, lse ------------------------------------------------------------------------------
