@@ -1,40 +1,29 @@
 // Flash attention forward for gfx950 (MI355X): online softmax, bf16 I/O, fp32 statistics.
-// head_dim 128 (LLM: causal GQA 40:8, zig-zag context-parallel chunk geometry) and 64 (ViT,
-// non-causal, 1025 tokens).  Bound: MFMA; algorithmic work 4 * d flop per visible (q, k) pair.
+// head_dim 128 (LLM: causal GQA 40:8, zig-zag context-parallel chunk geometry), 96 (SigLIP) and 64 (ViT, non-causal, 1025 tokens):
+// the kernel for every geometry attn64.hip / attn64v.hip refuse.  Bound: MFMA; algorithmic work 4 * d flop per visible (q, k) pair.
 //
-// Structure (one workgroup = 8 waves = 256 query rows of ONE query head; KV tile = 64 keys):
-//   * K and V tiles are staged HBM/L2 -> registers -> LDS (double buffered, one barrier per tile):
-//     the global loads of tile t+1 are issued before tile t is computed and written to the other
-//     LDS buffer afterwards, so HBM/L2 latency hides under the MFMA work of the current tile.
-//   * S^T = K Q^T ("swapped" product, v_mfma_f32_32x32x16_bf16): a lane then owns ONE query row
-//     (column lane&31) and 32 of the 64 keys, so row max / row sum are in-lane reductions plus one
-//     v_permlane32_swap with the partner lane -- no LDS traffic for the softmax.
-//   * O^T = V^T P^T: the P^T operand is exactly the packed S^T accumulator (any consistent
-//     assignment of keys to MFMA k-slots is valid because the contraction is a sum), and the V^T
-//     operand comes from the row-major V tile through the LDS transpose read ds_read_b64_tr_b16.
-//   * LDS layouts are XOR-swizzled so that ds_read_b128 (K fragments) and ds_read_b64_tr_b16
-//     (V^T fragments) are bank-conflict free for the lane groups gfx950 services them in.
-//   * Sequence geometry is chunked (see vita_attn_params): causal visibility is decided per
-//     (query chunk id, key chunk id) pair, element masks are only evaluated on diagonal tiles.
-//   * Workgroup order: kv head = block id % n_kv_heads (= the XCD when n_kv_heads = 8, so one
-//     XCD's L2 serves one kv head's K/V stream to all its concurrently running query tiles), query
-//     tiles heaviest-first so the causal tail is short.
+// Structure (one workgroup = 8 waves = 256 query rows of ONE query head; KV tile = 64 keys).  The tile body is attn_fwd8.h's, shared
+// with flash_extend_kernel (attn_extend.hip): LDS-DMA of the K|V slot, S^T = K Q^T, the online-softmax step, O^T = V^T P^T with one
+// bf16 term of P, the bf16 / lse epilogue.  This file owns:
+//   * the double-buffered walk: the DMA of tile t+1 is issued before tile t is computed and lands in the other LDS slot under its
+//     MFMA work; one s_waitcnt + barrier per tile.
+//   * Sequence geometry is chunked (see vita_attn_params): causal visibility is decided per (query chunk id, key chunk id) pair,
+//     element masks (diagonal, ragged last chunk, packed segments) are only evaluated on the tiles that need them.
+//   * Workgroup order: kv head = block id % n_kv_heads (= the XCD when n_kv_heads = 8, so one XCD's L2 serves one kv head's K/V
+//     stream to all its concurrently running query tiles), query tiles heaviest-first so the causal tail is short.
 //
 // Reference behaviour restated: M/core/transformer/dot_product_attention.py:186-289 (unfused
 // math: softmax(QK^T / sqrt(d)) V with GQA repeat :171-175), :312-329 (ViT, non-causal),
 // :374-390 (LLM causal).  Zig-zag chunk ownership: M/training/utils.py:329-341.
 #include "attn_args.h"
+#include "attn_fwd8.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-// per-phase shader-clock totals of a TIMING build, [group A|B][top, qk, sm_pv, barrier, n]
-__device__ unsigned long long g_attn_timing[16];
-constexpr int QTILE = 256;   // query rows per workgroup (8 waves x 32)
-constexpr int KVT = 64;      // keys per tile
-
-// K tiles use attn_tile.h's frag layout (row = key within tile), V tiles its tr layout.
+using fwd8::KVT;
+using fwd8::QTILE;
 
 // One kv tile position of the iteration space (all fields wave-uniform -> SGPRs).
 struct TileIt {
@@ -44,29 +33,18 @@ struct TileIt {
   int64_t crow;       // first row of chunk c in the K/V buffers
 };
 
-// VARIANT (libvita_hip.so builds 6: LDS-DMA with QK_AHEAD 3; the others and TIMING are not instantiated.  The parameters stay because
-// folding them out of the source changes the d = 64 instances' register allocation, which needs a same-box A / B of its own):
-//   0 = K/V tiles go HBM/L2 -> LDS directly with the LDS-DMA (global_load_lds_dwordx4); the DMA writes
-//       lane-linear, so the bank swizzles are applied to the per-lane SOURCE address (same involution
-//       on the fragment reads); no staging VGPRs, no ds_write burst behind the barrier;
-//   1 = register staging (global_load -> VGPR -> ds_write_b128), loads issued two tiles ahead;
-//   bits 1-2 = QK_AHEAD: K-fragment reads pinned that many k-steps ahead of their MFMAs.
-// Measured and dropped: a 3-slot "staggered" schedule (waves 4..7 half a tile behind
-// waves 0..3): 0 to -3 %; s_setprio around the MFMA clusters: -2 %; a 4-wave x 64-row variant with
-// one wave per SIMD and compiler-allocated AGPRs: -19 %; an in-wave software-pipelined 4-wave x 32-row kernel
-// (exp of tile t between the MFMAs of tile t+1, 4-slot ring): -35 % (LDS-bound; see DESIGN.md 4.1, git history).
-template <int D, bool CAUSAL, int VARIANT = 0, bool TIMING = false>
+// One variant is built: K/V through the LDS-DMA, K-fragment reads pinned QK_AHEAD = 3 k-steps ahead (attn_fwd8.h).  The register-staging
+// path (global_load -> VGPR -> ds_write_b128, loads two tiles ahead), the other QK_AHEAD settings and the shader-clock TIMING
+// instrumentation were template parameters nobody instantiated; r14 deleted them with a same-box A / B of every instance family
+// (profiles/r14_kernel_bodies_ab.txt; register counts unchanged, profiles/r14_kernel_bodies_isa.txt).
+// Measured and dropped: a 3-slot "staggered" schedule (waves 4..7 half a tile behind waves 0..3): 0 to -3 %;
+// s_setprio around the MFMA clusters: -2 %; a 4-wave x 64-row variant with one wave per SIMD and compiler-allocated AGPRs: -19 %; an
+// in-wave software-pipelined 4-wave x 32-row kernel (exp of tile t between the MFMAs of tile t+1, 4-slot ring): -35 % (LDS-bound;
+// see DESIGN.md 4.1, git history).
+template <int D, bool CAUSAL>
 __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
-  constexpr int DS = D / 16;              // QK^T k-steps
-  constexpr int DB = D / 32;              // O^T row blocks
-  constexpr int ROWB = D * 2;             // bytes per K/V row
-  constexpr int TILEB = KVT * ROWB;       // bytes per K (or V) tile
-  constexpr int SLOTB = 2 * TILEB;        // bytes per ring slot (K tile | V tile)
-  constexpr int SLOTS = ROWB / 16;        // 16-byte slots per row
-  constexpr int LD_PER_THR = (KVT * SLOTS) / 512;  // 16-byte loads per thread per operand
-  constexpr bool GLDS = !(VARIANT & 1);
-  static_assert(GLDS || (KVT * SLOTS) % 512 == 0, "register staging deals whole 16-byte pieces to 512 threads (d = 96: LDS-DMA only)");
-  constexpr int QK_AHEAD = (VARIANT >> 1) & 3;          // 0 = compiler's own schedule
+  using T = fwd8::Tile<D>;
+  constexpr int DS = T::DS, DB = T::DB, SLOTB = T::SLOTB;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K tile | V tile]
   // LDS byte address of the ring (32-bit); fragment reads use  VGPR(lane offset + slot base) + imm
@@ -103,32 +81,8 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
     for (int ds = 0; ds < DS; ++ds) qf[ds] = *reinterpret_cast<const bf16x8*>(qp + ds * 16);
   }
 
-  // ---- per-lane LDS read offsets (everything else is a compile-time immediate) ----------------
-  // K fragment (A operand): row l31 (+32), 16-byte slot 2*ds + hi
-  unsigned koff[DS];
-#pragma unroll
-  for (int ds = 0; ds < DS; ++ds) koff[ds] = frag_off<D>(l31, 2 * ds + hi);
-  // V^T fragment for O^T row block db: inside a 16-lane group, lane i supplies the 8-byte piece
-  // (row i>>2, columns 4*(i&3)..) of a [4 keys][16 d] block; keys 16t + 4*hi' + {0..3} (+8)
-  unsigned voff[DB];
-  const int key_l = tr_lane_row(lane);
-#pragma unroll
-  for (int db = 0; db < DB; ++db) {
-    const int col = tr_lane_col(lane, db);
-    voff[db] = TILEB + tr_off<D>(key_l, col >> 4, (col & 15) * 2);
-  }
-  // staging: this thread's LD_PER_THR 16-byte pieces of a tile -> global element offsets
-  // (relative to the tile's first row, 32-bit) and LDS byte offsets (relative to the slot)
-  unsigned g_koff[LD_PER_THR], g_voff[LD_PER_THR], l_koff[LD_PER_THR], l_voff[LD_PER_THR];
-#pragma unroll
-  for (int it = 0; it < LD_PER_THR; ++it) {
-    const int e = tid + it * 512;
-    const int row = e / SLOTS, slot = e % SLOTS;
-    g_koff[it] = (unsigned)(row * p.k_rs + slot * 8);
-    g_voff[it] = (unsigned)(row * p.v_rs + slot * 8);
-    l_koff[it] = frag_off<D>(row, slot);
-    l_voff[it] = TILEB + tr_off<D>(row, slot >> 1, (slot & 1) << 4);
-  }
+  unsigned koff[DS], voff[DB];                      // per-lane LDS read offsets of the K and V^T fragments
+  fwd8::frag_offsets<D>(lane, koff, voff);
 
   f32x16 o_acc[DB];
 #pragma unroll
@@ -156,122 +110,17 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
     if (++t.j == t.n) { ++t.c; enter_chunk(t); }
   };
 
-  // LDS-DMA path: wave w issues pieces q = 0..PIECES-1 of K and of V; piece (w, q) = rows
-  // 4*(w*PIECES+q)*(256/ROWB).. of the tile (1 KiB), lane i lands at byte 16*i of the piece.
-  // (d = 96: a piece is 5 1/3 rows and an operand 12 pieces; the 24 pieces of a slot are dealt three per wave — waves 0 .. 3 K, 4 .. 7 V —
-  // and lane i of piece x fills the 16-byte unit u = 64 x + i = (row u / 12, physical slot u % 12).)
-  constexpr bool D96 = D == 96;
-  constexpr int PIECES = D96 ? 3 : TILEB / 1024 / 8;   // wave-instructions per operand per wave (d = 96: per wave, of ITS operand)
-  constexpr int RPP = 1024 / ROWB;                      // tile rows per 1-KiB piece (d = 96: unused)
-  const bool v_wave = D96 && wave >= 4;
-  unsigned dk_off[PIECES], dv_off[PIECES];             // per-lane source offsets (elements) inside a tile
-  int d_row[PIECES], d_ks[PIECES], d_vs[PIECES];
-#pragma unroll
-  for (int q = 0; q < PIECES; ++q) {
-    const int unit = (D96 ? (wave & 3) * PIECES + q : 0) * 64 + lane;
-    const int row = D96 ? unit / SLOTS : (wave * PIECES + q) * RPP + lane / SLOTS;   // tile row this lane fills
-    const int ps = D96 ? unit % SLOTS : lane % SLOTS;           // physical 16-byte slot in the row
-    // logical slot whose data must land at physical slot ps (inverse of the read swizzles)
-    d_ks[q] = frag_slot_inv<D>(row, ps);
-    d_vs[q] = tr_slot_inv<D>(row, ps);
-    d_row[q] = row;
-    dk_off[q] = (unsigned)(row * p.k_rs + d_ks[q] * 8);
-    dv_off[q] = (unsigned)(row * p.v_rs + d_vs[q] * 8);
-  }
+  fwd8::DmaLane<D> dma;
+  fwd8::dma_lane_init<D>(dma, wave, lane, p.k_rs, p.v_rs);
   auto dma_tile = [&](const TileIt& t, unsigned sl) __attribute__((always_inline)) {
     const int64_t row0 = t.crow + (int64_t)t.j * KVT;
-    const bf16_t* kp = kbase + row0 * p.k_rs;           // wave-uniform bases + 32-bit lane offsets
-    const bf16_t* vp = vbase + row0 * p.v_rs;
-    const int left = t.rows - t.j * KVT;               // valid rows in this tile (>= 1)
-    if constexpr (D96) {                               // this wave's three pieces of ITS operand; rows past the end clamped (masked later)
-      const bf16_t* xp = v_wave ? vp : kp;
-      const int64_t rs = v_wave ? p.v_rs : p.k_rs;
-      const unsigned dst = sl + (v_wave ? TILEB : 0) + (wave & 3) * PIECES * 1024;
-#pragma unroll
-      for (int q = 0; q < PIECES; ++q) {
-        const int row = d_row[q] < left ? d_row[q] : left - 1;
-        __builtin_amdgcn_global_load_lds((gvoid*)(xp + (int64_t)row * rs + (v_wave ? d_vs[q] : d_ks[q]) * 8),
-                                         (lvoid*)(uintptr_t)(dst + q * 1024), 16, 0, 0);
-      }
-    } else if (left >= KVT) {
-#pragma unroll
-      for (int q = 0; q < PIECES; ++q) {
-        const int piece = wave * PIECES + q;
-        __builtin_amdgcn_global_load_lds((gvoid*)(kp + dk_off[q]), (lvoid*)(uintptr_t)(sl + piece * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gvoid*)(vp + dv_off[q]), (lvoid*)(uintptr_t)(sl + TILEB + piece * 1024), 16, 0, 0);
-      }
-    } else {                                            // padded tail: clamp rows (masked later)
-#pragma unroll
-      for (int q = 0; q < PIECES; ++q) {
-        const int piece = wave * PIECES + q;
-        const int row = d_row[q] < left ? d_row[q] : left - 1;
-        __builtin_amdgcn_global_load_lds((gvoid*)(kp + (int64_t)row * p.k_rs + d_ks[q] * 8),
-                                         (lvoid*)(uintptr_t)(sl + piece * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gvoid*)(vp + (int64_t)row * p.v_rs + d_vs[q] * 8),
-                                         (lvoid*)(uintptr_t)(sl + TILEB + piece * 1024), 16, 0, 0);
-      }
-    }
+    // wave-uniform bases + 32-bit lane offsets; valid rows in this tile = t.rows - t.j * KVT (>= 1)
+    fwd8::dma_tile<D>(dma, wave, kbase + row0 * p.k_rs, vbase + row0 * p.v_rs, p.k_rs, p.v_rs, t.rows - t.j * KVT, sl);
   };
 
-  u32x4 kreg[LD_PER_THR], vreg[LD_PER_THR];
-  auto issue_loads = [&](const TileIt& t) __attribute__((always_inline)) {
-    const int64_t row0 = t.crow + (int64_t)t.j * KVT;
-    const bf16_t* kp = kbase + row0 * p.k_rs;          // wave-uniform base + 32-bit lane offset
-    const bf16_t* vp = vbase + row0 * p.v_rs;
-    const int left = t.rows - t.j * KVT;               // valid rows in this tile
-    if (left >= KVT) {
-#pragma unroll
-      for (int it = 0; it < LD_PER_THR; ++it) {
-        kreg[it] = *reinterpret_cast<const u32x4*>(kp + g_koff[it]);
-        vreg[it] = *reinterpret_cast<const u32x4*>(vp + g_voff[it]);
-      }
-    } else {                                            // padded tail: clamp rows (masked later)
-#pragma unroll
-      for (int it = 0; it < LD_PER_THR; ++it) {
-        const int e = tid + it * 512;
-        const int row = min(e / SLOTS, left - 1), slot = e % SLOTS;
-        kreg[it] = *reinterpret_cast<const u32x4*>(kp + (int64_t)row * p.k_rs + slot * 8);
-        vreg[it] = *reinterpret_cast<const u32x4*>(vp + (int64_t)row * p.v_rs + slot * 8);
-      }
-    }
-  };
-  auto write_lds = [&](unsigned sl) __attribute__((always_inline)) {
-#pragma unroll
-    for (int it = 0; it < LD_PER_THR; ++it) {
-      *(lds_u32x4*)(uintptr_t)(sl + l_koff[it]) = kreg[it];
-      *(lds_u32x4*)(uintptr_t)(sl + l_voff[it]) = vreg[it];
-    }
-  };
-
-  // ---- the phases of one tile -----------------------------------------------------------------
+  // ---- this kernel's element mask of one tile: diagonal, ragged end of the chunk, packed segment start ----------------------------
   f32x16 s0, s1;
-  auto qk_phase = [&](unsigned sl) __attribute__((always_inline)) {     // sl = LDS address of the slot
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
-    bf16x8 ka[DS], kb[DS];
-#pragma unroll
-    for (int ds = 0; ds < DS; ++ds) {
-      const unsigned a = sl + koff[ds];
-      ka[ds] = *(lds_bf16x8*)(uintptr_t)(a);
-      kb[ds] = *(lds_bf16x8*)(uintptr_t)(a + 32 * ROWB);
-    }
-#pragma unroll
-    for (int ds = 0; ds < DS; ++ds) {
-      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka[ds], qf[ds], s0, 0, 0, 0);
-      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb[ds], qf[ds], s1, 0, 0, 0);
-    }
-    if (QK_AHEAD > 0) {
-      // pin the issue order: K fragments run QK_AHEAD k-steps ahead of the MFMAs that consume them
-      __builtin_amdgcn_sched_group_barrier(0x100, 2 * QK_AHEAD, 0);
-#pragma unroll
-      for (int ds = 0; ds < DS; ++ds) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        if (ds + QK_AHEAD < DS) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-      }
-    }
-  };
-  auto sm_pv_phase = [&](unsigned sl, int kv_off, bool diag, int kv_rows) __attribute__((always_inline)) {
-    // key index (inside the tile) of accumulator register r: (r&3) + 8*(r>>2) + 4*hi (+32 for s1)
+  auto mask_tile = [&](int kv_off, bool diag, int kv_rows) __attribute__((always_inline)) {
     const bool need_mask = (diag && kv_off + KVT - 1 > q_off) || (kv_off + KVT > kv_rows) || (kv_off < wg_last_start);
     if (need_mask) {
       const int lim_c = diag ? (my_q - kv_off) : 0x7fffffff;        // key <= lim_c visible
@@ -284,79 +133,19 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
         if (key + 32 > lim || key + 32 < lo) s1[r] = -INFINITY;
       }
     }
-    // online softmax, log2 domain
-    float mx = fmaxf(s0[0], s1[0]);
-#pragma unroll
-    for (int r = 1; r < 16; ++r) mx = fmaxf(fmaxf(s0[r], s1[r]), mx);
-    mx = swap32_max(mx);
-    const float m_new = fmaxf(m_run, mx * scale_log2e);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    m_run = m_new;
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      s0[r] = __builtin_amdgcn_exp2f(fmaf(s0[r], scale_log2e, -m_new));
-      s1[r] = __builtin_amdgcn_exp2f(fmaf(s1[r], scale_log2e, -m_new));
-      psum += s0[r] + s1[r];
-    }
-    l_run = l_run * alpha + psum;
-    if (!__all(alpha == 1.0f)) {
-#pragma unroll
-      for (int i = 0; i < DB; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o_acc[i][r] *= alpha;
-    }
-    // P^T operand: step t uses registers 8*(t&1).. of block t>>1 (any consistent key <-> k-slot
-    // assignment is valid; the V^T fragment below uses the same one)
-    bf16x8 pf[4];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      pf[0][j] = (__bf16)s0[j];
-      pf[1][j] = (__bf16)s0[8 + j];
-      pf[2][j] = (__bf16)s1[j];
-      pf[3][j] = (__bf16)s1[8 + j];
-    }
-    unsigned va[DB];
-#pragma unroll
-    for (int db = 0; db < DB; ++db) va[db] = sl + voff[db];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int db = 0; db < DB; ++db) {
-        const unsigned vp = va[db] + 16 * t * ROWB;
-        const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(vp));
-        const s16x4 c = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(vp + 8 * ROWB));
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        const s16x8 ac = __builtin_shufflevector(a, c, 0, 1, 2, 3, 4, 5, 6, 7);
-        o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ac), pf[t], o_acc[db], 0, 0, 0);
-      }
-    }
   };
 
-  // ---- prologue: tile 0 -> LDS slot 0, tile 1 -> registers --------------------------------------
+  // ---- prologue: tile 0 -> LDS slot 0 ---------------------------------------------------------------
   TileIt cur;
   cur.c = 0; cur.j = 0; cur.n = 0; cur.rows = 0; cur.diag = 0; cur.crow = 0;
   enter_chunk(cur);
-  TileIt nx1 = cur;                                   // tile t+1 (its data sits in registers)
+  TileIt nx1 = cur;                                   // tile t+1
   if (cur.c < p.n_kv_chunks) {
-    if (GLDS) {
-      dma_tile(cur, lds0);
-      advance(nx1);
-    } else {
-      issue_loads(cur);
-      write_lds(lds0);
-      advance(nx1);
-      if (nx1.c < p.n_kv_chunks) issue_loads(nx1);
-    }
+    dma_tile(cur, lds0);
+    advance(nx1);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-
-  unsigned long long t_top = 0, t_qk = 0, t_sm = 0, t_bar = 0, t_n = 0, tc = 0;
-  auto tick = [&](unsigned long long& acc) __attribute__((always_inline)) {
-    if (TIMING) { const unsigned long long now = __builtin_amdgcn_s_memtime(); acc += now - tc; tc = now; }
-  };
-  if (TIMING) tc = __builtin_amdgcn_s_memtime();
 
   int slot = 0;
   while (cur.c < p.n_kv_chunks) {
@@ -364,37 +153,24 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
     TileIt nx2 = nx1;
     // tile t+1 -> the other LDS slot (every wave finished reading it before the last barrier)
     if (has_n1) {
-      if (GLDS) {
-        dma_tile(nx1, lds0 + (slot ^ 1) * SLOTB);      // lands under this tile's MFMA work
-        advance(nx2);
-      } else {
-        write_lds(lds0 + (slot ^ 1) * SLOTB);          // registers -> LDS
-        advance(nx2);
-        if (nx2.c < p.n_kv_chunks) issue_loads(nx2);    // tile t+2: HBM/L2 -> registers
-      }
+      dma_tile(nx1, lds0 + (slot ^ 1) * SLOTB);        // lands under this tile's MFMA work
+      advance(nx2);
     }
     const unsigned sl = lds0 + slot * SLOTB;
     const int kv_off = cur.j * KVT;                  // tile offset inside its chunk
     // wave-uniform skip: the whole tile lies after this wave's last query row
     const bool skip = cur.diag && kv_off > q_off + 31;
-    tick(t_top);
     if (!skip) {
-      qk_phase(sl);
-      if (TIMING) { asm volatile("s_nop 0" :: "v"(s0[15]), "v"(s1[15])); tick(t_qk); }
-      sm_pv_phase(sl, kv_off, cur.diag, cur.rows);
-      if (TIMING) { asm volatile("s_nop 0" :: "v"(o_acc[DB - 1][15])); tick(t_sm); }
+      fwd8::qk_phase<D>(sl, koff, qf, s0, s1);
+      mask_tile(kv_off, cur.diag, cur.rows);
+      fwd8::softmax_step<D>(fwd8::tile_row_max(s0, s1) * scale_log2e, scale_log2e, s0, s1, m_run, l_run, o_acc);
+      fwd8::pv_phase<D, 1>(sl, voff, s0, s1, o_acc);
     }
-    if (GLDS) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces have landed
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces have landed
     __syncthreads();
-    tick(t_bar);
-    ++t_n;
     slot ^= 1;
     cur = nx1;
     nx1 = nx2;
-  }
-  if (TIMING && lane == 0 && (wave == 0 || wave == 4)) {
-    unsigned long long* g = g_attn_timing + (wave == 4 ? 8 : 0);
-    atomicAdd(g + 0, t_top); atomicAdd(g + 1, t_qk); atomicAdd(g + 2, t_sm); atomicAdd(g + 3, t_bar); atomicAdd(g + 4, t_n);
   }
 
   // ---- epilogue ----------------------------------------------------------------------------------
@@ -402,32 +178,19 @@ __global__ __launch_bounds__(512, 2) void flash_fwd_kernel(AttnArgs p) {
   const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
   if (q_live) {
     const int64_t orow = (int64_t)qc * p.chunk_len + my_q;
-    bf16_t* op = p.o + (int64_t)b * p.o_bs + orow * p.o_rs + (int64_t)kvh * p.o_gs + (int64_t)hq * p.o_hs;
-#pragma unroll
-    for (int db = 0; db < DB; ++db) {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int d = 32 * db + 8 * rg + 4 * hi;
-        u32x2 w = {pack_bf16x2(o_acc[db][rg * 4 + 0] * inv, o_acc[db][rg * 4 + 1] * inv),
-                   pack_bf16x2(o_acc[db][rg * 4 + 2] * inv, o_acc[db][rg * 4 + 3] * inv)};
-        *reinterpret_cast<u32x2*>(op + d) = w;
-      }
-    }
-    if (p.lse && hi == 0) {
-      const float lse = l_tot > 0.f ? (m_run + log2f(l_tot)) * 0.69314718055994530942f : -INFINITY;
-      p.lse[((int64_t)b * p.n_q_heads + head) * p.n_q_rows + orow] = lse;
-    }
+    fwd8::store_row_bf16<D>(p.o + (int64_t)b * p.o_bs + orow * p.o_rs + (int64_t)kvh * p.o_gs + (int64_t)hq * p.o_hs, o_acc, inv, hi);
+    if (p.lse && hi == 0) p.lse[((int64_t)b * p.n_q_heads + head) * p.n_q_rows + orow] = fwd8::lse_natural(m_run, l_tot);
   }
 }
 
 template <int D, bool CAUSAL>
 int launch_attn(const AttnArgs& a, int64_t nblocks, hipStream_t st) {
-  constexpr int lds = 2 * 2 * KVT * D * 2;
+  constexpr int lds = fwd8::Tile<D>::LDS_BYTES;
   static std::atomic<unsigned long long> attr_set{0};
   vita_device_once(attr_set, [&] {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd_kernel<D, CAUSAL, 6>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_fwd_kernel<D, CAUSAL>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   });
-  hipLaunchKernelGGL((flash_fwd_kernel<D, CAUSAL, 6>), dim3((unsigned)nblocks), dim3(512), lds, st, a);
+  hipLaunchKernelGGL((flash_fwd_kernel<D, CAUSAL>), dim3((unsigned)nblocks), dim3(512), lds, st, a);
   return vita_check_launch();
 }
 

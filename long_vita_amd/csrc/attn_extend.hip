@@ -7,25 +7,28 @@
 // never beyond n_keys - 1): ONE integer per lane decides every mask, and only tiles that reach beyond the smallest lim of a wave
 // evaluate it.
 //
-// Built on flash_fwd_kernel<128, true> (attn.hip): 8 waves x 32 rows, 64-key K/V tiles staged by LDS-DMA with the bank swizzle on the
-// source address, S^T = K Q^T / O^T = V^T P^T on v_mfma_f32_32x32x16_bf16, in-lane online softmax.  What differs:
+// Shares attn_fwd8.h's tile body with flash_fwd_kernel (attn.hip): 8 waves x 32 rows, 64-key K/V tiles staged by LDS-DMA with the bank
+// swizzle on the source address, S^T = K Q^T / O^T = V^T P^T on v_mfma_f32_32x32x16_bf16, the online-softmax step, the bf16 / lse
+// epilogue.  What is this kernel's own:
 //   * the 256 rows of a workgroup are STACKED (row, query head of the kv group) pairs, row-major: stacked index s = row * G + head.
 //     One K/V tile read serves all G heads of the group, and a 16-row follow-up fills 80 of 256 MFMA rows instead of 16;
 //   * the keys are cut into n_splits ranges of whole tiles (blocks = kv head x query tile x split) so that a short follow-up behind
 //     a long context still fills the chip; every split writes un-normalised fp32 partials (m, l in the log2 domain, o) and
-//     extend_merge_kernel forms the bf16 context and the natural-log lse.  One split writes the result directly.
+//     extend_merge_kernel forms the bf16 context and the natural-log lse.  One split writes the result directly;
+//   * the mask by one limit per lane, the tile maximum rounded up to an integer under quant_m, and two bf16 terms of P when all
+//     stacked rows fit one query tile.
 // decode_attn_merge_kernel (decode.hip) is not reused: it writes a dense [heads][128] context and no lse; this merge writes through
 // row / head strides and one workgroup handles four (row, head) pairs.
 //
 // Reference behaviour restated: H/models/long_vita_qwen2_intern/modeling_long_vita.py:150-202 (q_len > 1 behind a DynamicCache:
 // cache_position = arange(past_seen, past_seen + s), causal mask over past + new keys) and the cached decode loop
 // M/inference/text_generation/generation.py:127-131 fed more than one token.
-#include "attn_tile.h"
+#include "attn_fwd8.h"
 
 namespace {
 
-constexpr int QTILE = 256;       // stacked query rows per workgroup (8 waves x 32)
-constexpr int KVT = 64;          // keys per tile
+using fwd8::KVT;             // keys per tile
+using fwd8::QTILE;           // stacked query rows per workgroup (8 waves x 32)
 constexpr int D = 128;
 constexpr int kMaxSplits = 64;
 constexpr int kTargetBlocks = 512;      // two rounds of one workgroup per CU (256 CUs)
@@ -41,12 +44,10 @@ struct ExtArgs {
   int n_keys, n_full;
   int64_t q_pos0, key_pos0, key_pos_step;
   int n_splits, tiles_per_split;
-  int quant_m;                   // running max kept on integers (log2 domain): see sm_pv_phase
+  int quant_m;                   // running max kept on integers (log2 domain): see the kernel's main loop
   int partial_out;               // write the fp32 partials even with one split (the beam step merges them with its tail partial)
   float scale_log2e;
 };
-
-// K tiles in attn_tile.h's frag layout, V tiles in its tr layout, at d = 128
 
 // last visible key of query row i (-1: none)
 __device__ __forceinline__ int last_visible_key(const ExtArgs& p, int i) {
@@ -57,22 +58,14 @@ __device__ __forceinline__ int last_visible_key(const ExtArgs& p, int i) {
   return (int)lim;
 }
 
-// SPLIT_P: the probabilities enter O^T = V^T P^T as TWO bf16 terms, p = hi + lo (lo = bf16(p - hi)), so the product carries ~16 bits of
-// p instead of 8 — the precision of the decode kernels' fp32 p.  With random V the 2^-9 rounding of a single bf16 p is the largest error
-// of the whole kernel (it does not average out: the error sum has the size of the output sum).  Used when all stacked rows fit ONE
-// query tile (t * G <= 256: a launch that streams K/V once, the decode kernels' regime); it costs 16 more MFMAs per tile (48 instead of
-// 32), whose effect on the launch time has not been measured apart.  Longer launches keep the prefill kernels' single bf16 term.
+// SPLIT_P: two bf16 terms of P (attn_fwd8.h's pv_phase) — the precision of the decode kernels' fp32 p.  With random V the 2^-9 rounding
+// of a single bf16 p is the largest error of the whole kernel (it does not average out: the error sum has the size of the output sum).
+// Used when all stacked rows fit ONE query tile (t * G <= 256: a launch that streams K/V once, the decode kernels' regime); it costs
+// 16 more MFMAs per tile (48 instead of 32).  Longer launches keep the prefill kernels' single bf16 term.
 template <bool SPLIT_P>
 __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
-  constexpr int DS = D / 16;              // QK^T k-steps
-  constexpr int DB = D / 32;              // O^T row blocks
-  constexpr int ROWB = D * 2;             // bytes per K/V row
-  constexpr int TILEB = KVT * ROWB;       // bytes per K (or V) tile
-  constexpr int SLOTB = 2 * TILEB;        // bytes per ring slot (K tile | V tile)
-  constexpr int SLOTS = ROWB / 16;        // 16-byte slots per row
-  constexpr int QK_AHEAD = 3;             // K-fragment reads pinned that many k-steps ahead of their MFMAs (attn.hip)
-  constexpr int PIECES = TILEB / 1024 / 8;   // 1-KiB DMA pieces per operand per wave
-  constexpr int RPP = 1024 / ROWB;           // tile rows per piece
+  using T = fwd8::Tile<D>;
+  constexpr int DS = T::DS, DB = T::DB, SLOTB = T::SLOTB;
 
   extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][K tile | V tile]
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_char*)smem;
@@ -112,17 +105,8 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
     for (int ds = 0; ds < DS; ++ds) qf[ds] = *reinterpret_cast<const bf16x8*>(qp + ds * 16);
   }
 
-  // ---- per-lane LDS read offsets ---------------------------------------------------------------------------------------------------
-  unsigned koff[DS];
-#pragma unroll
-  for (int ds = 0; ds < DS; ++ds) koff[ds] = frag_off<D>(l31, 2 * ds + hi);
-  unsigned voff[DB];
-  const int key_l = tr_lane_row(lane);
-#pragma unroll
-  for (int db = 0; db < DB; ++db) {
-    const int col = tr_lane_col(lane, db);
-    voff[db] = TILEB + tr_off<D>(key_l, col >> 4, (col & 15) * 2);
-  }
+  unsigned koff[DS], voff[DB];                      // per-lane LDS read offsets of the K and V^T fragments
+  fwd8::frag_offsets<D>(lane, koff, voff);
 
   f32x16 o_acc[DB];
 #pragma unroll
@@ -134,144 +118,16 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
   const bf16_t* kbase = p.k + (int64_t)kvh * p.kv_gs;
   const bf16_t* vbase = p.v + (int64_t)kvh * p.kv_gs;
 
-  // ---- LDS-DMA: wave w issues pieces q = 0 .. PIECES - 1 of K and of V; the bank swizzle is applied to the SOURCE address ----------
-  unsigned dk_off[PIECES], dv_off[PIECES];
-  int d_row[PIECES], d_ks[PIECES], d_vs[PIECES];
-#pragma unroll
-  for (int q = 0; q < PIECES; ++q) {
-    const int row = (wave * PIECES + q) * RPP + lane / SLOTS;   // tile row this lane fills
-    const int ps = lane % SLOTS;                                // physical 16-byte slot in the row
-    d_ks[q] = frag_slot_inv<D>(row, ps);
-    d_vs[q] = tr_slot_inv<D>(row, ps);
-    d_row[q] = row;
-    dk_off[q] = (unsigned)(row * p.kv_rs + d_ks[q] * 8);
-    dv_off[q] = (unsigned)(row * p.kv_rs + d_vs[q] * 8);
-  }
+  fwd8::DmaLane<D> dma;
+  fwd8::dma_lane_init<D>(dma, wave, lane, p.kv_rs, p.kv_rs);
   auto dma_tile = [&](int j, unsigned sl) __attribute__((always_inline)) {
     const int64_t row0 = (int64_t)j * KVT;
-    const bf16_t* kp = kbase + row0 * p.kv_rs;          // wave-uniform bases + 32-bit lane offsets
-    const bf16_t* vp = vbase + row0 * p.kv_rs;
-    const int64_t left = (int64_t)p.n_keys - row0;      // rows of the cache behind row0 (>= 1): nothing past n_keys is ever read
-    if (left >= KVT) {
-#pragma unroll
-      for (int q = 0; q < PIECES; ++q) {
-        const int piece = wave * PIECES + q;
-        __builtin_amdgcn_global_load_lds((gvoid*)(kp + dk_off[q]), (lvoid*)(uintptr_t)(sl + piece * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gvoid*)(vp + dv_off[q]), (lvoid*)(uintptr_t)(sl + TILEB + piece * 1024), 16, 0, 0);
-      }
-    } else {                                            // last tile: clamp rows (masked later)
-#pragma unroll
-      for (int q = 0; q < PIECES; ++q) {
-        const int piece = wave * PIECES + q;
-        const int row = d_row[q] < (int)left ? d_row[q] : (int)left - 1;
-        __builtin_amdgcn_global_load_lds((gvoid*)(kp + (int64_t)row * p.kv_rs + d_ks[q] * 8),
-                                         (lvoid*)(uintptr_t)(sl + piece * 1024), 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((gvoid*)(vp + (int64_t)row * p.kv_rs + d_vs[q] * 8),
-                                         (lvoid*)(uintptr_t)(sl + TILEB + piece * 1024), 16, 0, 0);
-      }
-    }
-  };
-
-  // ---- the phases of one tile ------------------------------------------------------------------------------------------------------
-  f32x16 s0, s1;
-  auto qk_phase = [&](unsigned sl) __attribute__((always_inline)) {
-#pragma unroll
-    for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
-    bf16x8 ka[DS], kb[DS];
-#pragma unroll
-    for (int ds = 0; ds < DS; ++ds) {
-      const unsigned a = sl + koff[ds];
-      ka[ds] = *(lds_bf16x8*)(uintptr_t)(a);
-      kb[ds] = *(lds_bf16x8*)(uintptr_t)(a + 32 * ROWB);
-    }
-#pragma unroll
-    for (int ds = 0; ds < DS; ++ds) {
-      s0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ka[ds], qf[ds], s0, 0, 0, 0);
-      s1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kb[ds], qf[ds], s1, 0, 0, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x100, 2 * QK_AHEAD, 0);
-#pragma unroll
-    for (int ds = 0; ds < DS; ++ds) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-      if (ds + QK_AHEAD < DS) __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-    }
-  };
-  auto sm_pv_phase = [&](unsigned sl, int k0) __attribute__((always_inline)) {
-    // key index (inside the tile) of accumulator register r: (r&3) + 8*(r>>2) + 4*hi (+32 for s1)
-    if (k0 + KVT - 1 > wave_min_lim) {                 // the tile reaches past the n_full / diagonal / n_keys limit of some row
-      const int lim = my_lim - k0;                     // key <= lim visible
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int key = (r & 3) + 8 * (r >> 2) + 4 * hi;
-        if (key > lim) s0[r] = -INFINITY;
-        if (key + 32 > lim) s1[r] = -INFINITY;
-      }
-    }
-    float mx = fmaxf(s0[0], s1[0]);
-#pragma unroll
-    for (int r = 1; r < 16; ++r) mx = fmaxf(fmaxf(s0[r], s1[r]), mx);
-    mx = swap32_max(mx);
-    // quant_m (every launch whose shape is split over the keys): the running max moves on INTEGERS of the log2 domain.  Two histories
-    // of a row (one split or many, wherever the cuts fall) then differ by whole powers of two in every p = 2^(s - m): bf16(p) is the
-    // same mantissa, the rescales are exact, and the splits compose to the unsplit result up to fp32 summation order.  With a real-valued
-    // max the two bf16 roundings of p are unrelated and split and unsplit results sit 2.8e-3 apart (each 2.2e-3 from the exact one).
-    // Unsplit shapes keep the real-valued max: the prefill kernel's arithmetic on the same rows.
-    float m_tile = mx * scale_log2e;
-    if (p.quant_m) m_tile = ceilf(m_tile);
-    const float m_new = fmaxf(m_run, m_tile);
-    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-    m_run = m_new;
-    float psum = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      s0[r] = __builtin_amdgcn_exp2f(fmaf(s0[r], scale_log2e, -m_new));
-      s1[r] = __builtin_amdgcn_exp2f(fmaf(s1[r], scale_log2e, -m_new));
-      psum += s0[r] + s1[r];
-    }
-    l_run = l_run * alpha + psum;
-    if (!__all(alpha == 1.0f)) {
-#pragma unroll
-      for (int i = 0; i < DB; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) o_acc[i][r] *= alpha;
-    }
-    bf16x8 pf[4];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      pf[0][j] = (__bf16)s0[j];
-      pf[1][j] = (__bf16)s0[8 + j];
-      pf[2][j] = (__bf16)s1[j];
-      pf[3][j] = (__bf16)s1[8 + j];
-    }
-    bf16x8 pl[4];
-    if (SPLIT_P) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        pl[0][j] = (__bf16)(s0[j] - (float)pf[0][j]);
-        pl[1][j] = (__bf16)(s0[8 + j] - (float)pf[1][j]);
-        pl[2][j] = (__bf16)(s1[j] - (float)pf[2][j]);
-        pl[3][j] = (__bf16)(s1[8 + j] - (float)pf[3][j]);
-      }
-    }
-    unsigned va[DB];
-#pragma unroll
-    for (int db = 0; db < DB; ++db) va[db] = sl + voff[db];
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-#pragma unroll
-      for (int db = 0; db < DB; ++db) {
-        const unsigned vp = va[db] + 16 * t * ROWB;
-        const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(vp));
-        const s16x4 c = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(uintptr_t)(vp + 8 * ROWB));
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        const s16x8 ac = __builtin_shufflevector(a, c, 0, 1, 2, 3, 4, 5, 6, 7);
-        o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ac), pf[t], o_acc[db], 0, 0, 0);
-        if (SPLIT_P) o_acc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ac), pl[t], o_acc[db], 0, 0, 0);
-      }
-    }
+    // rows of the cache behind row0 (>= 1, an int: n_keys is one): nothing past n_keys is ever read
+    fwd8::dma_tile<D>(dma, wave, kbase + row0 * p.kv_rs, vbase + row0 * p.kv_rs, p.kv_rs, p.kv_rs, p.n_keys - j * KVT, sl);
   };
 
   // ---- main loop: tile j in LDS slot (j - j_begin) & 1, tile j + 1 lands under its MFMA work ---------------------------------------
+  f32x16 s0, s1;
   if (j_begin < j_end) dma_tile(j_begin, lds0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -281,8 +137,25 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
     const unsigned sl = lds0 + slot * SLOTB;
     const int k0 = j * KVT;
     if (k0 <= wave_lim) {                               // wave-uniform: some row of this wave sees a key of the tile
-      qk_phase(sl);
-      sm_pv_phase(sl, k0);
+      fwd8::qk_phase<D>(sl, koff, qf, s0, s1);
+      if (k0 + KVT - 1 > wave_min_lim) {                // the tile reaches past the n_full / diagonal / n_keys limit of some row
+        const int lim = my_lim - k0;                    // key <= lim visible
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int key = (r & 3) + 8 * (r >> 2) + 4 * hi;
+          if (key > lim) s0[r] = -INFINITY;
+          if (key + 32 > lim) s1[r] = -INFINITY;
+        }
+      }
+      // quant_m (every launch whose shape is split over the keys): the running max moves on INTEGERS of the log2 domain.  Two histories
+      // of a row (one split or many, wherever the cuts fall) then differ by whole powers of two in every p = 2^(s - m): bf16(p) is the
+      // same mantissa, the rescales are exact, and the splits compose to the unsplit result up to fp32 summation order.  With a real-valued
+      // max the two bf16 roundings of p are unrelated and split and unsplit results sit 2.8e-3 apart (each 2.2e-3 from the exact one).
+      // Unsplit shapes keep the real-valued max: the prefill kernel's arithmetic on the same rows.
+      float m_tile = fwd8::tile_row_max(s0, s1) * scale_log2e;
+      if (p.quant_m) m_tile = ceilf(m_tile);
+      fwd8::softmax_step<D>(m_tile, scale_log2e, s0, s1, m_run, l_run, o_acc);
+      fwd8::pv_phase<D, SPLIT_P ? 2 : 1>(sl, voff, s0, s1, o_acc);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's DMA pieces have landed
     __syncthreads();
@@ -294,20 +167,8 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
   if (!live) return;
   const int head = kvh * G + my_hq;
   if (p.n_splits == 1 && !p.partial_out) {
-    const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
-    bf16_t* op = p.o + (int64_t)my_row * p.o_rs + (int64_t)head * p.o_hs;
-#pragma unroll
-    for (int db = 0; db < DB; ++db) {
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        const int d = 32 * db + 8 * rg + 4 * hi;
-        u32x2 w = {pack_bf16x2(o_acc[db][rg * 4 + 0] * inv, o_acc[db][rg * 4 + 1] * inv),
-                   pack_bf16x2(o_acc[db][rg * 4 + 2] * inv, o_acc[db][rg * 4 + 3] * inv)};
-        *reinterpret_cast<u32x2*>(op + d) = w;
-      }
-    }
-    if (p.lse && hi == 0)
-      p.lse[(int64_t)head * p.t + my_row] = l_tot > 0.f ? (m_run + log2f(l_tot)) * 0.69314718055994530942f : -INFINITY;
+    fwd8::store_row_bf16<D>(p.o + (int64_t)my_row * p.o_rs + (int64_t)head * p.o_hs, o_acc, l_tot > 0.f ? 1.0f / l_tot : 0.f, hi);
+    if (p.lse && hi == 0) p.lse[(int64_t)head * p.t + my_row] = fwd8::lse_natural(m_run, l_tot);
   } else {
     const int64_t rec = ((int64_t)split * (p.n_kv_heads * G) + head) * p.t + my_row;
     float* po = p.po + rec * D;
@@ -630,7 +491,7 @@ extern "C" int vita_beam_attn_fwd(const void* q, int64_t q_row_stride, int64_t q
   a.n_splits = beam_splits(n_beams, n_q_heads, prefix_len);
   const int64_t key_tiles = (prefix_len + KVT - 1) / KVT;
   a.tiles_per_split = (int)((key_tiles + a.n_splits - 1) / a.n_splits);
-  a.quant_m = 1;                                                // the partials are always merged: see sm_pv_phase
+  a.quant_m = 1;                                                // the partials are always merged: see the kernel's main loop
   a.partial_out = 1;
   a.scale_log2e = softmax_scale * LOG2E;
   const int64_t n_rec = (int64_t)n_q_heads * n_beams;

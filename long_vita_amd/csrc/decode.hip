@@ -21,20 +21,43 @@ __device__ __forceinline__ float dot8(const u32x4 a, const u32x4 b) {
   return s;
 }
 
-constexpr int kGemvRows = 1;
+// ---- what gemv_kernel and gemv_rows_kernel share -----------------------------------------------------------------------------
+// One 16-byte vector of the RMS-normalised x: bf16(bf16(x * rstd) * gamma), as vita_rmsnorm_fwd rounds it.
+// The two kernels do NOT share the sum of squares behind rstd, on purpose: gemv_kernel adds dot8(x, x) per vector (eight products,
+// then one add into the sum), gemv_rows_kernel adds pair by pair as rmsnorm_fwd_kernel does, which is what makes its normalised row
+// bit-equal to vita_rmsnorm_fwd.  The two orders can round rstd differently; changing either changes output bits.
+__device__ __forceinline__ u32x4 gemv_norm_x(u32x4 xv, const float rstd, const u32x4 gv) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    xv[j] = pack_bf16x2(bf16_round(bf16lo_to_f32(xv[j]) * rstd) * bf16lo_to_f32(gv[j]),
+                        bf16_round(bf16hi_to_f32(xv[j]) * rstd) * bf16hi_to_f32(gv[j]));
+  return xv;
+}
+// s0 (and s1, SWIGLU's "up" row) = the wave's dot products; bias / residual = the output's element where EPI reads one (GEMV_ELEM)
+#define GEMV_ELEM(E, ptr, i) (EPI == (E) ? bf16_to_f32((ptr)[i]) : 0.f)
+template <int EPI>
+__device__ __forceinline__ bf16_t gemv_epilogue(const float s0, const float s1, const float bias, const float residual) {
+  float o = s0;
+  if (EPI == VITA_EPI_BIAS) o += bias;
+  if (EPI == VITA_EPI_RESIDUAL) o = bf16_round(o) + residual;
+  if (EPI == VITA_EPI_SWIGLU) {                     // same rounding chain as the GEMM epilogue
+    const float g = bf16_round(s0), u = bf16_round(s1);
+    o = bf16_round(g / (1.0f + __expf(-g))) * u;
+  }
+  return f32_to_bf16(o);
+}
 
 // ---- y[N] = epilogue(W[N,K] . norm(x)[K]) : one wave per output, 16-byte pieces of the W row per lane ----
-// NORM: x is RMS-normalised on the fly, bf16(bf16(x * rstd) * gamma) as vita_rmsnorm_fwd rounds it; every wave
-// recomputes the 10 KB sum of squares (L2-resident) instead of a separate launch + round trip.
+// NORM: x is RMS-normalised on the fly; every wave recomputes the 10 KB sum of squares (L2-resident) instead of a separate
+// launch + round trip.
 template <int EPI, bool NORM>
 __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ W,
                                                    int64_t ldw, bf16_t* __restrict__ y, int64_t N, int64_t K,
                                                    const bf16_t* __restrict__ bias, const bf16_t* __restrict__ R,
                                                    const bf16_t* __restrict__ gamma, float eps) {
-  constexpr int ROWS = kGemvRows;                  // outputs per wave: x is read (and normalised) once for all of them
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t n0 = ((int64_t)blockIdx.x * 4 + wave) * ROWS;
-  if (n0 >= N) return;
+  const int64_t n = (int64_t)blockIdx.x * 4 + wave;
+  if (n >= N) return;
   const int nvec = (int)(K >> 3);
   const u32x4* xr = reinterpret_cast<const u32x4*>(x);
   const u32x4* gr = reinterpret_cast<const u32x4*>(gamma);
@@ -44,54 +67,25 @@ __global__ __launch_bounds__(256) void gemv_kernel(const bf16_t* __restrict__ x,
     for (int v = lane; v < nvec; v += 64) ss += dot8(xr[v], xr[v]);
     rstd = rsqrtf(wave_reduce_sum(ss) / (float)K + eps);
   }
-  const u32x4* w0[ROWS];
-  const u32x4* w1[ROWS];
-  float a0[ROWS], a1[ROWS];
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const int64_t n = (n0 + r < N) ? n0 + r : N - 1;                          // clamp: tail rows recompute row N-1
-    w0[r] = reinterpret_cast<const u32x4*>(W + n * ldw);
-    w1[r] = reinterpret_cast<const u32x4*>(W + (n + N) * ldw);                // SWIGLU: the "up" row
-    a0[r] = 0.f; a1[r] = 0.f;
-  }
+  const u32x4* w0 = reinterpret_cast<const u32x4*>(W + n * ldw);
+  const u32x4* w1 = reinterpret_cast<const u32x4*>(W + (n + N) * ldw);          // SWIGLU: the "up" row
+  float a0 = 0.f, a1 = 0.f;
 #pragma unroll 4
   for (int v = lane; v < nvec; v += 64) {
     u32x4 xv = xr[v];
-    if (NORM) {
-      const u32x4 gv = gr[v];
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        xv[j] = pack_bf16x2(bf16_round(bf16lo_to_f32(xv[j]) * rstd) * bf16lo_to_f32(gv[j]),
-                            bf16_round(bf16hi_to_f32(xv[j]) * rstd) * bf16hi_to_f32(gv[j]));
-    }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-      a0[r] += dot8(xv, w0[r][v]);
-      if (EPI == VITA_EPI_SWIGLU) a1[r] += dot8(xv, w1[r][v]);
-    }
+    if (NORM) xv = gemv_norm_x(xv, rstd, gr[v]);
+    a0 += dot8(xv, w0[v]);
+    if (EPI == VITA_EPI_SWIGLU) a1 += dot8(xv, w1[v]);
   }
-#pragma unroll
-  for (int r = 0; r < ROWS; ++r) {
-    const float s0 = wave_reduce_sum(a0[r]);
-    const float s1 = (EPI == VITA_EPI_SWIGLU) ? wave_reduce_sum(a1[r]) : 0.f;
-    const int64_t n = n0 + r;
-    if (lane != 0 || n >= N) continue;
-    float o = s0;
-    if (EPI == VITA_EPI_BIAS) o += bf16_to_f32(bias[n]);
-    if (EPI == VITA_EPI_RESIDUAL) o = bf16_round(o) + bf16_to_f32(R[n]);
-    if (EPI == VITA_EPI_SWIGLU) {                     // same rounding chain as the GEMM epilogue
-      const float g = bf16_round(s0), u = bf16_round(s1);
-      o = bf16_round(g / (1.0f + __expf(-g))) * u;
-    }
-    y[n] = f32_to_bf16(o);
-  }
+  const float s0 = wave_reduce_sum(a0);
+  const float s1 = (EPI == VITA_EPI_SWIGLU) ? wave_reduce_sum(a1) : 0.f;
+  if (lane == 0) y[n] = gemv_epilogue<EPI>(s0, s1, GEMV_ELEM(VITA_EPI_BIAS, bias, n), GEMV_ELEM(VITA_EPI_RESIDUAL, R, n));
 }
 
 template <int EPI, bool NORM>
 void launch_gemv(const void* x, const void* W, int64_t ldw, void* y, int64_t N, int64_t K, const void* bias,
                  const void* R, const void* gamma, float eps, hipStream_t st) {
-  const int64_t waves = (N + kGemvRows - 1) / kGemvRows;
-  hipLaunchKernelGGL((gemv_kernel<EPI, NORM>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, (const bf16_t*)x,
+  hipLaunchKernelGGL((gemv_kernel<EPI, NORM>), dim3((unsigned)((N + 3) / 4)), dim3(256), 0, st, (const bf16_t*)x,
                      (const bf16_t*)W, ldw, (bf16_t*)y, N, K, (const bf16_t*)bias, (const bf16_t*)R,
                      (const bf16_t*)gamma, eps);
 }
@@ -155,12 +149,7 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const bf16_t* __restrict
 #pragma unroll
     for (int b = 0; b < R; ++b) {
       xv[b] = xr[b][v];
-      if (NORM) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-          xv[b][j] = pack_bf16x2(bf16_round(bf16lo_to_f32(xv[b][j]) * rstd[b]) * bf16lo_to_f32(gv[j]),
-                                 bf16_round(bf16hi_to_f32(xv[b][j]) * rstd[b]) * bf16hi_to_f32(gv[j]));
-      }
+      if (NORM) xv[b] = gemv_norm_x(xv[b], rstd[b], gv);
     }
 #pragma unroll
     for (int r = 0; r < NOUT; ++r) {
@@ -182,14 +171,7 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const bf16_t* __restrict
       const float s1 = (EPI == VITA_EPI_SWIGLU) ? wave_reduce_sum(a1[r][b]) : 0.f;
       const int64_t n = n0 + r;
       if (lane != 0 || n >= N || b >= rows) continue;
-      float o = s0;
-      if (EPI == VITA_EPI_BIAS) o += bf16_to_f32(bias[n]);
-      if (EPI == VITA_EPI_RESIDUAL) o = bf16_round(o) + bf16_to_f32(Res[(int64_t)b * ldr + n]);
-      if (EPI == VITA_EPI_SWIGLU) {                     // same rounding chain as the GEMM epilogue
-        const float g = bf16_round(s0), u = bf16_round(s1);
-        o = bf16_round(g / (1.0f + __expf(-g))) * u;
-      }
-      y[(int64_t)b * ldy + n] = f32_to_bf16(o);
+      y[(int64_t)b * ldy + n] = gemv_epilogue<EPI>(s0, s1, GEMV_ELEM(VITA_EPI_BIAS, bias, n), GEMV_ELEM(VITA_EPI_RESIDUAL, Res, (int64_t)b * ldr + n));
     }
   }
 }

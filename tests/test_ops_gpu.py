@@ -325,7 +325,7 @@ def test_flash_attention_mixed_qkv_views(ops):
     tol("out, ref", rel_l2(out, ref), 3.1e-03)
 
 
-@pytest.mark.parametrize("cp,S", [(2, 2048), (4, 4096), (8, 4096)])
+@pytest.mark.parametrize("cp,S", [(2, 768), (2, 2048), (4, 4096), (8, 4096)])      # (2, 768): chunks of 192 rows, walked by attn.hip
 def test_flash_attention_zigzag_chunks(ops, cp, S):
     """Every rank's zig-zag context-parallel attention (local Q x all-gathered K/V in rank order)
     re-assembled == monolithic causal attention (SURVEY.md §8c cross-check ii)."""
