@@ -721,6 +721,50 @@ int vita_decode_layer_attn(const vita_decode_layer_params* p, void* stream);
 int vita_decode_layer_mlp(const vita_decode_layer_params* p, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * FP8 KV cache for the cached decode (opt-in, CP = 1 and TP = 1).  What Megatron keeps per layer in
+ * InferenceParams.key_value_memory_dict (and the HF DynamicCache of modeling_long_vita.py:150-202) as bf16 is kept as OCP e4m3fn
+ * codes [capacity][groups][128] (1 byte per element) plus one fp32 scale per (row, kv group) [capacity][groups], K and V apart.
+ * The rule, per K (after RoPE) or V head row x[0..127]: amax = max |x_i| (a NaN element makes it NaN); s = amax > 0 ? amax / 448 : 1;
+ * code_i = e4m3fn_rne(x_i / s) (fp32, IEEE division, no clamp); the cache reads back f32(code_i) * s.  A non-finite element leaves
+ * non-finite values in its row.  Code strides are in BYTES and multiples of 8 (8-byte vectors, pointers 8-byte aligned); scale
+ * strides are in floats.
+ *
+ * vita_kv8_store: quantises `rows` K and V head rows per group, read in place from the mixed qkv buffer (k_src / v_src point at
+ *   row 0, group 0; strides in bf16 elements, multiples of 8, pointers 16-byte aligned), into cache rows row0 + r.  row0_dev != NULL:
+ *   row0 is read from that int64 in device memory (the captured token step).  A row range that does not lie inside
+ *   [0, capacity) writes nothing (refused on the host when row0 is the host's).  Rows outside [row0, row0 + rows) are not touched.
+ *   Fills the cache during prefill (rows = s) and appends a decode token (rows = 1).
+ * vita_decode_attn_partial_kv8: vita_decode_attn_partial over such a cache: the same split geometry, len_dev rule and fp32
+ *   partials (part_m, part_l, part_o; the neutral element for a split without keys), which vita_decode_attn_merge and the
+ *   context-parallel message take unchanged.  Scores and P.V are computed as for bf16 K / V on the codes; the K scale multiplies
+ *   the finished dot product, the V scale multiplies p.
+ * vita_decode_layer_attn_kv8: vita_decode_layer_attn with the cache described by `c`; k_cache, v_cache, kv_row_stride and
+ *   kv_group_stride of the parameter struct are not read.  The appended row holds the codes and scales of the rule applied to the
+ *   K / V row vita_decode_layer_attn appends; the context is that of vita_kv8_store + vita_decode_attn_partial_kv8 +
+ *   vita_decode_attn_merge, bit for bit.  vita_decode_layer_mlp follows unchanged.
+ * Stands behind Megatron's InferenceParams.key_value_memory_dict (Attention._adjust_key_value_for_inference under the decode loop
+ * M/inference/text_generation/generation.py:127-131) and the HF cache update of modeling_long_vita.py:150-202. */
+typedef struct {
+  void *k_codes, *v_codes;       /* [capacity][kv_groups][128] e4m3fn */
+  int64_t code_row_stride, code_group_stride;   /* bytes */
+  void *k_scales, *v_scales;     /* [capacity][kv_groups] fp32 */
+  int64_t scale_row_stride, scale_group_stride; /* floats */
+} vita_kv8_cache;
+/* InferenceParams.key_value_memory_dict (Megatron); modeling_long_vita.py:150-202 (HF cache) */
+int vita_kv8_store(const void* k_src, const void* v_src, int64_t src_row_stride, int64_t src_group_stride, int64_t rows,
+                   int groups, int head_dim, void* k_codes, void* v_codes, int64_t code_row_stride, int64_t code_group_stride,
+                   void* k_scales, void* v_scales, int64_t scale_row_stride, int64_t scale_group_stride, int64_t row0,
+                   const void* row0_dev, int64_t capacity, void* stream);
+/* InferenceParams.key_value_memory_dict (Megatron); modeling_long_vita.py:150-202 (HF cache) */
+int vita_decode_attn_partial_kv8(const void* q, int64_t q_group_stride, int64_t q_head_stride, const void* k_codes,
+                                 const void* v_codes, int64_t code_row_stride, int64_t code_group_stride, const void* k_scales,
+                                 const void* v_scales, int64_t scale_row_stride, int64_t scale_group_stride, int len,
+                                 const void* len_dev, int n_splits, int groups, int qpg, int head_dim, float softmax_scale,
+                                 void* part_m, void* part_l, void* part_o, void* stream);
+/* InferenceParams.key_value_memory_dict (Megatron); modeling_long_vita.py:150-202 (HF cache) */
+int vita_decode_layer_attn_kv8(const vita_decode_layer_params* p, const vita_kv8_cache* c, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Frame / image preprocessing — ImageProcessor.process_images and dynamic_preprocess,
  * H/data/processor/image_processor.py:180-223,404-448, then the bf16 cast of
  * M/tasks/inference/module.py:693.  frames [n][height][width][3] uint8 RGB (frame_stride bytes apart)

@@ -539,6 +539,38 @@ extern "C" int vita_decode_layer_attn(const vita_decode_layer_params* p, void* s
                                 p->ctx, st);
 }
 
+// the same layer over an FP8 cache (kv8.hip): the same QKV GEMV and merge, RoPE + quantised append, attention on codes + scales
+extern "C" int vita_decode_layer_attn_kv8(const vita_decode_layer_params* p, const vita_kv8_cache* c, void* stream) {
+  if (!decode_layer_args_ok(p) || !c || !p->ln1 || !p->qkv_w || !p->qkv_b || !p->cos || !p->sin || !c->k_codes || !c->v_codes ||
+      !c->k_scales || !c->v_scales || !p->part_m || !p->part_l || !p->part_o)
+    return VITA_ERR_INVALID_ARG;
+  const int qpg = p->heads / p->kv_groups, hpg = qpg + 2;
+  if (p->head_dim != 128 || qpg > 8 || (p->hidden & 7) || p->len < 0 || p->len > p->capacity || p->append_row >= p->capacity ||
+      p->n_splits <= 0 || (c->code_row_stride & 7) || (c->code_group_stride & 7) ||
+      (((uintptr_t)c->k_codes | (uintptr_t)c->v_codes) & 7) || (((uintptr_t)c->k_scales | (uintptr_t)c->v_scales) & 3))
+    return VITA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t qkv_out = (int64_t)(p->heads + 2 * p->kv_groups) * p->head_dim;
+  launch_gemv<VITA_EPI_BIAS, true>(p->h, p->qkv_w, p->hidden, p->qkv, qkv_out, p->hidden, p->qkv_b, nullptr, p->ln1, p->eps, st);
+  int rc = vita_kv8_rope_append(p->qkv, p->kv_groups, qpg, p->head_dim, p->cos, p->sin, c, p->append_row, st);
+  if (rc != VITA_OK) return rc;
+  const int H = p->heads, D = p->head_dim;
+  if (p->len > 0) {
+    rc = vita_decode_attn_partial_kv8(p->qkv, (int64_t)hpg * D, D, c->k_codes, c->v_codes, c->code_row_stride, c->code_group_stride,
+                                      c->k_scales, c->v_scales, c->scale_row_stride, c->scale_group_stride, p->len, nullptr,
+                                      p->n_splits, p->kv_groups, qpg, D, p->softmax_scale, p->part_m, p->part_l, p->part_o, st);
+    if (rc != VITA_OK) return rc;
+  }
+  const int nparts = p->len > 0 ? p->n_splits : 0;
+  if (p->msg) {                       // packed (o, m, l) partial, as vita_decode_layer_attn writes it
+    float* msg = (float*)p->msg;
+    return vita_decode_attn_merge(p->part_m, p->part_l, p->part_o, nparts, H, (int64_t)H * D, H, D, msg + (int64_t)H * D,
+                                  msg + (int64_t)H * D + H, msg, nullptr, st);
+  }
+  return vita_decode_attn_merge(p->part_m, p->part_l, p->part_o, nparts, H, (int64_t)H * D, H, D, nullptr, nullptr, nullptr,
+                                p->ctx, st);
+}
+
 extern "C" int vita_decode_layer_mlp(const vita_decode_layer_params* p, void* stream) {
   if (!decode_layer_args_ok(p) || !p->o_w || !p->ln2 || !p->fc1_w || !p->fc2_w) return VITA_ERR_INVALID_ARG;
   if (p->head_dim != 128 || (p->hidden & 7) || (p->ffn & 7)) return VITA_ERR_UNSUPPORTED;

@@ -175,6 +175,12 @@ __device__ __forceinline__ void vita_store_row8(float* p, const float* v) {
   *reinterpret_cast<f32x4*>(p + 4) = hi;
 }
 
+// ---- FP8 KV cache (kv8.hip) ------------------------------------------------------------------------------------------------
+// RoPE of the token's q / k heads in place + quantised append of its K / V: the second kernel of vita_decode_layer_attn_kv8
+// (decode.hip), which has checked the arguments.
+int vita_kv8_rope_append(void* qkv, int groups, int qpg, int head_dim, const void* cos_tab, const void* sin_tab,
+                         const vita_kv8_cache* c, int append_row, hipStream_t stream);
+
 // ---- LDS-DMA issued from inline asm ------------------------------------------------------------------------------------------
 // `buffer_load_dword[x4] ... lds` moves 4 / 16 bytes per lane from a buffer address (descriptor base + per-lane byte offset) to
 // LDS address m0 + lane * size.  Issued through the compiler's builtin, hipcc remembers that an LDS write is in flight and puts

@@ -141,7 +141,7 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
                                                     do_sample=False, top_k=0, top_p=0.0, temperature=1.0,
                                                     use_eod_token_for_early_termination=True, external_inputs=None,
                                                     *, use_kv_cache=True, logit_mask=True, termination_id=None,
-                                                    reference_compat=False, token_selector=None):
+                                                    reference_compat=False, token_selector=None, kv_cache_dtype=None):
     """Generator with the reference's contract (:33-280): `tokens` [1, max_sequence_length] holds the prompt
     (length lengths[0]) followed by padding and is filled in place; yields (tokens[:, :ctx+1], lengths,
     output_log_probs) per generated token.  args.use_kv_cache / args.logit_mask / the tokenizer's eod are keyword
@@ -153,7 +153,9 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
     sync_output on those steps.
 
     token_selector(last_token_logits [1, V], context_length) -> [1] token ids, when given, replaces _sample_strategy (the device-side
-    choice with a repetition penalty, hf_adaptor.py); None: nothing changes."""
+    choice with a repetition penalty, hf_adaptor.py); None: nothing changes.
+
+    kv_cache_dtype: "bf16" or "fp8_e4m3" for this request's cache; None: the model's setting (GPTVLModel.kv_cache_dtype)."""
     from .inference_params import ForwardStep
     batch_size, max_sequence_length = tokens.shape
     if batch_size != 1:
@@ -165,6 +167,7 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
     forward_step = ForwardStep(model, batch_size, max_sequence_length, external_inputs=None)
     ip = forward_step.inference_params
     ip.use_kv_cache = use_kv_cache
+    ip.kv_cache_dtype = kv_cache_dtype
     output_log_probs = None
     if return_output_log_probs:
         output_log_probs = torch.empty((batch_size, max_sequence_length - 1, model.cfg.vocab), dtype=torch.float32,
@@ -297,6 +300,8 @@ def beam_search_and_return_on_first_stage(model, tokens=None, lengths=0, beam_si
         raise NotImplementedError("beam search over top-k / top-p filtered logits is not built")
     if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1:
         raise NotImplementedError("beam search is built for CP = 1 and TP = 1")
+    if getattr(model, "kv_cache_dtype", "bf16") != "bf16":
+        raise NotImplementedError("beam search on an FP8 KV cache is not built (set model.kv_cache_dtype = 'bf16')")
     if tokens is None or tokens.dim() != 2 or tokens.size(0) != 1:
         raise ValueError("beam search runs batch 1")                                       # :295-296
     if not BEAM_MIN <= beam_size <= BEAM_MAX:

@@ -20,6 +20,7 @@ import torch
 
 from . import context_parallel, ops, parallel_state as mpu, tracing, training_utils
 from .dot_product_attention import DotProductAttention
+from .inference_params import check_kv_cache_dtype
 from .language_model_embedding import LanguageModelEmbedding
 from .layers import ColumnParallelLinear
 from .rotary_pos_embedding import RotaryEmbedding
@@ -74,6 +75,17 @@ class GPTVLModel:
         # a prefill with a logit mask (CP = 1, TP = 1) runs the per-row tail of the LAST layer — attention, o-projection, MLP — only for
         # the rows the mask keeps; 0 runs the full layer (tests, A / B)
         self.trim_last_layer = bool(int(os.environ.get("VITA_TRIM_LAST_LAYER", "1")))
+        # what a prefill's KV cache holds: "bf16", or "fp8_e4m3" = e4m3 codes + one fp32 scale per (row, kv group), 0.516 of the
+        # bytes (CP = 1, TP = 1).  An InferenceParams with a kv_cache_dtype of its own overrides it
+        self.kv_cache_dtype = os.environ.get("VITA_KV_CACHE_DTYPE", "bf16")
+
+    @property
+    def kv_cache_dtype(self) -> str:
+        return self._kv_cache_dtype
+
+    @kv_cache_dtype.setter
+    def kv_cache_dtype(self, name: str):
+        self._kv_cache_dtype = check_kv_cache_dtype(name)
 
     # ---------------------------------------------------------------------------------------------
     @classmethod
@@ -122,7 +134,8 @@ class GPTVLModel:
         return ws
 
     def decoder_layer(self, h: torch.Tensor, lp: dict, cos, sin, ws, kv_dst: Optional[torch.Tensor] = None,
-                      cached_rows: Optional[int] = None, keep: Optional[tuple] = None) -> torch.Tensor:
+                      cached_rows: Optional[int] = None, keep: Optional[tuple] = None,
+                      kv_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
         """h [s, hidden] updated in place.  kv_dst [2, cap, groups, d]: this rank's cache shard for the
         layer; the rotated K and V rows of the local sequence are stored into rows [0, s).
         cached_rows = L (CP = 1): the s rows are NEW tokens behind L rows the shard already holds — their K / V go to rows
@@ -130,7 +143,9 @@ class GPTVLModel:
         keep = (idx int64 [n] on the device, [256-row query tiles that hold them]) on the LAST layer of a masked prefill (CP = 1,
         TP = 1): K / V of every row are computed and cached as ever, attention runs for those tiles only and the per-row rest of the
         layer for the n kept rows only, each with the arithmetic of the full layer; returns those rows [n, hidden] (h is left as the
-        layer found it).  A geometry whose attention takes no window runs the full layer and returns h."""
+        layer found it).  A geometry whose attention takes no window runs the full layer and returns h.
+        kv_scale [2, cap, groups] fp32: kv_dst is an FP8 cache (CP = 1): the rows are quantised into it (ops.kv8_store); the
+        layer's own attention reads the bf16 K / V of the mixed buffer as ever, so the prefill's logits do not depend on the cache."""
         c = self.cfg
         s = h.shape[0]
         cp = mpu.get_context_parallel_world_size()
@@ -142,7 +157,11 @@ class GPTVLModel:
         m5 = qkv.view(1, s, c.kv_groups, c.qpg + 2, c.head_dim)
         q5 = m5[:, :, :, : c.qpg]                                  # grouped query view, read in place
         if kv_dst is not None:
-            if use_cp:
+            if kv_scale is not None:
+                if use_cp or cached_rows is not None:
+                    raise NotImplementedError("an FP8 KV cache is filled by the CP = 1 prefill and the token step only")
+                ops.kv8_store(m5[0, :, :, c.qpg], m5[0, :, :, c.qpg + 1], kv_dst[0], kv_dst[1], kv_scale[0], kv_scale[1], row0)
+            elif use_cp:
                 context_parallel.unpack_kv(ws["kv"], out=kv_dst[:, :s])
             else:
                 kv_dst[0, row0: row0 + s].copy_(m5[0, :, :, c.qpg])
@@ -263,7 +282,8 @@ class GPTVLModel:
         for li, lp in enumerate(self.p["layers"]):                                        # self.decoder(...) :299
             with tracing.range(f"prefill: layer {li}"):
                 out = self.decoder_layer(h, lp, cos, sin, ws, None if ip is None else ip.key_value_memory_dict[li + 1],
-                                         keep=keep if li == last else None)
+                                         keep=keep if li == last else None,
+                                         kv_scale=None if ip is None else ip.kv_scale_dict.get(li + 1))
         if ip is not None:
             self._compact_cache(ip, s)
         tracing.push("prefill: final norm + masked head")
@@ -307,7 +327,17 @@ class GPTVLModel:
             raise ValueError("prefill_valid_tokens exceeds the tokens fed")
         room = max(0, ip.max_sequence_length - prompt)
         cap = s_local + -(-room // cp) + 1
-        buf = torch.empty(c.num_layers, 2, cap, c.kv_groups, c.head_dim, dtype=torch.bfloat16, device=device)
+        dtype = getattr(ip, "kv_cache_dtype", None) or self.kv_cache_dtype
+        ip.kv_scale_dict = {}
+        if dtype == "fp8_e4m3":
+            if cp > 1 or mpu.get_tensor_model_parallel_world_size() > 1 or self.force_cp_path:
+                raise NotImplementedError("the FP8 KV cache is built for CP = 1 and TP = 1")
+            lay = ops.kv8_cache_layout(c.num_layers, cap, c.kv_groups, c.head_dim)
+            buf = torch.empty(lay["codes"], dtype=ops.KV8_DTYPE, device=device)
+            scales = torch.empty(lay["scales"], dtype=torch.float32, device=device)
+            ip.kv_scale_dict = {li + 1: scales[li] for li in range(c.num_layers)}
+        else:
+            buf = torch.empty(c.num_layers, 2, cap, c.kv_groups, c.head_dim, dtype=torch.bfloat16, device=device)
         ip.key_value_memory_dict = {li + 1: buf[li] for li in range(c.num_layers)}    # Megatron keys by layer_number
         ip.prefill_valid_tokens = prompt
 
@@ -359,13 +389,22 @@ class GPTVLModel:
         length = row + (1 if owner else 0)
         for li, lp in enumerate(self.p["layers"]):
             kv = ip.key_value_memory_dict[li + 1]
+            sc = ip.kv_scale_dict.get(li + 1)                   # FP8 cache (CP = 1): codes in kv, scales here
             if length > kv.shape[1]:
                 raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
             x = ops.rmsnorm(h, lp["ln1"], c.eps, out=ws["x"])
             qkv = ops.gemv(x.view(-1), lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"].view(-1))
             ops.rope_qkv_(ws["qkv"], c.kv_groups, c.qpg, c.head_dim, cos, sin, None, 1)
             m4 = qkv.view(c.kv_groups, c.qpg + 2, c.head_dim)
-            if counters is not None:
+            if sc is not None:
+                # the append row is the device counter under the captured graph, the python-side count otherwise
+                ops.kv8_store(m4[None, :, c.qpg], m4[None, :, c.qpg + 1], kv[0], kv[1], sc[0], sc[1],
+                              counters[0] if counters is not None else row)
+                if counters is not None:
+                    pm, pl, po = ops.decode_attn_partial_kv8(m4[:, : c.qpg], kv[0], kv[1], sc[0], sc[1], kv.shape[1], len_dev=counters[1])
+                else:
+                    pm, pl, po = ops.decode_attn_partial_kv8(m4[:, : c.qpg], kv[0], kv[1], sc[0], sc[1], length)
+            elif counters is not None:
                 kv[0].index_copy_(0, counters[0], m4[None, :, c.qpg])
                 kv[1].index_copy_(0, counters[0], m4[None, :, c.qpg + 1])
                 pm, pl, po = ops.decode_attn_partial(m4[:, : c.qpg], kv[0], kv[1], kv.shape[1], len_dev=counters[1])
@@ -439,6 +478,16 @@ class GPTVLModel:
                 if cp > 1:
                     s.msg, s.gathered, s.n_ranks = ws["msg"].data_ptr(), ws["gmsg"].data_ptr(), cp
                 structs.append(s)
+            if ip.kv_scale_dict:                                  # FP8 cache: where vita_decode_layer_attn_kv8 finds codes and scales
+                extra["kv8"] = []
+                for li in range(len(structs)):
+                    kv, sc = ip.key_value_memory_dict[li + 1], ip.kv_scale_dict[li + 1]
+                    k8 = _L.Kv8Cache()
+                    k8.k_codes, k8.v_codes = kv[0].data_ptr(), kv[1].data_ptr()
+                    k8.code_row_stride, k8.code_group_stride = kv.stride(1), kv.stride(2)       # 1-byte elements: bytes
+                    k8.k_scales, k8.v_scales = sc[0].data_ptr(), sc[1].data_ptr()
+                    k8.scale_row_stride, k8.scale_group_stride = sc.stride(1), sc.stride(2)
+                    extra["kv8"].append(k8)
             st = ip._layer_structs = (structs, extra)
         structs, extra = st
         h = ops.row_gather(self.p["embed"], token.reshape(1), out=ws["h"], check_bounds=False)
@@ -453,9 +502,13 @@ class GPTVLModel:
         n_splits = ops.decode_splits(length)
         lib, stream = _L.load(), torch.cuda.current_stream().cuda_stream
         group = mpu.get_context_parallel_group() if cp > 1 else None
-        for s in structs:
+        kv8 = extra.get("kv8")
+        for li, s in enumerate(structs):
             s.append_row, s.len, s.n_splits = (row if owner else -1), length, n_splits
-            _L.check(lib.vita_decode_layer_attn(C.byref(s), stream), "vita_decode_layer_attn")
+            if kv8 is not None:
+                _L.check(lib.vita_decode_layer_attn_kv8(C.byref(s), C.byref(kv8[li]), stream), "vita_decode_layer_attn_kv8")
+            else:
+                _L.check(lib.vita_decode_layer_attn(C.byref(s), stream), "vita_decode_layer_attn")
             if cp > 1:
                 dist.all_gather_into_tensor(ws["gmsg"].view(-1), ws["msg"], group=group)
             _L.check(lib.vita_decode_layer_mlp(C.byref(s), stream), "vita_decode_layer_mlp")
@@ -515,7 +568,8 @@ class GPTVLModel:
                 raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
             logits = self._decode_graphed(input_ids[0], position_ids[0], ip).view(1, 1, -1).clone()
             return ops.logit_postprocess_(logits, self.cfg.output_multiplier_scale, self.cfg.output_logit_softcapping)
-        if t >= max(2, self.extend_min_tokens) and tp == 1 and mpu.get_context_parallel_world_size() == 1:
+        # the one-pass extend kernel reads a bf16 cache: an FP8 cache takes the per-token loop below
+        if t >= max(2, self.extend_min_tokens) and tp == 1 and mpu.get_context_parallel_world_size() == 1 and not ip.kv_scale_dict:
             return self._extend_forward(input_ids, position_ids, ip)
         ip._graph = None                      # eager steps move the python-side counters only
         # tensor parallelism (the released server runs TP 8 x CP 4, server_cp .sh:102-104): the kernel-by-kernel step, whose

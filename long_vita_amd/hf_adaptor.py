@@ -32,7 +32,7 @@ from typing import Optional
 import torch
 
 from . import checkpoint, generation, gpt_vl_model, lib, ops, vision
-from .inference_params import ForwardStep
+from .inference_params import ForwardStep, check_kv_cache_dtype
 
 
 def _get(cfg, name, default=None):
@@ -150,9 +150,19 @@ class LongVITAForCausalLM:
         self.cache_headroom = 4096          # rows a forward(use_cache=True) prefill leaves for generated tokens (generate() sizes it exactly)
         self.device_select = True           # penalty / sampling on the device (ops.select_token); False or VITA_DEVICE_SELECT=0: _sample_strategy
 
+    @property
+    def kv_cache_dtype(self) -> str:
+        """What the KV cache of forward(use_cache=True) / generate() holds: "bf16" (default) or "fp8_e4m3" (e4m3 codes + a scale
+        per row and kv group, about half the bytes).  Lives on the model (GPTVLModel.kv_cache_dtype)."""
+        return self.model.kv_cache_dtype
+
+    @kv_cache_dtype.setter
+    def kv_cache_dtype(self, name: str):
+        self.model.kv_cache_dtype = name
+
     # -- construction ---------------------------------------------------------------------------------
     @classmethod
-    def from_state_dict(cls, config, state_dict, device="cuda", generation_config=None):
+    def from_state_dict(cls, config, state_dict, device="cuda", generation_config=None, kv_cache_dtype=None):
         """state_dict: `LongVITAForCausalLM.state_dict()` names — `model.embed_tokens / layers.N.* / norm`, `lm_head`,
         `model.vision_model.*`, `model.vision_projection.*` (modeling_long_vita.py:67-68)."""
         lib.load(allow_build=False)                      # the HIP path or nothing
@@ -163,11 +173,14 @@ class LongVITAForCausalLM:
             vis = vision.MegatronVisionModel.from_oracle_layout(vcfg, vp, device)
         lp = checkpoint.hf_llm_to_params(state_dict, gcfg)
         model = gpt_vl_model.GPTVLModel.from_oracle_layout(gcfg, lp, external_feature_model=vis, device=device)
-        return cls(config, model, generation_config)
+        self = cls(config, model, generation_config)
+        if kv_cache_dtype is not None:
+            self.kv_cache_dtype = kv_cache_dtype
+        return self
 
     @classmethod
     def from_pretrained(cls, model_path, *model_args, torch_dtype=None, device_map=None, attn_implementation=None,
-                        trust_remote_code=None, device=None, **kwargs):
+                        trust_remote_code=None, device=None, kv_cache_dtype=None, **kwargs):
         """`AutoModelForCausalLM.from_pretrained(model_path, trust_remote_code=True, device_map=..., torch_dtype=torch.bfloat16,
         attn_implementation="flash_attention_2")` of inference_long_vita.py:811-817: config.json + *.safetensors of a `*_HF` directory."""
         if torch_dtype not in (None, torch.bfloat16, "bfloat16", "auto"):
@@ -180,7 +193,9 @@ class LongVITAForCausalLM:
             gen = types.SimpleNamespace(**{**dict(max_new_tokens=20, do_sample=False, use_cache=True, top_k=0, top_p=0.0, temperature=1.0,
                                                   eos_token_id=config.get("eos_token_id"), pad_token_id=config.get("pad_token_id")), **g})
         dev = device or (device_map if isinstance(device_map, (str, torch.device)) and device_map != "auto" else "cuda")
-        return cls.from_state_dict(config, checkpoint.load_hf_safetensors(model_path), device=dev, generation_config=gen)
+        check_kv_cache_dtype(kv_cache_dtype, allow_none=True)       # before the weights are read
+        return cls.from_state_dict(config, checkpoint.load_hf_safetensors(model_path), device=dev, generation_config=gen,
+                                   kv_cache_dtype=kv_cache_dtype)
 
     def eval(self):
         return self
@@ -202,8 +217,9 @@ class LongVITAForCausalLM:
                 position_ids: Optional[torch.Tensor] = None, past_key_values=None, inputs_embeds: Optional[torch.Tensor] = None,
                 labels=None, use_cache: Optional[bool] = None, output_attentions: Optional[bool] = None,
                 output_hidden_states: Optional[bool] = None, return_dict: Optional[bool] = None, cache_position=None,
-                num_logits_to_keep: int = 0, **kwargs):
-        """modeling_long_vita.py:250-327.  logits [1, n, vocab] bf16 for the last `num_logits_to_keep` rows (0: every row, as there)."""
+                num_logits_to_keep: int = 0, kv_cache_dtype: Optional[str] = None, **kwargs):
+        """modeling_long_vita.py:250-327.  logits [1, n, vocab] bf16 for the last `num_logits_to_keep` rows (0: every row, as there).
+        kv_cache_dtype: the format of the cache a use_cache=True prefill allocates (None: self.kv_cache_dtype)."""
         if (input_ids is None) == (inputs_embeds is None):
             raise ValueError("You must specify exactly one of input_ids or inputs_embeds")                 # :127-128
         if labels is not None:
@@ -256,6 +272,7 @@ class LongVITAForCausalLM:
             step = ForwardStep(self.model, 1, s + self.cache_headroom)
             ip = step.inference_params
             ip.external_inputs, ip.logit_mask = ext, mask
+            ip.kv_cache_dtype = kv_cache_dtype
             if dec_in is not None:
                 raise NotImplementedError("inputs_embeds with use_cache=True")
             logits = step(input_ids, pos, None)
@@ -283,8 +300,17 @@ class LongVITAForCausalLM:
         rows = max(need + max(int(self.cache_headroom), 1), cap + cap // 2)
         buf = torch.empty((layers, 2, rows) + tuple(old.shape[2:]), dtype=old.dtype, device=old.device)
         for li in range(layers):
-            buf[li, :, : ip.local_len].copy_(kv[li + 1][:, : ip.local_len])
+            if old.dtype == ops.KV8_DTYPE:                   # codes move as bytes
+                buf[li, :, : ip.local_len].view(torch.uint8).copy_(kv[li + 1][:, : ip.local_len].view(torch.uint8))
+            else:
+                buf[li, :, : ip.local_len].copy_(kv[li + 1][:, : ip.local_len])
         ip.key_value_memory_dict = {li + 1: buf[li] for li in range(layers)}
+        scales = getattr(ip, "kv_scale_dict", None)
+        if scales:                                           # an FP8 cache: the rows' scales move with their codes
+            sbuf = torch.empty((layers, 2, rows) + tuple(scales[1].shape[2:]), dtype=torch.float32, device=old.device)
+            for li in range(layers):
+                sbuf[li, :, : ip.local_len].copy_(scales[li + 1][:, : ip.local_len])
+            ip.kv_scale_dict = {li + 1: sbuf[li] for li in range(layers)}
         ip.max_sequence_length = max(ip.max_sequence_length, ip.sequence_len_offset + n_new + int(self.cache_headroom))
         ip._graph = None
         ip._layer_structs = None
@@ -294,13 +320,18 @@ class LongVITAForCausalLM:
     def generate(self, inputs: Optional[torch.Tensor] = None, images: Optional[torch.Tensor] = None,
                  image_indices: Optional[torch.Tensor] = None, input_ids: Optional[torch.Tensor] = None, generation_config=None,
                  max_new_tokens: Optional[int] = None, do_sample: Optional[bool] = None, eos_token_id=None, past_key_values=None,
-                 return_dict_in_generate: bool = False, **kwargs):
+                 return_dict_in_generate: bool = False, kv_cache_dtype: Optional[str] = None, **kwargs):
         """`model.generate(inputs=inputs, images=images, image_indices=image_indices)` (inference_long_vita.py:868): one prefill over
         the prompt (ViT + scatter + decoder), then one cached step per token; stops behind the first end-of-sequence token.  Returns
         [1, prompt + generated] like transformers' greedy search.
         past_key_values = the cache of an earlier call and inputs = the WHOLE conversation (as transformers takes it): only the tokens
         behind cache.get_seq_length() are fed, in one extend step, then one cached step per token.  return_dict_in_generate: an object
-        with `sequences` and `past_key_values` (the cache holds everything but the last generated token, as transformers' does)."""
+        with `sequences` and `past_key_values` (the cache holds everything but the last generated token, as transformers' does).
+        kv_cache_dtype: "bf16" or "fp8_e4m3" for the cache this call allocates (None: self.kv_cache_dtype); a cache handed in keeps
+        its own format.  There is no beam search on an FP8 cache: num_beams > 1 raises NotImplementedError there."""
+        cache_dtype = check_kv_cache_dtype(kv_cache_dtype, allow_none=True) or self.kv_cache_dtype
+        if cache_dtype != "bf16" and int(kwargs.get("num_beams") or 1) > 1:
+            raise NotImplementedError("beam search on an FP8 KV cache is not built")
         ids = inputs if inputs is not None else input_ids
         if ids is None or ids.dim() != 2 or ids.shape[0] != 1:
             raise ValueError("generate(inputs=[1, S] token ids) — the Long-VITA path runs batch 1")
@@ -319,7 +350,8 @@ class LongVITAForCausalLM:
                 raise NotImplementedError("repetition_penalty needs the device selection (model.device_select / VITA_DEVICE_SELECT)")
         kw = dict(do_sample=do_sample, top_k=top_k if do_sample else 0, top_p=top_p if do_sample else 0.0, temperature=temperature)
         if past_key_values is not None or return_dict_in_generate:
-            return self._generate_cached(ids, images, image_indices, past_key_values, n_new, eos, kw, select, return_dict_in_generate)
+            return self._generate_cached(ids, images, image_indices, past_key_values, n_new, eos, kw, select, return_dict_in_generate,
+                                         kv_cache_dtype)
         pad = _get(gc, "pad_token_id")
         tokens = torch.full((1, s + n_new), 0 if pad is None else int(pad), dtype=torch.long, device=self.device)
         tokens[:, :s] = ids
@@ -328,7 +360,8 @@ class LongVITAForCausalLM:
         loop = generation.generate_tokens_probs_and_return_on_first_stage(
             self.model, tokens, lengths, external_inputs=self._external_inputs(images, image_indices),
             use_kv_cache=bool(_get(gc, "use_cache", True)), logit_mask=True, termination_id=None,
-            token_selector=None if select is None else (lambda logits, context_length: select(logits)), **kw)
+            token_selector=None if select is None else (lambda logits, context_length: select(logits)),
+            kv_cache_dtype=kv_cache_dtype, **kw)
         for out, _, _ in loop:
             if int(out[0, -1]) in eos:
                 break
@@ -361,7 +394,7 @@ class LongVITAForCausalLM:
                                     top_k=top_k, top_p=top_p, u=u[j:j + 1] if do_sample else None, mark_chosen=True)
         return select
 
-    def _generate_cached(self, ids, images, image_indices, cache, n_new, eos, kw, select, return_dict):
+    def _generate_cached(self, ids, images, image_indices, cache, n_new, eos, kw, select, return_dict, kv_cache_dtype=None):
         """The decode loop over forward(past_key_values=): the uncached part of `ids` in one call (a prefill without a cache, an extend
         step behind one), then single-token steps; the token choice (`select`: the device selector, or None) and the stopping rule are the loop's above."""
         s = ids.shape[1]
@@ -374,7 +407,8 @@ class LongVITAForCausalLM:
                                  "with at least one token the cache has not seen (its logits start the answer)")
             out = self.forward(input_ids=ids[:, seen:], past_key_values=cache, num_logits_to_keep=1)
         else:
-            out = self.forward(input_ids=ids, images=images, image_indices=image_indices, use_cache=True, num_logits_to_keep=1)
+            out = self.forward(input_ids=ids, images=images, image_indices=image_indices, use_cache=True, num_logits_to_keep=1,
+                               kv_cache_dtype=kv_cache_dtype)
         cache = out.past_key_values
         seq = ids
         for j in range(n_new):

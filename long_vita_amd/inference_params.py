@@ -19,13 +19,31 @@ from __future__ import annotations
 import torch
 
 
+KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")
+
+
+def check_kv_cache_dtype(name, allow_none: bool = False):
+    """The cache formats this package keeps: "bf16" (the default) and "fp8_e4m3" (OCP e4m3fn codes + one fp32 scale per row and
+    kv group).  Anything else is a ValueError."""
+    if name is None and allow_none:
+        return None
+    if name not in KV_CACHE_DTYPES:
+        raise ValueError(f"kv_cache_dtype must be one of {KV_CACHE_DTYPES}, got {name!r}")
+    return name
+
+
 class InferenceParams:
-    def __init__(self, max_batch_size: int, max_sequence_length: int):
+    def __init__(self, max_batch_size: int, max_sequence_length: int, kv_cache_dtype=None):
         self.max_sequence_length = max_sequence_length
         self.max_batch_size = max_batch_size
         self.sequence_len_offset = 0
         self.batch_size_offset = 0
         self.key_value_memory_dict = {}
+        # "bf16" | "fp8_e4m3" | None = the model's setting (GPTVLModel.kv_cache_dtype), resolved when the prefill allocates.  On an
+        # FP8 cache key_value_memory_dict[layer_number] is [2, capacity, kv_groups, head_dim] torch.float8_e4m3fn and
+        # kv_scale_dict[layer_number] the fp32 scales [2, capacity, kv_groups]
+        self.kv_cache_dtype = kv_cache_dtype
+        self.kv_scale_dict = {}
         # attributes the Long-VITA decode loop attaches
         self.external_inputs = None
         self.logit_mask = None
@@ -42,6 +60,18 @@ class InferenceParams:
         self.beam_tails = {}
         self.beam_ancestry = None
 
+    @property
+    def kv_cache_dtype(self):
+        return self._kv_cache_dtype
+
+    @kv_cache_dtype.setter
+    def kv_cache_dtype(self, name):
+        self._kv_cache_dtype = check_kv_cache_dtype(name, allow_none=True)
+
+    @property
+    def kv_cache_is_fp8(self) -> bool:
+        return bool(self.kv_scale_dict) or self._kv_cache_dtype == "fp8_e4m3"
+
     def begin_beams(self, beams: int, tail_cap: int, device=None):
         """Turn the batch-1 cache of a prefilled prompt into the shared prefix of `beams` beams (beam search,
         M/inference/text_generation/generation.py:283-471; CP = 1).  The shard's rows [0, local_len) stay where they are,
@@ -51,6 +81,8 @@ class InferenceParams:
         been reordered.  beam_n_gen counts the steps stored."""
         if not 1 <= beams or tail_cap < 1:
             raise ValueError("begin_beams: beams >= 1 and tail_cap >= 1")
+        if self.kv_cache_is_fp8:
+            raise NotImplementedError("beam search on an FP8 KV cache is not built (the beam attention reads a bf16 prefix)")
         self.beams, self.beam_n_gen, self.beam_prefix_len = int(beams), 0, self.local_len
         self.beam_tails = {}
         if self.key_value_memory_dict:
@@ -79,6 +111,7 @@ class InferenceParams:
         self.sequence_len_offset = 0
         self.batch_size_offset = 0
         self.key_value_memory_dict = {}
+        self.kv_scale_dict = {}
         self.prefill_valid_tokens = None
         self.local_len = 0
         self.decode_steps = 0

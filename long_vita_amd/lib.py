@@ -139,6 +139,15 @@ class DecodeLayerParams(C.Structure):
     ]
 
 
+class Kv8Cache(C.Structure):
+    """Mirror of ``vita_kv8_cache`` (include/vita_hip.h)."""
+
+    _fields_ = [
+        ("k_codes", C.c_void_p), ("v_codes", C.c_void_p), ("code_row_stride", C.c_int64), ("code_group_stride", C.c_int64),
+        ("k_scales", C.c_void_p), ("v_scales", C.c_void_p), ("scale_row_stride", C.c_int64), ("scale_group_stride", C.c_int64),
+    ]
+
+
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list EVERY function declared in include/vita_hip.h
@@ -242,6 +251,10 @@ PROTOTYPES = {
     "vita_beam_attn_fwd": (_i, [_p, _l, _l, _l, _p, _p, _l, _l, _l, _p, _p, _l, _p, _i, _i, _i, _i, _i, _f, _p, _p, C.c_size_t, _p]),
     "vita_beam_candidates_workspace_bytes": (_l, [_l, _l]),
     "vita_beam_candidates": (_i, [_p, _l, _l, _l, _p, _f, _i, _p, _p, _p, _l, _p]),
+    # FP8 (e4m3) KV cache for the cached decode
+    "vita_kv8_store": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _p, _l, _l, _p, _p, _l, _l, _l, _p, _l, _p]),
+    "vita_decode_attn_partial_kv8": (_i, [_p, _l, _l, _p, _p, _l, _l, _p, _p, _l, _l, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
+    "vita_decode_layer_attn_kv8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(Kv8Cache), _p]),
 }
 
 _lock = threading.Lock()

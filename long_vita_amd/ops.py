@@ -1118,6 +1118,82 @@ def decode_attn_merge(pm: torch.Tensor, pl: torch.Tensor, po: torch.Tensor, fina
 
 
 # ------------------------------------------------------------------------------------------------
+# FP8 (e4m3) KV cache for the cached decode (include/vita_hip.h: vita_kv8_*)
+# ------------------------------------------------------------------------------------------------
+KV8_DTYPE = torch.float8_e4m3fn          # OCP e4m3fn, what gfx950 converts natively (not MI300's fnuz)
+KV8_MAX = 448.0
+
+
+def kv8_cache_layout(layers: int, capacity: int, groups: int, head_dim: int = 128) -> dict:
+    """Pure layout, no allocation: shapes of the code and scale tensors of an FP8 cache and what a cached token costs.
+    codes [layers, 2, capacity, groups, head_dim] e4m3 (1 byte), scales [layers, 2, capacity, groups] fp32: K and V of a
+    (row, kv group) each carry one scale."""
+    token = layers * 2 * groups * (head_dim + 4)
+    token_bf16 = layers * 2 * groups * head_dim * 2
+    return {"codes": (layers, 2, capacity, groups, head_dim), "scales": (layers, 2, capacity, groups),
+            "bytes_per_token": token, "bytes_per_token_bf16": token_bf16, "ratio": token / token_bf16,
+            "bytes": token * capacity}
+
+
+def _kv8_views(k_codes, v_codes, k_scales, v_scales, what):
+    cap, G, d = k_codes.shape
+    if k_codes.dtype not in (KV8_DTYPE, torch.uint8) or v_codes.dtype != k_codes.dtype:
+        raise ValueError(f"{what}: codes must be {KV8_DTYPE} (or their bytes as uint8)")
+    if v_codes.shape != k_codes.shape or v_codes.stride() != k_codes.stride() or k_codes.stride(2) != 1:
+        raise ValueError(f"{what}: code views [cap, G, d] must share shape and strides, unit inner stride")
+    if tuple(k_scales.shape) != (cap, G) or v_scales.shape != k_scales.shape or v_scales.stride() != k_scales.stride():
+        raise ValueError(f"{what}: scale views [cap, G] must share shape and strides")
+    return cap, G, d
+
+
+def kv8_store(k_src: torch.Tensor, v_src: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_scales: torch.Tensor,
+              v_scales: torch.Tensor, row0) -> None:
+    """Quantise K / V head rows k_src, v_src [rows, G, d] (bf16 views of the mixed qkv buffer, shared strides, unit inner stride)
+    into rows row0 .. row0 + rows of the cache views k_codes / v_codes [cap, G, d] and k_scales / v_scales [cap, G] fp32.
+    row0: an int, or an int64 [1] device tensor read by the kernel (the captured token step)."""
+    cap, G, d = _kv8_views(k_codes, v_codes, k_scales, v_scales, "kv8_store")
+    rows = k_src.shape[0]
+    if tuple(k_src.shape) != (rows, G, d) or v_src.shape != k_src.shape or v_src.stride() != k_src.stride() or k_src.stride(2) != 1:
+        raise ValueError("kv8_store: sources [rows, G, d] with shared strides and unit inner stride")
+    on_dev = isinstance(row0, torch.Tensor)
+    if not on_dev and (row0 < 0 or row0 + rows > cap):
+        raise ValueError("kv8_store: rows do not fit the cache")
+    if rows == 0:
+        return
+    _L.check(_L.load().vita_kv8_store(_dev(k_src, "k_src", BF16), _dev(v_src, "v_src", BF16), k_src.stride(0), k_src.stride(1), rows,
+                                      G, d, _dev(k_codes, "k_codes"), _dev(v_codes, "v_codes"), k_codes.stride(0), k_codes.stride(1),
+                                      _dev(k_scales, "k_scales", torch.float32), _dev(v_scales, "v_scales", torch.float32),
+                                      k_scales.stride(0), k_scales.stride(1), 0 if on_dev else int(row0),
+                                      _dev(row0, "row0", torch.int64) if on_dev else None, cap, _stream()), "vita_kv8_store")
+
+
+def decode_attn_partial_kv8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_scales: torch.Tensor,
+                            v_scales: torch.Tensor, length: int, softmax_scale: Optional[float] = None,
+                            len_dev: Optional[torch.Tensor] = None):
+    """decode_attn_partial over an FP8 cache (code views [cap, G, d], scale views [cap, G]): the same partials, for decode_attn_merge."""
+    G, qpg, d = q.shape
+    cap, G2, d2 = _kv8_views(k_codes, v_codes, k_scales, v_scales, "decode_attn_partial_kv8")
+    if (G2, d2) != (G, d) or q.stride(2) != 1 or length > cap:
+        raise ValueError("decode_attn_partial_kv8: q [G, qpg, d], caches [cap, G, d] holding `length` rows")
+    H = G * qpg
+    n = DECODE_MAX_SPLITS if len_dev is not None else decode_splits(length)
+    pm = torch.empty(n, H, dtype=torch.float32, device=q.device)
+    pl = torch.empty(n, H, dtype=torch.float32, device=q.device)
+    po = torch.empty(n, H, d, dtype=torch.float32, device=q.device)
+    if length == 0:
+        pm.fill_(float("-inf")); pl.zero_(); po.zero_()
+        return pm, pl, po
+    scale = 1.0 / math.sqrt(d) if softmax_scale is None else softmax_scale
+    _L.check(_L.load().vita_decode_attn_partial_kv8(_dev(q, "q", BF16), q.stride(0), q.stride(1), _dev(k_codes, "k_codes"),
+                                                    _dev(v_codes, "v_codes"), k_codes.stride(0), k_codes.stride(1),
+                                                    _dev(k_scales, "k_scales", torch.float32), _dev(v_scales, "v_scales", torch.float32),
+                                                    k_scales.stride(0), k_scales.stride(1), int(length),
+                                                    _opt(len_dev, "len_dev", torch.int32), n, G, qpg, d, float(scale), _dev(pm, "pm"),
+                                                    _dev(pl, "pl"), _dev(po, "po"), _stream()), "vita_decode_attn_partial_kv8")
+    return pm, pl, po
+
+
+# ------------------------------------------------------------------------------------------------
 # beam search on a shared-prefix KV cache (M/inference/text_generation/generation.py:283-471)
 # ------------------------------------------------------------------------------------------------
 BEAM_MAX = 8
