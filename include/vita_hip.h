@@ -765,6 +765,42 @@ int vita_decode_attn_partial_kv8(const void* q, int64_t q_group_stride, int64_t 
 int vita_decode_layer_attn_kv8(const vita_decode_layer_params* p, const vita_kv8_cache* c, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * FP8 decoder weights for the cached token step (opt-in, CP = 1 and TP = 1).  The four linears of a decoder layer
+ * (linear_qkv, linear_proj, linear_fc1, linear_fc2) are kept a second time as OCP e4m3fn codes [N][K] (1 byte per element, row
+ * stride in BYTES, a multiple of 16, pointer 16-byte aligned) plus one fp32 scale per run of 128 consecutive K elements of a row,
+ * scales [N][K / 128] dense: 0.516 of the bf16 bytes.  The rule is the KV cache's, per run w[0..127]: amax = max |w_i|;
+ * s = amax > 0 ? amax / 448 : 1; code_i = e4m3fn_rne(w_i / s) (fp32, IEEE division, no clamp); the GEMV computes with
+ * f32(code_i) * s.  K must be a multiple of 128 (else VITA_ERR_UNSUPPORTED, as for misaligned codes or scales).
+ *
+ * vita_w8_quantize: W [N][K] bf16 (row stride ldw in elements, a multiple of 8, pointer 16-byte aligned) -> codes and scales.
+ *   Bytes of a code row behind K are not written.  Runs once per weight.
+ * vita_gemv_w8: vita_gemv_bf16 over codes and scales: y[N] = epilogue(dequant(codes, scales)[N,K] . x[K]), the epilogues NONE /
+ *   BIAS / RESIDUAL / SWIGLU (codes and scales of cat[gate, up], 2 N rows) with vita_gemv_bf16's rounding chain; gamma != NULL:
+ *   x is RMS-normalised first (gamma [K], eps) with the arithmetic the fused layer entries use on the bf16 path.  The products are
+ *   summed in fp32, a run's scale multiplies a lane's finished partial sum, nothing is rounded to bf16 in front of the epilogue.
+ *   Rows behind N and columns behind K are never read.
+ * vita_decode_layer_attn_w8 / vita_decode_layer_mlp_w8: vita_decode_layer_attn / _mlp with the four GEMVs of the layer reading
+ *   the codes and scales of `w` (dense: row stride K); qkv_w, o_w, fc1_w and fc2_w of the parameter struct are not read.
+ *   kv8 != NULL: the cache is the FP8 cache it describes, as for vita_decode_layer_attn_kv8; NULL: the bf16 cache of the
+ *   parameter struct.  The same kernels as vita_gemv_w8 and the separate attention entries, bit for bit.  hidden and ffn must be
+ *   multiples of 128.
+ * Stand behind the linears of M/core/tensor_parallel/layers.py:825 at sq = 1, under the decode loop
+ * M/inference/text_generation/generation.py:127-131. */
+typedef struct {
+  const void *qkv_codes, *o_codes, *fc1_codes, *fc2_codes;      /* e4m3fn [N][K], dense, 16-byte aligned */
+  const void *qkv_scales, *o_scales, *fc1_scales, *fc2_scales;  /* fp32 [N][K / 128], dense */
+} vita_w8_layer;
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
+int vita_w8_quantize(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, int64_t ldc_bytes, void* scales, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
+int vita_gemv_w8(const void* x, const void* codes, int64_t ldc_bytes, const void* scales, void* y, int64_t N, int64_t K,
+                 int epilogue, const void* bias, const void* R, const void* gamma, float eps, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
+int vita_decode_layer_attn_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, const vita_kv8_cache* kv8, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
+int vita_decode_layer_mlp_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Frame / image preprocessing — ImageProcessor.process_images and dynamic_preprocess,
  * H/data/processor/image_processor.py:180-223,404-448, then the bf16 cast of
  * M/tasks/inference/module.py:693.  frames [n][height][width][3] uint8 RGB (frame_stride bytes apart)

@@ -13,40 +13,6 @@
 
 namespace {
 
-__device__ __forceinline__ float dot8(const u32x4 a, const u32x4 b) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    s += bf16lo_to_f32(a[j]) * bf16lo_to_f32(b[j]) + bf16hi_to_f32(a[j]) * bf16hi_to_f32(b[j]);
-  return s;
-}
-
-// ---- what gemv_kernel and gemv_rows_kernel share -----------------------------------------------------------------------------
-// One 16-byte vector of the RMS-normalised x: bf16(bf16(x * rstd) * gamma), as vita_rmsnorm_fwd rounds it.
-// The two kernels do NOT share the sum of squares behind rstd, on purpose: gemv_kernel adds dot8(x, x) per vector (eight products,
-// then one add into the sum), gemv_rows_kernel adds pair by pair as rmsnorm_fwd_kernel does, which is what makes its normalised row
-// bit-equal to vita_rmsnorm_fwd.  The two orders can round rstd differently; changing either changes output bits.
-__device__ __forceinline__ u32x4 gemv_norm_x(u32x4 xv, const float rstd, const u32x4 gv) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    xv[j] = pack_bf16x2(bf16_round(bf16lo_to_f32(xv[j]) * rstd) * bf16lo_to_f32(gv[j]),
-                        bf16_round(bf16hi_to_f32(xv[j]) * rstd) * bf16hi_to_f32(gv[j]));
-  return xv;
-}
-// s0 (and s1, SWIGLU's "up" row) = the wave's dot products; bias / residual = the output's element where EPI reads one (GEMV_ELEM)
-#define GEMV_ELEM(E, ptr, i) (EPI == (E) ? bf16_to_f32((ptr)[i]) : 0.f)
-template <int EPI>
-__device__ __forceinline__ bf16_t gemv_epilogue(const float s0, const float s1, const float bias, const float residual) {
-  float o = s0;
-  if (EPI == VITA_EPI_BIAS) o += bias;
-  if (EPI == VITA_EPI_RESIDUAL) o = bf16_round(o) + residual;
-  if (EPI == VITA_EPI_SWIGLU) {                     // same rounding chain as the GEMM epilogue
-    const float g = bf16_round(s0), u = bf16_round(s1);
-    o = bf16_round(g / (1.0f + __expf(-g))) * u;
-  }
-  return f32_to_bf16(o);
-}
-
 // ---- y[N] = epilogue(W[N,K] . norm(x)[K]) : one wave per output, 16-byte pieces of the W row per lane ----
 // NORM: x is RMS-normalised on the fly; every wave recomputes the 10 KB sum of squares (L2-resident) instead of a separate
 // launch + round trip.
@@ -510,23 +476,33 @@ bool decode_layer_args_ok(const vita_decode_layer_params* p) {
 }
 }  // namespace
 
-extern "C" int vita_decode_layer_attn(const vita_decode_layer_params* p, void* stream) {
-  if (!decode_layer_args_ok(p) || !p->ln1 || !p->qkv_w || !p->qkv_b || !p->cos || !p->sin || !p->k_cache || !p->v_cache ||
-      !p->part_m || !p->part_l || !p->part_o)
-    return VITA_ERR_INVALID_ARG;
-  if (p->head_dim != 128 || (p->hidden & 7) || p->len < 0 || p->len > p->capacity || p->append_row >= p->capacity ||
-      p->n_splits <= 0)
-    return VITA_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int qpg = p->heads / p->kv_groups;
-  const int64_t qkv_out = (int64_t)(p->heads + 2 * p->kv_groups) * p->head_dim;
-  launch_gemv<VITA_EPI_BIAS, true>(p->h, p->qkv_w, p->hidden, p->qkv, qkv_out, p->hidden, p->qkv_b, nullptr, p->ln1, p->eps, st);
-  hipLaunchKernelGGL(rope_append_kernel, dim3(4), dim3(256), 0, st, (bf16_t*)p->qkv, p->kv_groups, qpg, p->head_dim,
-                     (const bf16_t*)p->cos, (const bf16_t*)p->sin, (bf16_t*)p->k_cache, (bf16_t*)p->v_cache,
-                     p->kv_row_stride, p->kv_group_stride, p->append_row);
+namespace {
+// what the attention entries check of an FP8 cache, and everything they do behind the QKV GEMV: RoPE + K / V append, the split
+// attention and the merge.  c != NULL: the cache is the FP8 cache it describes (kv8.hip).
+bool w8_misaligned(const void* codes, const void* scales) { return ((uintptr_t)codes & 15) || ((uintptr_t)scales & 3); }
+bool kv8_cache_null(const vita_kv8_cache* c) { return !c || !c->k_codes || !c->v_codes || !c->k_scales || !c->v_scales; }
+bool kv8_cache_misaligned(const vita_kv8_cache* c) {
+  return (c->code_row_stride & 7) || (c->code_group_stride & 7) || (((uintptr_t)c->k_codes | (uintptr_t)c->v_codes) & 7) ||
+         (((uintptr_t)c->k_scales | (uintptr_t)c->v_scales) & 3);
+}
+int decode_layer_attn_tail(const vita_decode_layer_params* p, const vita_kv8_cache* c, hipStream_t st) {
+  const int qpg = p->heads / p->kv_groups, hpg = qpg + 2;
   const int H = p->heads, D = p->head_dim;
+  int rc = VITA_OK;
+  if (c) {
+    rc = vita_kv8_rope_append(p->qkv, p->kv_groups, qpg, D, p->cos, p->sin, c, p->append_row, st);
+    if (rc != VITA_OK) return rc;
+  } else {
+    hipLaunchKernelGGL(rope_append_kernel, dim3(4), dim3(256), 0, st, (bf16_t*)p->qkv, p->kv_groups, qpg, p->head_dim,
+                       (const bf16_t*)p->cos, (const bf16_t*)p->sin, (bf16_t*)p->k_cache, (bf16_t*)p->v_cache,
+                       p->kv_row_stride, p->kv_group_stride, p->append_row);
+  }
   if (p->len > 0) {
-    const int rc = launch_decode_partial(p, st);
+    rc = c ? vita_decode_attn_partial_kv8(p->qkv, (int64_t)hpg * D, D, c->k_codes, c->v_codes, c->code_row_stride,
+                                          c->code_group_stride, c->k_scales, c->v_scales, c->scale_row_stride,
+                                          c->scale_group_stride, p->len, nullptr, p->n_splits, p->kv_groups, qpg, D,
+                                          p->softmax_scale, p->part_m, p->part_l, p->part_o, st)
+           : launch_decode_partial(p, st);
     if (rc != VITA_OK) return rc;
   }
   const int nparts = p->len > 0 ? p->n_splits : 0;
@@ -538,55 +514,93 @@ extern "C" int vita_decode_layer_attn(const vita_decode_layer_params* p, void* s
   return vita_decode_attn_merge(p->part_m, p->part_l, p->part_o, nparts, H, (int64_t)H * D, H, D, nullptr, nullptr, nullptr,
                                 p->ctx, st);
 }
+// the MLP entries' first step at CP > 1: merge the ranks' partials into the context
+int decode_layer_merge_ranks(const vita_decode_layer_params* p, hipStream_t st) {
+  if (!p->gathered) return VITA_OK;
+  if (p->n_ranks <= 0) return VITA_ERR_INVALID_ARG;
+  const int H = p->heads, D = p->head_dim;
+  const float* g = (const float*)p->gathered;
+  const int64_t msg_len = (int64_t)H * D + 2 * H;
+  return vita_decode_attn_merge(g + (int64_t)H * D, g + (int64_t)H * D + H, g, p->n_ranks, msg_len, msg_len, H, D, nullptr, nullptr,
+                                nullptr, p->ctx, st);
+}
+}  // namespace
 
-// the same layer over an FP8 cache (kv8.hip): the same QKV GEMV and merge, RoPE + quantised append, attention on codes + scales
-extern "C" int vita_decode_layer_attn_kv8(const vita_decode_layer_params* p, const vita_kv8_cache* c, void* stream) {
-  if (!decode_layer_args_ok(p) || !c || !p->ln1 || !p->qkv_w || !p->qkv_b || !p->cos || !p->sin || !c->k_codes || !c->v_codes ||
-      !c->k_scales || !c->v_scales || !p->part_m || !p->part_l || !p->part_o)
+extern "C" int vita_decode_layer_attn(const vita_decode_layer_params* p, void* stream) {
+  if (!decode_layer_args_ok(p) || !p->ln1 || !p->qkv_w || !p->qkv_b || !p->cos || !p->sin || !p->k_cache || !p->v_cache ||
+      !p->part_m || !p->part_l || !p->part_o)
     return VITA_ERR_INVALID_ARG;
-  const int qpg = p->heads / p->kv_groups, hpg = qpg + 2;
-  if (p->head_dim != 128 || qpg > 8 || (p->hidden & 7) || p->len < 0 || p->len > p->capacity || p->append_row >= p->capacity ||
-      p->n_splits <= 0 || (c->code_row_stride & 7) || (c->code_group_stride & 7) ||
-      (((uintptr_t)c->k_codes | (uintptr_t)c->v_codes) & 7) || (((uintptr_t)c->k_scales | (uintptr_t)c->v_scales) & 3))
+  if (p->head_dim != 128 || (p->hidden & 7) || p->len < 0 || p->len > p->capacity || p->append_row >= p->capacity ||
+      p->n_splits <= 0)
     return VITA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int64_t qkv_out = (int64_t)(p->heads + 2 * p->kv_groups) * p->head_dim;
   launch_gemv<VITA_EPI_BIAS, true>(p->h, p->qkv_w, p->hidden, p->qkv, qkv_out, p->hidden, p->qkv_b, nullptr, p->ln1, p->eps, st);
-  int rc = vita_kv8_rope_append(p->qkv, p->kv_groups, qpg, p->head_dim, p->cos, p->sin, c, p->append_row, st);
+  return decode_layer_attn_tail(p, nullptr, st);
+}
+
+// the same layer over an FP8 cache (kv8.hip): the same QKV GEMV and merge, RoPE + quantised append, attention on codes + scales
+extern "C" int vita_decode_layer_attn_kv8(const vita_decode_layer_params* p, const vita_kv8_cache* c, void* stream) {
+  if (!decode_layer_args_ok(p) || kv8_cache_null(c) || !p->ln1 || !p->qkv_w || !p->qkv_b || !p->cos || !p->sin || !p->part_m ||
+      !p->part_l || !p->part_o)
+    return VITA_ERR_INVALID_ARG;
+  if (p->head_dim != 128 || p->heads / p->kv_groups > 8 || (p->hidden & 7) || p->len < 0 || p->len > p->capacity ||
+      p->append_row >= p->capacity || p->n_splits <= 0 || kv8_cache_misaligned(c))
+    return VITA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t qkv_out = (int64_t)(p->heads + 2 * p->kv_groups) * p->head_dim;
+  launch_gemv<VITA_EPI_BIAS, true>(p->h, p->qkv_w, p->hidden, p->qkv, qkv_out, p->hidden, p->qkv_b, nullptr, p->ln1, p->eps, st);
+  return decode_layer_attn_tail(p, c, st);
+}
+
+// the same layer with FP8 weights (w8.hip): the four GEMVs read codes + scales, everything between them is unchanged
+extern "C" int vita_decode_layer_attn_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, const vita_kv8_cache* c,
+                                         void* stream) {
+  if (!decode_layer_args_ok(p) || !w || !w->qkv_codes || !w->qkv_scales || !p->ln1 || !p->qkv_b || !p->cos || !p->sin ||
+      !p->part_m || !p->part_l || !p->part_o || (c ? kv8_cache_null(c) : (!p->k_cache || !p->v_cache)))
+    return VITA_ERR_INVALID_ARG;
+  if (p->head_dim != 128 || p->heads / p->kv_groups > 8 || (p->hidden & 127) || p->len < 0 || p->len > p->capacity ||
+      p->append_row >= p->capacity || p->n_splits <= 0 || (c && kv8_cache_misaligned(c)) ||
+      w8_misaligned(w->qkv_codes, w->qkv_scales) || (((uintptr_t)p->h | (uintptr_t)p->ln1) & 15))
+    return VITA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t qkv_out = (int64_t)(p->heads + 2 * p->kv_groups) * p->head_dim;
+  const int rc = vita_gemv_w8(p->h, w->qkv_codes, p->hidden, w->qkv_scales, p->qkv, qkv_out, p->hidden, VITA_EPI_BIAS, p->qkv_b,
+                              nullptr, p->ln1, p->eps, st);
   if (rc != VITA_OK) return rc;
-  const int H = p->heads, D = p->head_dim;
-  if (p->len > 0) {
-    rc = vita_decode_attn_partial_kv8(p->qkv, (int64_t)hpg * D, D, c->k_codes, c->v_codes, c->code_row_stride, c->code_group_stride,
-                                      c->k_scales, c->v_scales, c->scale_row_stride, c->scale_group_stride, p->len, nullptr,
-                                      p->n_splits, p->kv_groups, qpg, D, p->softmax_scale, p->part_m, p->part_l, p->part_o, st);
-    if (rc != VITA_OK) return rc;
-  }
-  const int nparts = p->len > 0 ? p->n_splits : 0;
-  if (p->msg) {                       // packed (o, m, l) partial, as vita_decode_layer_attn writes it
-    float* msg = (float*)p->msg;
-    return vita_decode_attn_merge(p->part_m, p->part_l, p->part_o, nparts, H, (int64_t)H * D, H, D, msg + (int64_t)H * D,
-                                  msg + (int64_t)H * D + H, msg, nullptr, st);
-  }
-  return vita_decode_attn_merge(p->part_m, p->part_l, p->part_o, nparts, H, (int64_t)H * D, H, D, nullptr, nullptr, nullptr,
-                                p->ctx, st);
+  return decode_layer_attn_tail(p, c, st);
 }
 
 extern "C" int vita_decode_layer_mlp(const vita_decode_layer_params* p, void* stream) {
   if (!decode_layer_args_ok(p) || !p->o_w || !p->ln2 || !p->fc1_w || !p->fc2_w) return VITA_ERR_INVALID_ARG;
   if (p->head_dim != 128 || (p->hidden & 7) || (p->ffn & 7)) return VITA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
-  const int H = p->heads, D = p->head_dim;
-  if (p->gathered) {                  // CP > 1: merge the ranks' partials into the context
-    if (p->n_ranks <= 0) return VITA_ERR_INVALID_ARG;
-    const float* g = (const float*)p->gathered;
-    const int64_t msg_len = (int64_t)H * D + 2 * H;
-    const int rc = vita_decode_attn_merge(g + (int64_t)H * D, g + (int64_t)H * D + H, g, p->n_ranks, msg_len, msg_len, H, D,
-                                          nullptr, nullptr, nullptr, p->ctx, st);
-    if (rc != VITA_OK) return rc;
-  }
-  const int64_t hd = (int64_t)H * D;
+  const int rc = decode_layer_merge_ranks(p, st);
+  if (rc != VITA_OK) return rc;
+  const int64_t hd = (int64_t)p->heads * p->head_dim;
   launch_gemv<VITA_EPI_RESIDUAL, false>(p->ctx, p->o_w, hd, p->h, p->hidden, hd, nullptr, p->h, nullptr, 0.f, st);
   launch_gemv<VITA_EPI_SWIGLU, true>(p->h, p->fc1_w, p->hidden, p->act, p->ffn, p->hidden, nullptr, nullptr, p->ln2, p->eps, st);
   launch_gemv<VITA_EPI_RESIDUAL, false>(p->act, p->fc2_w, p->ffn, p->h, p->hidden, p->ffn, nullptr, p->h, nullptr, 0.f, st);
   return vita_check_launch();
+}
+
+extern "C" int vita_decode_layer_mlp_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, void* stream) {
+  if (!decode_layer_args_ok(p) || !w || !w->o_codes || !w->o_scales || !w->fc1_codes || !w->fc1_scales || !w->fc2_codes ||
+      !w->fc2_scales || !p->ln2)
+    return VITA_ERR_INVALID_ARG;
+  if (p->head_dim != 128 || (p->hidden & 127) || (p->ffn & 127) || w8_misaligned(w->o_codes, w->o_scales) ||
+      w8_misaligned(w->fc1_codes, w->fc1_scales) || w8_misaligned(w->fc2_codes, w->fc2_scales) ||
+      (((uintptr_t)p->h | (uintptr_t)p->ctx | (uintptr_t)p->act | (uintptr_t)p->ln2) & 15))
+    return VITA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = decode_layer_merge_ranks(p, st);
+  if (rc != VITA_OK) return rc;
+  const int64_t hd = (int64_t)p->heads * p->head_dim;
+  rc = vita_gemv_w8(p->ctx, w->o_codes, hd, w->o_scales, p->h, p->hidden, hd, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr, 0.f, st);
+  if (rc != VITA_OK) return rc;
+  rc = vita_gemv_w8(p->h, w->fc1_codes, p->hidden, w->fc1_scales, p->act, p->ffn, p->hidden, VITA_EPI_SWIGLU, nullptr, nullptr,
+                    p->ln2, p->eps, st);
+  if (rc != VITA_OK) return rc;
+  return vita_gemv_w8(p->act, w->fc2_codes, p->ffn, w->fc2_scales, p->h, p->hidden, p->ffn, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr,
+                      0.f, st);
 }

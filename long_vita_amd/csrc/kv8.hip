@@ -8,44 +8,11 @@
 // product, s_v multiplies p in front of P.V; (m, l, O) partials, split geometry and the neutral element are decode.hip's, and
 // vita_decode_attn_merge takes them as they are.
 #include "vita_common.h"
+#include "kv8_rule.h"
 
 #include <math.h>
 
 namespace {
-
-// ---- the rule on 8 bf16 values per lane, NL lanes per head row ------------------------------------------------------------------
-// |x| as integers orders like the floats and puts every NaN above inf: the maximum is exact and carries a NaN through.
-__device__ __forceinline__ unsigned kv8_absmax_bits(const u32x4 a) {
-  unsigned m = 0u;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    m = max(m, a[j] & 0x7fffu);
-    m = max(m, (a[j] >> 16) & 0x7fffu);
-  }
-  return m;
-}
-__device__ __forceinline__ float kv8_scale(unsigned absmax_bits) {
-  const float amax = __uint_as_float(absmax_bits << 16);
-  return amax > 0.f ? amax / 448.0f : 1.0f;
-}
-__device__ __forceinline__ u32x2 kv8_encode8(const u32x4 x, const float s) {
-  u32x2 c;
-#pragma unroll
-  for (int w = 0; w < 2; ++w) {
-    int v = 0;
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(bf16lo_to_f32(x[2 * w]) / s, bf16hi_to_f32(x[2 * w]) / s, v, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(bf16lo_to_f32(x[2 * w + 1]) / s, bf16hi_to_f32(x[2 * w + 1]) / s, v, true);
-    c[w] = (unsigned)v;
-  }
-  return c;
-}
-// 4 codes of one word -> two packed bf16 pairs (exact)
-__device__ __forceinline__ void kv8_decode4(const unsigned w, unsigned& p0, unsigned& p1) {
-  const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);
-  const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, true);
-  p0 = pack_bf16x2(lo[0], lo[1]);
-  p1 = pack_bf16x2(hi[0], hi[1]);
-}
 
 // ---- quantising store: item = (row r, group g, K or V); its 16 lanes hold 8 elements each ------------------------------------------
 // rows outside [row0, row0 + rows) are not touched; a row0 (host or device) that would leave the cache writes nothing.

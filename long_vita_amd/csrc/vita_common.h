@@ -89,6 +89,47 @@ __device__ __forceinline__ float row16_allreduce_sum(float v) {   // row_ror:8,4
   return v;
 }
 
+__device__ __forceinline__ float dot8(const u32x4 a, const u32x4 b) {
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    s += bf16lo_to_f32(a[j]) * bf16lo_to_f32(b[j]) + bf16hi_to_f32(a[j]) * bf16hi_to_f32(b[j]);
+  return s;
+}
+
+// ---- what the single-token GEMVs share (decode.hip: gemv_kernel, gemv_rows_kernel; w8.hip: gemv_w8_kernel) -------------------------
+// One 16-byte vector of the RMS-normalised x: bf16(bf16(x * rstd) * gamma), as vita_rmsnorm_fwd rounds it.
+// The kernels do NOT share the sum of squares behind rstd, on purpose: gemv_kernel adds dot8(x, x) per vector (eight products,
+// then one add into the sum), gemv_rows_kernel adds pair by pair as rmsnorm_fwd_kernel does, which is what makes its normalised row
+// bit-equal to vita_rmsnorm_fwd.  The two orders can round rstd differently; changing either changes output bits.
+// gemv_rstd is gemv_kernel's order for gemv_w8_kernel.  gemv_kernel keeps its own loop: calling this instead made hipcc contract
+// the products of its SWIGLU main loop the other way round, which changes output bits of the bf16 path.
+__device__ __forceinline__ float gemv_rstd(const u32x4* xr, const int nvec, const int lane, const int64_t K, const float eps) {
+  float ss = 0.f;
+  for (int v = lane; v < nvec; v += 64) ss += dot8(xr[v], xr[v]);
+  return rsqrtf(wave_reduce_sum(ss) / (float)K + eps);
+}
+__device__ __forceinline__ u32x4 gemv_norm_x(u32x4 xv, const float rstd, const u32x4 gv) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    xv[j] = pack_bf16x2(bf16_round(bf16lo_to_f32(xv[j]) * rstd) * bf16lo_to_f32(gv[j]),
+                        bf16_round(bf16hi_to_f32(xv[j]) * rstd) * bf16hi_to_f32(gv[j]));
+  return xv;
+}
+// s0 (and s1, SWIGLU's "up" row) = the wave's dot products; bias / residual = the output's element where EPI reads one (GEMV_ELEM)
+#define GEMV_ELEM(E, ptr, i) (EPI == (E) ? bf16_to_f32((ptr)[i]) : 0.f)
+template <int EPI>
+__device__ __forceinline__ bf16_t gemv_epilogue(const float s0, const float s1, const float bias, const float residual) {
+  float o = s0;
+  if (EPI == VITA_EPI_BIAS) o += bias;
+  if (EPI == VITA_EPI_RESIDUAL) o = bf16_round(o) + residual;
+  if (EPI == VITA_EPI_SWIGLU) {                     // same rounding chain as the GEMM epilogue
+    const float g = bf16_round(s0), u = bf16_round(s1);
+    o = bf16_round(g / (1.0f + __expf(-g))) * u;
+  }
+  return f32_to_bf16(o);
+}
+
 // RoPE (non-interleaved halves), bf16 rounding chain of rotary_pos_embedding.py:200-203 — shared by rope.hip and decode.hip
 // rotate one pair of 8-wide vectors (x1 = first half, x2 = second half) with cos/sin vectors.
 // ---- store of one 32 x 32 accumulator block of a "row per lane" epilogue (attention O, dQ, dK, dV) --------------------------------------

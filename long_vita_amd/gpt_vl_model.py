@@ -20,7 +20,7 @@ import torch
 
 from . import context_parallel, ops, parallel_state as mpu, tracing, training_utils
 from .dot_product_attention import DotProductAttention
-from .inference_params import check_kv_cache_dtype
+from .inference_params import check_decode_weight_dtype, check_kv_cache_dtype
 from .language_model_embedding import LanguageModelEmbedding
 from .layers import ColumnParallelLinear
 from .rotary_pos_embedding import RotaryEmbedding
@@ -78,6 +78,11 @@ class GPTVLModel:
         # what a prefill's KV cache holds: "bf16", or "fp8_e4m3" = e4m3 codes + one fp32 scale per (row, kv group), 0.516 of the
         # bytes (CP = 1, TP = 1).  An InferenceParams with a kv_cache_dtype of its own overrides it
         self.kv_cache_dtype = os.environ.get("VITA_KV_CACHE_DTYPE", "bf16")
+        # what the cached token step (CP = 1, TP = 1) reads the four linears of every layer from: "bf16", or "fp8_e4m3" = e4m3 codes +
+        # one fp32 scale per 128 K elements of a weight row, 0.516 of the bytes.  The quantised copies are built at the
+        # first token step and kept in self._w8 next to the bf16 weights, which prefill, extend and the beam step go on reading
+        self._w8 = None
+        self.decode_weight_dtype = os.environ.get("VITA_DECODE_WEIGHT_DTYPE", "bf16")
 
     @property
     def kv_cache_dtype(self) -> str:
@@ -86,6 +91,42 @@ class GPTVLModel:
     @kv_cache_dtype.setter
     def kv_cache_dtype(self, name: str):
         self._kv_cache_dtype = check_kv_cache_dtype(name)
+
+    @property
+    def decode_weight_dtype(self) -> str:
+        return self._decode_weight_dtype
+
+    @decode_weight_dtype.setter
+    def decode_weight_dtype(self, name: str):
+        self._decode_weight_dtype = check_decode_weight_dtype(name)
+        if name == "bf16":
+            self._w8 = None                  # frees the quantised copies
+
+    W8_NAMES = ("qkv_w", "o_w", "fc1_w", "fc2_w")
+
+    def _w8_layers(self, refresh: bool = False):
+        """The quantised copies of every layer's four weights, [{name: (codes, scales)}], or None with the switch at "bf16".  Built
+        on the device when first asked for (the first cached token step); refresh (the start of a request) re-quantises, in place,
+        every copy whose source has another data_ptr() or _version than the one it was made from."""
+        if getattr(self, "_decode_weight_dtype", "bf16") != "fp8_e4m3":
+            return None
+        if mpu.get_context_parallel_world_size() > 1 or mpu.get_tensor_model_parallel_world_size() > 1 or self.force_cp_path:
+            raise NotImplementedError("the FP8 decoder weights are built for CP = 1 and TP = 1")
+        if getattr(self, "_w8", None) is None:
+            self._w8 = [{} for _ in self.p["layers"]]
+            self._w8_src = [{} for _ in self.p["layers"]]
+        elif not refresh:
+            return self._w8
+        for q, src, lp in zip(self._w8, self._w8_src, self.p["layers"]):
+            for name in self.W8_NAMES:
+                w = lp[name]
+                tag = (w.data_ptr(), w._version)
+                if src.get(name) != tag:
+                    have = q.get(name)
+                    reuse = have if have is not None and have[0].shape == w.shape else (None, None)
+                    q[name] = ops.w8_quantize(w, *reuse)
+                    src[name] = tag
+        return self._w8
 
     # ---------------------------------------------------------------------------------------------
     @classmethod
@@ -329,6 +370,8 @@ class GPTVLModel:
         cap = s_local + -(-room // cp) + 1
         dtype = getattr(ip, "kv_cache_dtype", None) or self.kv_cache_dtype
         ip.kv_scale_dict = {}
+        if getattr(self, "_w8", None) is not None:
+            self._w8_layers(refresh=True)    # a request starts: re-quantise the copies whose source weights changed
         if dtype == "fp8_e4m3":
             if cp > 1 or mpu.get_tensor_model_parallel_world_size() > 1 or self.force_cp_path:
                 raise NotImplementedError("the FP8 KV cache is built for CP = 1 and TP = 1")
@@ -382,18 +425,25 @@ class GPTVLModel:
         cp, r = mpu.get_context_parallel_world_size(), mpu.get_context_parallel_rank()
         tp = mpu.get_tensor_model_parallel_world_size()     # TP > 1: cfg / params / cache hold this rank's heads, groups and ffn slice
         ws = self._decode_workspace(token.device)
+        w8 = self._w8_layers()                                  # FP8 weights (CP = 1, TP = 1): ops.gemv_w8 in place of ops.gemv
         h = ops.row_gather(self.p["embed"], token.reshape(1), out=ws["h"], check_bounds=False)   # [1, hidden]
         cos, sin = ops.rope_table(position.reshape(1), self.rotary_pos_emb.inv_freq)
         owner = (ip.decode_steps % cp) == r
         row = ip.local_len
         length = row + (1 if owner else 0)
         for li, lp in enumerate(self.p["layers"]):
+
+            def gemv(x, name, *args, **kw):
+                if w8 is None:
+                    return ops.gemv(x, lp[name], *args, **kw)
+                return ops.gemv_w8(x, *w8[li][name], *args, **kw)
+
             kv = ip.key_value_memory_dict[li + 1]
             sc = ip.kv_scale_dict.get(li + 1)                   # FP8 cache (CP = 1): codes in kv, scales here
             if length > kv.shape[1]:
                 raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
             x = ops.rmsnorm(h, lp["ln1"], c.eps, out=ws["x"])
-            qkv = ops.gemv(x.view(-1), lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"].view(-1))
+            qkv = gemv(x.view(-1), "qkv_w", ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"].view(-1))
             ops.rope_qkv_(ws["qkv"], c.kv_groups, c.qpg, c.head_dim, cos, sin, None, 1)
             m4 = qkv.view(c.kv_groups, c.qpg + 2, c.head_dim)
             if sc is not None:
@@ -421,15 +471,15 @@ class GPTVLModel:
                 gm, gl, go = ops.unpack_partials(ws["gmsg"], c.heads, c.head_dim)
                 ctx = ops.decode_attn_merge(gm, gl, go, True, out=ws["ctx"])
             if tp == 1:
-                ops.gemv(ctx.view(-1), lp["o_w"], ops.EPI_RESIDUAL, residual=h.view(-1), out=h.view(-1))
+                gemv(ctx.view(-1), "o_w", ops.EPI_RESIDUAL, residual=h.view(-1), out=h.view(-1))
             else:   # row-parallel: this rank's heads give a partial sum -> bf16 all-reduce over TP -> residual add (as in prefill)
                 part = ops.gemv(ctx.view(-1), lp["o_w"], ops.EPI_NONE, out=ws["x"].view(-1))
                 dist.all_reduce(part, group=mpu.get_tensor_model_parallel_group())
                 ops.add_(h, part.view(1, -1))
             x = ops.rmsnorm(h, lp["ln2"], c.eps, out=ws["x"])
-            act = ops.gemv(x.view(-1), lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"])
+            act = gemv(x.view(-1), "fc1_w", ops.EPI_SWIGLU, out=ws["act"])
             if tp == 1:
-                ops.gemv(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h.view(-1), out=h.view(-1))
+                gemv(act, "fc2_w", ops.EPI_RESIDUAL, residual=h.view(-1), out=h.view(-1))
             else:
                 part = ops.gemv(act, lp["fc2_w"], ops.EPI_NONE, out=ws["x"].view(-1))
                 dist.all_reduce(part, group=mpu.get_tensor_model_parallel_group())
@@ -490,6 +540,17 @@ class GPTVLModel:
                     extra["kv8"].append(k8)
             st = ip._layer_structs = (structs, extra)
         structs, extra = st
+        w8 = self._w8_layers()
+        if w8 is not None and extra.get("w8_of") is not w8:       # FP8 weights: where the _w8 entries find codes and scales
+            extra["w8"], extra["w8_of"] = [], w8                  # (built again should the copies have been freed and rebuilt)
+            for q in w8:
+                s = _L.W8Layer()
+                for name in self.W8_NAMES:
+                    codes, scales = q[name]
+                    setattr(s, name[:-2] + "_codes", codes.data_ptr())
+                    setattr(s, name[:-2] + "_scales", scales.data_ptr())
+                extra["w8"].append(s)
+        w8 = extra["w8"] if w8 is not None else None
         h = ops.row_gather(self.p["embed"], token.reshape(1), out=ws["h"], check_bounds=False)
         cos, sin = ops.rope_table(position.reshape(1), self.rotary_pos_emb.inv_freq)
         extra["cos"].copy_(cos)
@@ -505,6 +566,11 @@ class GPTVLModel:
         kv8 = extra.get("kv8")
         for li, s in enumerate(structs):
             s.append_row, s.len, s.n_splits = (row if owner else -1), length, n_splits
+            if w8 is not None:
+                _L.check(lib.vita_decode_layer_attn_w8(C.byref(s), C.byref(w8[li]), None if kv8 is None else C.byref(kv8[li]), stream),
+                         "vita_decode_layer_attn_w8")
+                _L.check(lib.vita_decode_layer_mlp_w8(C.byref(s), C.byref(w8[li]), stream), "vita_decode_layer_mlp_w8")
+                continue
             if kv8 is not None:
                 _L.check(lib.vita_decode_layer_attn_kv8(C.byref(s), C.byref(kv8[li]), stream), "vita_decode_layer_attn_kv8")
             else:
@@ -521,7 +587,10 @@ class GPTVLModel:
         launch-bound inner loop of decode) and replayed; token id, position and the cache row count are device
         scalars.  Returns logits [1, vocab] (a static buffer, overwritten by the next step)."""
         g = getattr(ip, "_graph", None)
+        if g is not None and getattr(ip, "_graph_weights", None) is not self._w8_layers():
+            g = None                                            # the switch moved inside a request: capture again
         if g is None:
+            ip._graph_weights = self._w8_layers()               # the copies the capture reads, quantised outside it
             dev = token.device
             st = {"tok": torch.zeros(1, dtype=torch.int64, device=dev),
                   "pos": torch.zeros(1, dtype=torch.int64, device=dev),

@@ -32,7 +32,7 @@ from typing import Optional
 import torch
 
 from . import checkpoint, generation, gpt_vl_model, lib, ops, vision
-from .inference_params import ForwardStep, check_kv_cache_dtype
+from .inference_params import ForwardStep, check_decode_weight_dtype, check_kv_cache_dtype
 
 
 def _get(cfg, name, default=None):
@@ -160,11 +160,25 @@ class LongVITAForCausalLM:
     def kv_cache_dtype(self, name: str):
         self.model.kv_cache_dtype = name
 
+    @property
+    def decode_weight_dtype(self) -> str:
+        """What the cached token step reads the decoder layers' linears from: "bf16" (default) or "fp8_e4m3" (e4m3 codes + a scale per
+        128 K elements of a weight row, kept next to the bf16 weights).  Lives on the model
+        (GPTVLModel.decode_weight_dtype)."""
+        return self.model.decode_weight_dtype
+
+    @decode_weight_dtype.setter
+    def decode_weight_dtype(self, name: str):
+        self.model.decode_weight_dtype = name
+
     # -- construction ---------------------------------------------------------------------------------
     @classmethod
-    def from_state_dict(cls, config, state_dict, device="cuda", generation_config=None, kv_cache_dtype=None):
+    def from_state_dict(cls, config, state_dict, device="cuda", generation_config=None, kv_cache_dtype=None,
+                        decode_weight_dtype=None):
         """state_dict: `LongVITAForCausalLM.state_dict()` names — `model.embed_tokens / layers.N.* / norm`, `lm_head`,
         `model.vision_model.*`, `model.vision_projection.*` (modeling_long_vita.py:67-68)."""
+        check_kv_cache_dtype(kv_cache_dtype, allow_none=True)       # before the weights are read
+        check_decode_weight_dtype(decode_weight_dtype, allow_none=True)
         lib.load(allow_build=False)                      # the HIP path or nothing
         gcfg, vcfg = configs_from_hf(config)
         vis = None
@@ -176,13 +190,16 @@ class LongVITAForCausalLM:
         self = cls(config, model, generation_config)
         if kv_cache_dtype is not None:
             self.kv_cache_dtype = kv_cache_dtype
+        if decode_weight_dtype is not None:
+            self.decode_weight_dtype = decode_weight_dtype
         return self
 
     @classmethod
     def from_pretrained(cls, model_path, *model_args, torch_dtype=None, device_map=None, attn_implementation=None,
-                        trust_remote_code=None, device=None, kv_cache_dtype=None, **kwargs):
+                        trust_remote_code=None, device=None, kv_cache_dtype=None, decode_weight_dtype=None, **kwargs):
         """`AutoModelForCausalLM.from_pretrained(model_path, trust_remote_code=True, device_map=..., torch_dtype=torch.bfloat16,
         attn_implementation="flash_attention_2")` of inference_long_vita.py:811-817: config.json + *.safetensors of a `*_HF` directory."""
+        check_decode_weight_dtype(decode_weight_dtype, allow_none=True)   # before anything is read
         if torch_dtype not in (None, torch.bfloat16, "bfloat16", "auto"):
             raise ValueError("the HIP path computes in bf16 (the reference script passes torch_dtype=torch.bfloat16)")
         config = json.load(open(os.path.join(model_path, "config.json")))
@@ -195,7 +212,7 @@ class LongVITAForCausalLM:
         dev = device or (device_map if isinstance(device_map, (str, torch.device)) and device_map != "auto" else "cuda")
         check_kv_cache_dtype(kv_cache_dtype, allow_none=True)       # before the weights are read
         return cls.from_state_dict(config, checkpoint.load_hf_safetensors(model_path), device=dev, generation_config=gen,
-                                   kv_cache_dtype=kv_cache_dtype)
+                                   kv_cache_dtype=kv_cache_dtype, decode_weight_dtype=decode_weight_dtype)
 
     def eval(self):
         return self

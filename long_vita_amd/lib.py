@@ -148,6 +148,15 @@ class Kv8Cache(C.Structure):
     ]
 
 
+class W8Layer(C.Structure):
+    """Mirror of ``vita_w8_layer`` (include/vita_hip.h)."""
+
+    _fields_ = [
+        ("qkv_codes", C.c_void_p), ("o_codes", C.c_void_p), ("fc1_codes", C.c_void_p), ("fc2_codes", C.c_void_p),
+        ("qkv_scales", C.c_void_p), ("o_scales", C.c_void_p), ("fc1_scales", C.c_void_p), ("fc2_scales", C.c_void_p),
+    ]
+
+
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list EVERY function declared in include/vita_hip.h
@@ -255,6 +264,11 @@ PROTOTYPES = {
     "vita_kv8_store": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _p, _l, _l, _p, _p, _l, _l, _l, _p, _l, _p]),
     "vita_decode_attn_partial_kv8": (_i, [_p, _l, _l, _p, _p, _l, _l, _p, _p, _l, _l, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "vita_decode_layer_attn_kv8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(Kv8Cache), _p]),
+    # FP8 (e4m3) decoder weights for the cached token step
+    "vita_w8_quantize": (_i, [_p, _l, _l, _l, _p, _l, _p, _p]),
+    "vita_gemv_w8": (_i, [_p, _p, _l, _p, _p, _l, _l, _i, _p, _p, _p, _f, _p]),
+    "vita_decode_layer_attn_w8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(W8Layer), C.POINTER(Kv8Cache), _p]),
+    "vita_decode_layer_mlp_w8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(W8Layer), _p]),
 }
 
 _lock = threading.Lock()

@@ -1194,6 +1194,70 @@ def decode_attn_partial_kv8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: tor
 
 
 # ------------------------------------------------------------------------------------------------
+# FP8 (e4m3) decoder weights for the cached token step (include/vita_hip.h: vita_w8_*, vita_gemv_w8)
+# ------------------------------------------------------------------------------------------------
+W8_BLOCK = 128                           # consecutive K elements of a weight row that share a scale
+
+
+def w8_layout(N: int, K: int) -> dict:
+    """Pure layout, no allocation: codes [N, K] e4m3 (1 byte), scales [N, K / 128] fp32, and their bytes next to the bf16 weight's."""
+    if K % W8_BLOCK:
+        raise ValueError(f"w8: K = {K} must be a multiple of {W8_BLOCK}")
+    nbytes = N * K + 4 * N * (K // W8_BLOCK)
+    return {"codes": (N, K), "scales": (N, K // W8_BLOCK), "bytes": nbytes, "bytes_bf16": 2 * N * K, "ratio": nbytes / (2 * N * K)}
+
+
+def _w8_views(codes: torch.Tensor, scales: torch.Tensor, what: str):
+    if codes.dim() != 2 or codes.dtype not in (KV8_DTYPE, torch.uint8) or codes.stride(1) != 1:
+        raise ValueError(f"{what}: codes [N, K] must be {KV8_DTYPE} (or their bytes as uint8) with unit inner stride")
+    rows, K = codes.shape
+    if K % W8_BLOCK:
+        raise RuntimeError(f"{what}: K = {K} must be a multiple of {W8_BLOCK}")
+    if tuple(scales.shape) != (rows, K // W8_BLOCK) or not scales.is_contiguous():
+        raise ValueError(f"{what}: scales must be dense fp32 [N, K / {W8_BLOCK}]")
+    return rows, K
+
+
+def w8_quantize(w: torch.Tensor, codes: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None):
+    """w [N, K] bf16 (unit inner stride) -> (codes [N, K] e4m3, scales [N, K / 128] fp32) by the KV cache's rule on every run of
+    128 consecutive K elements of a row.  codes / scales: destinations to fill (codes may be a padded-row view)."""
+    if w.dim() != 2 or w.stride(1) != 1:
+        raise ValueError("w8_quantize: w [N, K] with unit inner stride")
+    N, K = w.shape
+    lay = w8_layout(N, K)
+    if codes is None:
+        codes = torch.empty(lay["codes"], dtype=KV8_DTYPE, device=w.device)
+    if scales is None:
+        scales = torch.empty(lay["scales"], dtype=torch.float32, device=w.device)
+    if _w8_views(codes, scales, "w8_quantize") != (N, K):
+        raise ValueError("w8_quantize: codes and scales do not match w")
+    _L.check(_L.load().vita_w8_quantize(_dev(w, "w", BF16), w.stride(0), N, K, _dev(codes, "codes"), codes.stride(0),
+                                        _dev(scales, "scales", torch.float32), _stream()), "vita_w8_quantize")
+    return codes, scales
+
+
+def gemv_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+            residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None,
+            eps: float = 0.0) -> torch.Tensor:
+    """gemv over FP8 weights: y[N] = epilogue(dequant(codes, scales)[N, K] . x[K]); SWIGLU: codes of cat[gate, up], N = rows / 2.
+    gamma: x is RMS-normalised first (gamma [K], eps), as the fused layer entries do."""
+    K = x.numel()
+    n_rows, Kc = _w8_views(codes, scales, "gemv_w8")
+    if Kc != K:
+        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, K = {K} expected")
+    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
+    y = torch.empty(N, dtype=BF16, device=x.device) if out is None else out
+    if y.numel() != N or not y.is_contiguous() or not x.is_contiguous():
+        raise ValueError("gemv_w8 needs contiguous x and out of N elements")
+    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
+        raise ValueError("gemv_w8: gamma [K] contiguous")
+    _L.check(_L.load().vita_gemv_w8(_dev(x, "x", BF16), _dev(codes, "codes"), codes.stride(0), _dev(scales, "scales", torch.float32),
+                                    _dev(y, "out", BF16), N, K, epilogue, _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
+                                    _opt(gamma, "gamma", BF16), float(eps), _stream()), "vita_gemv_w8")
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
 # beam search on a shared-prefix KV cache (M/inference/text_generation/generation.py:283-471)
 # ------------------------------------------------------------------------------------------------
 BEAM_MAX = 8
