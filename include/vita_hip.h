@@ -686,6 +686,41 @@ int vita_beam_candidates(const void* logits /* bf16 [rows, ld] */, int64_t ld, i
                          const float* beam_scores /* [rows] */, float temperature, int n_out, int64_t* idx_out /* [n_out] */,
                          float* score_out /* [n_out] */, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched decode: 2 .. 8 requests advance one token each in ONE step, every request on the bf16 cache its own batch-1 prefill
+ * allocated (CP = 1, TP = 1).  Stands behind the loop of generate_tokens_probs_and_return_on_first_stage,
+ * M/inference/text_generation/generation.py:33-280, at batch_size > 1: the weights are streamed once per step for all rows
+ * (vita_gemv_rows_bf16), and these three entries are the per-row part.  The caches are reached through a pointer table in device
+ * memory, kv_ptrs [n_rows][2] of 64-bit addresses (K base, V base of row b's cache [capacity_b][groups][128], bf16); the row and
+ * group strides (elements, multiples of 8) are common to all rows, the capacities caps [n_rows] (int32, device) are not.
+ *
+ * vita_decode_attn_batch_partial: grid (n_splits, groups, n_rows).  Row b's query heads are read in place from row b of the mixed QKV
+ *   buffer (q + b * q_row_stride, head j of kv group g at + g * q_group_stride + j * q_head_stride); it attends to the first
+ *   min(lens[b], caps[b]) rows of its cache (lens int32 [n_rows], device; the host sizes n_splits from the longest row).  A row's
+ *   split geometry follows from its own length: splits_b = min(n_splits, ceil(len_b / 128)) workgroups share its keys, the ones
+ *   behind them write the neutral partial, so row b's partials are those of vita_decode_attn_partial with n_splits = splits_b, bit
+ *   for bit, whatever the other rows hold.  lens[b] <= 0: an idle row — every split writes the neutral partial and neither its cache
+ *   nor its table entry is read.  part_m, part_l [n_rows][n_splits][heads], part_o [n_rows][n_splits][heads][128], fp32.
+ * vita_decode_attn_batch_merge: grid (heads, n_rows): out [n_rows][heads][128] bf16, row b merged from its splits_b parts with the
+ *   arithmetic of vita_decode_attn_merge in the same order; an idle row is all zero.
+ * vita_rope_append_rows: RoPE of the q and k heads of n_rows mixed QKV rows in place (row b at mixed + b * mixed_row_stride, cos / sin
+ *   [n_rows][64] bf16: one position per row), and row b's rotated K and its V stored to row append_rows[b] of its cache (int32
+ *   [n_rows], device); append_rows[b] < 0 or >= caps[b]: rotated, nothing stored.  The arithmetic of vita_rope_qkv_fwd.
+ * Nothing is launched on a refusal: a null pointer, n_rows <= 0, n_splits <= 0, groups <= 0: VITA_ERR_INVALID_ARG; n_rows > 8,
+ * n_splits > 128, head_dim != 128, a qpg outside 1 .. 8, a stride that is not a multiple of 8: VITA_ERR_UNSUPPORTED.
+ * M/inference/text_generation/generation.py:33-280 */
+int vita_decode_attn_batch_partial(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                                   const void* kv_ptrs, int64_t kv_row_stride, int64_t kv_group_stride, const int32_t* lens,
+                                   const int32_t* caps, int n_rows, int n_splits, int groups, int qpg, int head_dim,
+                                   float softmax_scale, void* part_m, void* part_l, void* part_o, void* stream);
+/* M/inference/text_generation/generation.py:33-280 */
+int vita_decode_attn_batch_merge(const void* part_m, const void* part_l, const void* part_o, const int32_t* lens,
+                                 const int32_t* caps, int n_rows, int n_splits, int heads, int head_dim, void* out, void* stream);
+/* M/inference/text_generation/generation.py:33-280 */
+int vita_rope_append_rows(void* mixed, int64_t mixed_row_stride, int n_rows, int groups, int qpg, int head_dim, const void* cos,
+                          const void* sin, const void* kv_ptrs, int64_t kv_row_stride, int64_t kv_group_stride,
+                          const int32_t* append_rows, const int32_t* caps, void* stream);
+
 /* out[n] = bf16(a[n] + b[n]) (n % 8 == 0): the residual add that follows the tensor-parallel all-reduce of a
  * row-parallel linear's output (RowParallelLinear + bias_dropout_add, TP > 1 only; at TP = 1 the add is the GEMM's
  * RESIDUAL epilogue).

@@ -158,14 +158,15 @@ void launch_gemv_rows(const void* x, int64_t ldx, int rows, const void* W, int64
 }
 
 // ---- RoPE of the new token's q and k heads (in place in the mixed qkv row) + append of its K / V to the cache ----
-__global__ __launch_bounds__(256) void rope_append_kernel(bf16_t* __restrict__ mixed, int groups, int qpg, int head_dim,
-                                                          const bf16_t* __restrict__ cos_tab,
-                                                          const bf16_t* __restrict__ sin_tab, bf16_t* __restrict__ kc,
-                                                          bf16_t* __restrict__ vc, int64_t kv_row_stride,
-                                                          int64_t kv_group_stride, int append_row) {
+// The body has one owner: (blk, nblk) are the workgroup's index and count along the row's items, so that the batch-1 kernel and
+// the kernel for several rows (one cache per row) run the same statements.
+__device__ __forceinline__ void rope_append_body(int blk, int nblk, bf16_t* __restrict__ mixed, int groups, int qpg, int head_dim,
+                                                 const bf16_t* __restrict__ cos_tab, const bf16_t* __restrict__ sin_tab,
+                                                 bf16_t* __restrict__ kc, bf16_t* __restrict__ vc, int64_t kv_row_stride,
+                                                 int64_t kv_group_stride, int append_row) {
   const int half = head_dim >> 1, nv = half >> 3, hpg = qpg + 2;
   const int total = groups * hpg * nv;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+  for (int i = blk * blockDim.x + threadIdx.x; i < total; i += nblk * blockDim.x) {
     const int vi = i % nv, h = (i / nv) % hpg, g = i / (nv * hpg);
     bf16_t* p = mixed + ((int64_t)g * hpg + h) * head_dim + vi * 8;
     u32x4 x1 = *reinterpret_cast<const u32x4*>(p);
@@ -185,6 +186,30 @@ __global__ __launch_bounds__(256) void rope_append_kernel(bf16_t* __restrict__ m
   }
 }
 
+__global__ __launch_bounds__(256) void rope_append_kernel(bf16_t* __restrict__ mixed, int groups, int qpg, int head_dim,
+                                                          const bf16_t* __restrict__ cos_tab,
+                                                          const bf16_t* __restrict__ sin_tab, bf16_t* __restrict__ kc,
+                                                          bf16_t* __restrict__ vc, int64_t kv_row_stride,
+                                                          int64_t kv_group_stride, int append_row) {
+  rope_append_body(blockIdx.x, gridDim.x, mixed, groups, qpg, head_dim, cos_tab, sin_tab, kc, vc, kv_row_stride, kv_group_stride,
+                   append_row);
+}
+
+// the same for n_rows mixed rows (grid.y), each with its own cos / sin row and its own cache: kv_ptrs[b] = {K base, V base}, row b's
+// K / V go to cache row append_rows[b]; a row outside [0, caps[b]) is rotated and not stored
+__global__ __launch_bounds__(256) void rope_append_rows_kernel(bf16_t* __restrict__ mixed, int64_t mixed_row_stride, int groups, int qpg,
+                                                               int head_dim, const bf16_t* __restrict__ cos_tab,
+                                                               const bf16_t* __restrict__ sin_tab, bf16_t* const* __restrict__ kv_ptrs,
+                                                               int64_t kv_row_stride, int64_t kv_group_stride,
+                                                               const int* __restrict__ append_rows, const int* __restrict__ caps) {
+  const int b = blockIdx.y;
+  int row = append_rows[b];
+  if (row >= caps[b]) row = -1;
+  rope_append_body(blockIdx.x, gridDim.x, mixed + (int64_t)b * mixed_row_stride, groups, qpg, head_dim,
+                   cos_tab + (int64_t)b * (head_dim >> 1), sin_tab + (int64_t)b * (head_dim >> 1), kv_ptrs[2 * b], kv_ptrs[2 * b + 1],
+                   kv_row_stride, kv_group_stride, row);
+}
+
 // ---- decode attention, stage 1 ---------------------------------------------------------------
 // One workgroup = a contiguous range of cached keys of one kv group; its 4 waves run independently
 // (no barrier, no LDS in the loop) over interleaved 32-key (16 for qpg >= 7) tiles with their own online softmax:
@@ -195,11 +220,13 @@ __global__ __launch_bounds__(256) void rope_append_kernel(bf16_t* __restrict__ m
 //   registers.  The waves' (m, l, O) are merged through LDS once at the end.
 constexpr int kDecKeys = 128;        // key granularity of a split (host side: ops.DECODE_KEYS_PER_TILE)
 
+// The body has one owner: workgroup blk of nsplit (>= 1) over the `len` keys of kv group g of ONE cache, H heads in all; pm / pl / po
+// are that cache's partials.  The batch-1 kernel and the kernel for several rows with a cache each run the same statements.
 template <int QPG>
-__global__ __launch_bounds__(256, 2) void decode_attn_partial_kernel(
-    const bf16_t* __restrict__ q, int64_t q_group_stride, int64_t q_head_stride,
+__device__ __forceinline__ void decode_attn_partial_body(
+    int blk, int nsplit, int g, int H, const bf16_t* __restrict__ q, int64_t q_group_stride, int64_t q_head_stride,
     const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc, int64_t kv_row_stride,
-    int64_t kv_group_stride, int len, const int* __restrict__ len_dev, float scale_log2,
+    int64_t kv_group_stride, int len, float scale_log2,
     float* __restrict__ pm, float* __restrict__ pl, float* __restrict__ po) {
   constexpr int D = 128;
   constexpr int ITS = QPG >= 7 ? 4 : 8;                   // K/V row loads in flight per lane (register budget)
@@ -208,11 +235,8 @@ __global__ __launch_bounds__(256, 2) void decode_attn_partial_kernel(
   __shared__ float wo[4][QPG][D];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int sub = lane & 15, kq = lane >> 4;
-  const int blk = blockIdx.x, g = blockIdx.y;
-  const int H = gridDim.y * QPG;
-  if (len_dev) len = min(len, *len_dev);                  // row count kept on the device (graph replay)
   const int ntiles = (len + kDecKeys - 1) / kDecKeys;
-  const int tiles_per_wg = (ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int tiles_per_wg = (ntiles + nsplit - 1) / nsplit;
   const int key_begin = blk * tiles_per_wg * kDecKeys;
   const int key_end = min(len, key_begin + tiles_per_wg * kDecKeys);
   if (key_begin >= len) {                                 // empty split: neutral element of the merge
@@ -325,21 +349,57 @@ __global__ __launch_bounds__(256, 2) void decode_attn_partial_kernel(
   }
 }
 
+template <int QPG>
+__global__ __launch_bounds__(256, 2) void decode_attn_partial_kernel(
+    const bf16_t* __restrict__ q, int64_t q_group_stride, int64_t q_head_stride,
+    const bf16_t* __restrict__ kc, const bf16_t* __restrict__ vc, int64_t kv_row_stride,
+    int64_t kv_group_stride, int len, const int* __restrict__ len_dev, float scale_log2,
+    float* __restrict__ pm, float* __restrict__ pl, float* __restrict__ po) {
+  if (len_dev) len = min(len, *len_dev);                  // row count kept on the device (graph replay)
+  decode_attn_partial_body<QPG>(blockIdx.x, gridDim.x, blockIdx.y, gridDim.y * QPG, q, q_group_stride, q_head_stride, kc, vc,
+                                kv_row_stride, kv_group_stride, len, scale_log2, pm, pl, po);
+}
+
+// Up to 8 rows with a cache each (the batched decode step, generation.py:33-280): grid (n_splits, groups, n_rows).  Row b's length is
+// min(lens[b], caps[b]); its split geometry follows from that length alone — splits_b = min(gridDim.x, tiles of row b), the
+// workgroups behind them write the neutral partial — so its partials are those of decode_attn_partial_kernel launched with splits_b
+// workgroups, whatever the other rows hold.  A row of length 0 is idle: neutral partials, its table entry is not dereferenced.
+__device__ __forceinline__ int batch_row_len(const int* __restrict__ lens, const int* __restrict__ caps, int b) {
+  return max(0, min(lens[b], caps[b]));
+}
+__device__ __forceinline__ int batch_row_splits(int len, int n_splits) {
+  return min(n_splits, (len + kDecKeys - 1) / kDecKeys);
+}
+
+template <int QPG>
+__global__ __launch_bounds__(256, 2) void decode_attn_batch_partial_kernel(
+    const bf16_t* __restrict__ q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+    const bf16_t* const* __restrict__ kv_ptrs, int64_t kv_row_stride, int64_t kv_group_stride,
+    const int* __restrict__ lens, const int* __restrict__ caps, float scale_log2,
+    float* __restrict__ pm, float* __restrict__ pl, float* __restrict__ po) {
+  const int b = blockIdx.z, H = gridDim.y * QPG;
+  const int len = batch_row_len(lens, caps, b);
+  const int64_t part0 = (int64_t)b * gridDim.x * H;
+  const bf16_t* kc = len > 0 ? kv_ptrs[2 * b] : nullptr;
+  const bf16_t* vc = len > 0 ? kv_ptrs[2 * b + 1] : nullptr;
+  decode_attn_partial_body<QPG>(blockIdx.x, max(1, batch_row_splits(len, (int)gridDim.x)), blockIdx.y, H, q + (int64_t)b * q_row_stride,
+                                q_group_stride, q_head_stride, kc, vc, kv_row_stride, kv_group_stride, len, scale_log2, pm + part0,
+                                pl + part0, po + part0 * 128);
+}
+
 // ---- stage 2: merge nparts partials of one head; final -> bf16 context, else merged partial -----
 // pass 1: threads over parts -> block max M, weights w_p = exp2(m_p - M) in LDS, L = sum l_p w_p;
 // pass 2: thread d accumulates sum_p w_p O_p[d] with independent loads (the serial version was latency-bound).
 constexpr int kMergeMaxParts = 1024;
-__global__ __launch_bounds__(128) void decode_attn_merge_kernel(const float* __restrict__ pm,
-                                                                const float* __restrict__ pl,
-                                                                const float* __restrict__ po, int nparts,
-                                                                int64_t sml, int64_t so,
-                                                                float* __restrict__ om, float* __restrict__ ol,
-                                                                float* __restrict__ oo,
-                                                                bf16_t* __restrict__ out) {
+// The body has one owner (the batch-1 kernel and the kernel for several rows): the workgroup of `head` merges nparts parts.
+__device__ __forceinline__ void decode_attn_merge_body(int head, const float* __restrict__ pm, const float* __restrict__ pl,
+                                                       const float* __restrict__ po, int nparts, int64_t sml, int64_t so,
+                                                       float* __restrict__ om, float* __restrict__ ol, float* __restrict__ oo,
+                                                       bf16_t* __restrict__ out) {
   constexpr int D = 128;
   __shared__ float w[kMergeMaxParts];
   __shared__ float red[4];
-  const int head = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   float m = -INFINITY;
   for (int p = t; p < nparts; p += 128) m = fmaxf(m, pm[p * sml + head]);
 #pragma unroll
@@ -375,6 +435,29 @@ __global__ __launch_bounds__(128) void decode_attn_merge_kernel(const float* __r
     if (t == 0) { om[head] = M; ol[head] = L; }
     oo[head * D + t] = O;
   }
+}
+
+__global__ __launch_bounds__(128) void decode_attn_merge_kernel(const float* __restrict__ pm,
+                                                                const float* __restrict__ pl,
+                                                                const float* __restrict__ po, int nparts,
+                                                                int64_t sml, int64_t so,
+                                                                float* __restrict__ om, float* __restrict__ ol,
+                                                                float* __restrict__ oo,
+                                                                bf16_t* __restrict__ out) {
+  decode_attn_merge_body(blockIdx.x, pm, pl, po, nparts, sml, so, om, ol, oo, out);
+}
+
+// grid (heads, n_rows): row b merges the splits_b parts its own length gave it (the parts behind them are neutral and are not read:
+// the four-way sum of pass 2 then groups the parts exactly as the batch-1 merge over splits_b parts does); an idle row merges no
+// part, which leaves zeros
+__global__ __launch_bounds__(128) void decode_attn_batch_merge_kernel(const float* __restrict__ pm, const float* __restrict__ pl,
+                                                                      const float* __restrict__ po, const int* __restrict__ lens,
+                                                                      const int* __restrict__ caps, int n_splits,
+                                                                      bf16_t* __restrict__ out) {
+  const int b = blockIdx.y, H = gridDim.x;
+  const int64_t part0 = (int64_t)b * n_splits * H;
+  decode_attn_merge_body(blockIdx.x, pm + part0, pl + part0, po + part0 * 128, batch_row_splits(batch_row_len(lens, caps, b), n_splits), H,
+                         (int64_t)H * 128, nullptr, nullptr, nullptr, out + (int64_t)b * H * 128);
 }
 
 }  // namespace
@@ -457,6 +540,63 @@ extern "C" int vita_decode_attn_merge(const void* part_m, const void* part_l, co
                      (const float*)part_m, (const float*)part_l, (const float*)part_o, nparts, part_ml_stride, part_o_stride,
                      (float*)out_m,
                      (float*)out_l, (float*)out_o, (bf16_t*)out_bf16);
+  return vita_check_launch();
+}
+
+// ---- the batched decode step: up to 8 requests, each on the cache its own prefill allocated (generation.py:33-280) ----------
+namespace {
+constexpr int kBatchMaxRows = 8;        // what vita_gemv_rows_bf16 takes (ops.BEAM_MAX)
+constexpr int kBatchMaxSplits = 128;    // ops.DECODE_MAX_SPLITS
+}  // namespace
+
+extern "C" int vita_decode_attn_batch_partial(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                                              const void* kv_ptrs, int64_t kv_row_stride, int64_t kv_group_stride,
+                                              const int32_t* lens, const int32_t* caps, int n_rows, int n_splits, int groups, int qpg,
+                                              int head_dim, float softmax_scale, void* part_m, void* part_l, void* part_o,
+                                              void* stream) {
+  if (!q || !kv_ptrs || !lens || !caps || !part_m || !part_l || !part_o || n_rows <= 0 || n_splits <= 0 || groups <= 0)
+    return VITA_ERR_INVALID_ARG;
+  if (n_rows > kBatchMaxRows || n_splits > kBatchMaxSplits || head_dim != 128 || qpg < 1 || qpg > 8 || (q_row_stride & 7) ||
+      (q_group_stride & 7) || (q_head_stride & 7) || (kv_row_stride & 7) || (kv_group_stride & 7))
+    return VITA_ERR_UNSUPPORTED;
+  dim3 grid((unsigned)n_splits, (unsigned)groups, (unsigned)n_rows), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const float sl2 = softmax_scale * 1.4426950408889634f;
+#define VITA_DEC(Q)                                                                                                            \
+  case Q:                                                                                                                      \
+    hipLaunchKernelGGL(decode_attn_batch_partial_kernel<Q>, grid, block, 0, st, (const bf16_t*)q, q_row_stride, q_group_stride, \
+                       q_head_stride, (const bf16_t* const*)kv_ptrs, kv_row_stride, kv_group_stride, (const int*)lens,         \
+                       (const int*)caps, sl2, (float*)part_m, (float*)part_l, (float*)part_o);                                 \
+    break;
+  switch (qpg) {
+    VITA_DEC(1) VITA_DEC(2) VITA_DEC(3) VITA_DEC(4) VITA_DEC(5) VITA_DEC(6) VITA_DEC(7) VITA_DEC(8)
+  }
+#undef VITA_DEC
+  return vita_check_launch();
+}
+
+extern "C" int vita_decode_attn_batch_merge(const void* part_m, const void* part_l, const void* part_o, const int32_t* lens,
+                                            const int32_t* caps, int n_rows, int n_splits, int heads, int head_dim, void* out,
+                                            void* stream) {
+  if (!part_m || !part_l || !part_o || !lens || !caps || !out || n_rows <= 0 || n_splits <= 0 || heads <= 0)
+    return VITA_ERR_INVALID_ARG;
+  if (n_rows > kBatchMaxRows || n_splits > kBatchMaxSplits || head_dim != 128) return VITA_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(decode_attn_batch_merge_kernel, dim3((unsigned)heads, (unsigned)n_rows), dim3(128), 0, (hipStream_t)stream,
+                     (const float*)part_m, (const float*)part_l, (const float*)part_o, (const int*)lens, (const int*)caps, n_splits,
+                     (bf16_t*)out);
+  return vita_check_launch();
+}
+
+extern "C" int vita_rope_append_rows(void* mixed, int64_t mixed_row_stride, int n_rows, int groups, int qpg, int head_dim,
+                                     const void* cos, const void* sin, const void* kv_ptrs, int64_t kv_row_stride,
+                                     int64_t kv_group_stride, const int32_t* append_rows, const int32_t* caps, void* stream) {
+  if (!mixed || !cos || !sin || !kv_ptrs || !append_rows || !caps || n_rows <= 0 || groups <= 0) return VITA_ERR_INVALID_ARG;
+  if (n_rows > kBatchMaxRows || head_dim != 128 || qpg < 1 || qpg > 8 || (mixed_row_stride & 7) || (kv_row_stride & 7) ||
+      (kv_group_stride & 7))
+    return VITA_ERR_UNSUPPORTED;
+  hipLaunchKernelGGL(rope_append_rows_kernel, dim3(4, (unsigned)n_rows), dim3(256), 0, (hipStream_t)stream, (bf16_t*)mixed,
+                     mixed_row_stride, groups, qpg, head_dim, (const bf16_t*)cos, (const bf16_t*)sin, (bf16_t* const*)kv_ptrs,
+                     kv_row_stride, kv_group_stride, (const int*)append_rows, (const int*)caps);
   return vita_check_launch();
 }
 

@@ -155,9 +155,17 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
     token_selector(last_token_logits [1, V], context_length) -> [1] token ids, when given, replaces _sample_strategy (the device-side
     choice with a repetition penalty, hf_adaptor.py); None: nothing changes.
 
-    kv_cache_dtype: "bf16" or "fp8_e4m3" for this request's cache; None: the model's setting (GPTVLModel.kv_cache_dtype)."""
+    kv_cache_dtype: "bf16" or "fp8_e4m3" for this request's cache; None: the model's setting (GPTVLModel.kv_cache_dtype).
+
+    tokens [b, max_sequence_length] with b = 2 .. 8 and lengths [b] (CP = 1, TP = 1, bf16 cache): _generate_batched below — every
+    row is prefilled alone, then all started rows advance in ONE step of the model per token."""
     from .inference_params import ForwardStep
     batch_size, max_sequence_length = tokens.shape
+    if batch_size > 1:
+        yield from _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample, top_k, top_p, temperature,
+                                     use_eod_token_for_early_termination, external_inputs, use_kv_cache, logit_mask, termination_id,
+                                     reference_compat, token_selector, kv_cache_dtype)
+        return
     if batch_size != 1:
         raise ValueError("the Long-VITA decode loop runs batch 1")
     min_prompt_length = int(lengths.min().item())
@@ -225,6 +233,99 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
         yield tokens[:, : context_length + 1], lengths, output_log_probs
         if (use_eod_token_for_early_termination and termination_id is not None
                 and bool((new_sample == termination_id).all())):
+            break
+
+
+def _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample, top_k, top_p, temperature,
+                      use_eod_token_for_early_termination, external_inputs, use_kv_cache, logit_mask, termination_id,
+                      reference_compat, token_selector, kv_cache_dtype):
+    """The loop of :33-280 for tokens [B, max_sequence_length] and lengths [B], B = 2 .. 8 (CP = 1, TP = 1, bf16 caches).  The
+    generator walks context_length from lengths.min() to max_sequence_length and yields (tokens[:, :context_length + 1], lengths,
+    output_log_probs) as the reference does, and row b is written from position lengths[b] on (started = lengths <= context_length,
+    :217-219); its prompt is never overwritten.
+
+    What differs from the reference.  It prefills min_prompt_length tokens of every row and teacher-forces the rest of the longer
+    prompts one token per step; here every row is prefilled ALONE over its whole prompt — the batch-1 path with its own
+    InferenceParams, logit mask, cache (capacity from max_sequence_length) and external_inputs (None, or a list of B dicts / None)
+    — which is the same causal computation, and the prefill's last-row logits choose the token of step context_length ==
+    lengths[b].  Behind that the rows with lengths[b] < context_length that are not finished are the active rows of ONE batched
+    step of the model (inference_params.DecodeBatch: the weights are streamed once), fed tokens[:, context_length - 1] at position
+    context_length - 1; a row with lengths[b] > context_length is idle.  token_selector gets [B, V] logits and returns [B]; the
+    entries of rows that are not written mean nothing.  Termination is :239-246: done = (new_sample == termination_id) & started,
+    sticky per row, and the loop ends when every row is done.  A finished row goes idle: the reference keeps generating behind
+    the termination token and truncates afterwards, here those positions keep what the buffer held.  output_log_probs[b, p] is
+    filled for p >= lengths[b] - 1 of a live row and is NaN at the other positions from lengths.min() - 1 on (the reference holds
+    the log-probs of teacher-forced prompt positions there; this path does not compute them)."""
+    from .inference_params import BATCH_MAX, DecodeBatch, ForwardStep
+    B, max_sequence_length = tokens.shape
+    if B > BATCH_MAX:
+        raise ValueError(f"the batched decode loop takes at most {BATCH_MAX} rows")
+    if not use_kv_cache:
+        raise ValueError("the batched decode loop runs on KV caches (use_kv_cache=True)")
+    if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1:
+        raise NotImplementedError("the batched decode loop is built for CP = 1 and TP = 1")
+    if (kv_cache_dtype or getattr(model, "kv_cache_dtype", "bf16")) != "bf16":
+        raise NotImplementedError("batched decode on an FP8 KV cache is not built (the batched attention reads bf16 caches)")
+    if external_inputs is not None and (not isinstance(external_inputs, (list, tuple)) or len(external_inputs) != B):
+        raise ValueError(f"external_inputs must be None or a list of {B} dicts / None")
+    lens = [int(v) for v in lengths.reshape(-1).tolist()]
+    if len(lens) != B:
+        raise ValueError(f"lengths must hold {B} entries")
+    if min(lens) >= max_sequence_length or max(lens) > max_sequence_length:
+        raise ValueError("context length + tokens_to_generate too large")                  # :85-86
+    dev = tokens.device
+    position_ids = torch.arange(max_sequence_length, dtype=torch.long, device=dev)[None]
+    rows, prefill_logits = [], []
+    for b in range(B):                                     # every prompt alone, whole, at batch 1
+        forward_step = ForwardStep(model, 1, max_sequence_length, external_inputs=None)
+        ip = forward_step.inference_params
+        ip.kv_cache_dtype = kv_cache_dtype
+        ip.prefill_valid_tokens = lens[b]
+        ip.external_inputs = (external_inputs[b] or None) if external_inputs is not None else None
+        tokens_in = tokens[b: b + 1, : lens[b]]
+        if logit_mask:
+            ip.logit_mask, _ = build_logit_mask(tokens_in, lens[b], reference_compat)
+        logits = forward_step(tokens_in, position_ids[:, : lens[b]], None)
+        ip.logit_mask = None
+        prefill_logits.append(logits[0, -1, :] if logit_mask else logits[0, lens[b] - 1, :])
+        rows.append(ip)
+    batch = DecodeBatch(rows)
+    vocab = prefill_logits[0].shape[-1]
+    output_log_probs = None
+    if return_output_log_probs:
+        output_log_probs = torch.empty((B, max_sequence_length - 1, vocab), dtype=torch.float32, device=dev)
+    idle_logits = torch.zeros(B, vocab, dtype=prefill_logits[0].dtype, device=dev)
+    done = [False] * B
+    for context_length in range(min(lens), max_sequence_length):
+        active = [lens[b] < context_length and not done[b] for b in range(B)]
+        live = [lens[b] <= context_length and not done[b] for b in range(B)]
+        if any(active):
+            batch.step_rows(active)
+            logits = model(tokens[:, context_length - 1: context_length],
+                           position_ids[:, context_length - 1: context_length].expand(B, 1), None, inference_params=batch)
+            last_token_logits = logits[:, -1, :].clone()
+        else:
+            last_token_logits = idle_logits.clone()
+        for b in range(B):
+            if lens[b] == context_length:
+                last_token_logits[b] = prefill_logits[b]
+        live_t = torch.tensor(live, dtype=torch.bool, device=dev)
+        if return_output_log_probs:
+            output_log_probs[:, context_length - 1, :] = float("nan")
+        if any(live):
+            if token_selector is not None:
+                new_sample = token_selector(last_token_logits, context_length).view(-1)
+            else:
+                _, new_sample = _sample_strategy(last_token_logits, do_sample=do_sample, top_k=top_k, top_p=top_p,
+                                                 temperature=temperature)
+            tokens[live_t, context_length] = new_sample[live_t]                             # :217-219, finished rows left alone
+            if return_output_log_probs:
+                output_log_probs[live_t, context_length - 1, :] = torch.log_softmax(last_token_logits[live_t].float(), dim=1)
+            if use_eod_token_for_early_termination and termination_id is not None:        # :239-246
+                for b, hit in enumerate((new_sample == termination_id).tolist()):
+                    done[b] = done[b] or (hit and live[b])
+        yield tokens[:, : context_length + 1], lengths, output_log_probs
+        if all(done):
             break
 
 

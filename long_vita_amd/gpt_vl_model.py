@@ -20,7 +20,7 @@ import torch
 
 from . import context_parallel, ops, parallel_state as mpu, tracing, training_utils
 from .dot_product_attention import DotProductAttention
-from .inference_params import check_decode_weight_dtype, check_kv_cache_dtype
+from .inference_params import DecodeBatch, check_decode_weight_dtype, check_kv_cache_dtype
 from .language_model_embedding import LanguageModelEmbedding
 from .layers import ColumnParallelLinear
 from .rotary_pos_embedding import RotaryEmbedding
@@ -276,6 +276,8 @@ class GPTVLModel:
             raise NotImplementedError("the loss / backward path is long_vita_amd.training.TrainStep")
         assert packed_seq_params is None
         ip = inference_params
+        if isinstance(ip, DecodeBatch):
+            return self._batch_forward(input_ids, position_ids, ip)
         if ip is not None:
             if getattr(ip, "external_inputs", None) is not None and not ip.key_value_memory_dict:   # :261-266
                 external_inputs = ip.external_inputs
@@ -730,3 +732,61 @@ class GPTVLModel:
         logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)   # <= 16 rows: vita_gemm_skinny_bf16
         ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)   # as the token step (no-op at 0 / 0)
         return logits.contiguous()                                                        # [B, 1, vocab]: the rows are the beams
+
+    def _batch_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], batch: DecodeBatch) -> torch.Tensor:
+        """One token for each of B = 2 .. 8 requests in ONE step (the loop of M/inference/text_generation/generation.py:33-280 at
+        batch_size > 1): tokens [B, 1] at positions [B, 1], every request on the cache its own batch-1 prefill allocated
+        (inference_params.DecodeBatch).  The weights are streamed once for all B rows: RMSNorm folded into the multi-row GEMVs, RoPE
+        of the B rows at their own positions with each row's K / V appended to its own cache (ops.rope_append_rows), the split
+        attention of every row over its own length (ops.decode_attn_batch), then the head for B rows.  The rows DecodeBatch.step_rows
+        marked active advance; an idle row's cache is neither written nor read and its logits mean nothing.  Without a prepared
+        step every row is active.  Nothing is read back to the host.  CP = 1 and TP = 1; the bf16 weights are read whatever
+        decode_weight_dtype says (as the beam step does); the fused C layer entries and the captured token step stay batch 1.
+        Returns [B, 1, vocab]; row b's hidden state has the bits of the unfused batch-1 token step on request b."""
+        c = self.cfg
+        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
+            raise NotImplementedError("the batched decode step is built for CP = 1 and TP = 1")
+        B = len(batch)
+        if tuple(input_ids.shape) != (B, 1):
+            raise ValueError(f"the batched decode step takes tokens [{B}, 1]")
+        if position_ids is None:
+            position = torch.tensor([ip.sequence_len_offset for ip in batch.rows], dtype=torch.long, device=input_ids.device)
+        elif tuple(position_ids.shape) != (B, 1):
+            raise ValueError(f"the batched decode step takes positions [{B}, 1]")
+        else:
+            position = position_ids[:, 0].contiguous()
+        if batch.active is None:
+            batch.step_rows([True] * B)                          # raises before any launch when a cache is full
+        batch.consumed_tokens = 1
+        rows = self._batch_token(input_ids[:, 0].contiguous(), position, batch)
+        logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)   # <= 16 rows: vita_gemm_skinny_bf16
+        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)   # as the token step (no-op at 0 / 0)
+        return logits.contiguous()                                                        # [B, 1, vocab]
+
+    def _batch_token(self, tokens: torch.Tensor, position: torch.Tensor, batch: DecodeBatch) -> torch.Tensor:
+        """The prepared step of `batch` through the layers: tokens [B] and positions [B] int64 -> final-normed hidden [B, hidden]
+        (_decode_token for B rows with a cache each)."""
+        c = self.cfg
+        B = len(batch)
+        ws = self._ws.get(("batch", B))
+        if ws is None:
+            e = lambda *shape, dt=torch.bfloat16: torch.empty(*shape, dtype=dt, device=tokens.device)  # noqa: E731
+            n, H, D = ops.DECODE_MAX_SPLITS, c.heads, c.head_dim
+            ws = self._ws[("batch", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn),
+                                           "parts": (e(B, n, H, dt=torch.float32), e(B, n, H, dt=torch.float32),
+                                                     e(B, n, H, D, dt=torch.float32))}
+        h = ops.row_gather(self.p["embed"], tokens, check_bounds=False)                   # [B, hidden]
+        cos, sin = ops.rope_table(position, self.rotary_pos_emb.inv_freq)
+        for li, lp in enumerate(self.p["layers"]):
+            ptrs = batch.kv_ptrs[li]
+            qkv = ops.gemv_rows(h, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], eps=c.eps)
+            ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs, batch.kv_row_stride, batch.kv_group_stride,
+                                 batch.append_rows, batch.caps)
+            m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
+            ctx = ops.decode_attn_batch(m4[:, :, : c.qpg], ptrs, batch.kv_row_stride, batch.kv_group_stride, batch.lens, batch.caps,
+                                        batch.max_len, out=ws["ctx"], parts=ws["parts"])
+            ops.gemv_rows(ctx.view(B, -1), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+            act = ops.gemv_rows(h, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], eps=c.eps)
+            ops.gemv_rows(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+        batch.advance()
+        return ops.rmsnorm(h, self.p["final_ln"], c.eps)

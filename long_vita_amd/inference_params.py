@@ -131,6 +131,98 @@ class InferenceParams:
         self.beams, self.beam_n_gen, self.beam_prefix_len, self.beam_tails, self.beam_ancestry = None, 0, 0, {}, None
 
 
+BATCH_MIN, BATCH_MAX = 2, 8              # rows of one batched decode step (what vita_gemv_rows_bf16 takes: ops.BEAM_MAX)
+
+
+class DecodeBatch:
+    """2 .. 8 prefilled batch-1 requests that advance one token each in ONE step of the model (GPTVLModel._batch_forward; the loop of
+    M/inference/text_generation/generation.py:33-280 at batch_size > 1; CP = 1, TP = 1).  Every request keeps the bf16 cache its own
+    prefill allocated, whatever its capacity: the kernels reach the caches through kv_ptrs [layers, B, 2] (int64 on the device: K
+    base and V base per layer and row, built once) and caps [B]; the row and group strides are common.  No K / V is copied, so a
+    table can be rebuilt when requests join or leave.
+
+    step_rows(active) prepares a step: an active row appends at its current length and attends to length + 1, an inactive one gets
+    append = -1 and len = 0 (its cache is neither written nor read).  lens / append_rows (int32, device) are uploaded from the host
+    mirror; nothing is read back.  advance() — called by the model behind the step's launches — moves the mirror and every active
+    row's local_len / decode_steps / sequence_len_offset, so a row's InferenceParams can go on alone at batch 1.
+    consumed_tokens / sequence_len_offset are what ForwardStep reads and writes."""
+
+    def __init__(self, rows):
+        rows = list(rows)
+        if not BATCH_MIN <= len(rows) <= BATCH_MAX:
+            raise ValueError(f"DecodeBatch takes {BATCH_MIN} .. {BATCH_MAX} prefilled requests, got {len(rows)}")
+        for ip in rows:
+            if not isinstance(ip, InferenceParams):
+                raise ValueError("DecodeBatch: every row is the InferenceParams of a prefilled batch-1 request")
+            if ip.kv_cache_is_fp8:
+                raise NotImplementedError("batched decode on an FP8 KV cache is not built (the batched attention reads bf16 caches)")
+            if not ip.key_value_memory_dict:
+                raise ValueError("DecodeBatch: every row is the InferenceParams of a prefilled batch-1 request")
+            if ip.beams is not None:
+                raise ValueError("DecodeBatch: a row holds beam state")
+        first = rows[0].key_value_memory_dict
+        self.layer_numbers = list(first)
+        kv0 = first[self.layer_numbers[0]]
+        for ip in rows:
+            if list(ip.key_value_memory_dict) != self.layer_numbers:
+                raise ValueError("DecodeBatch: the rows' caches hold different layers")
+            cap = ip.key_value_memory_dict[self.layer_numbers[0]].shape[1]
+            for kv in ip.key_value_memory_dict.values():
+                if kv.dtype != torch.bfloat16:
+                    raise ValueError("DecodeBatch: every cache must be bf16")
+                if kv.device != kv0.device:
+                    raise ValueError("DecodeBatch: every cache must be on the same device")
+                if kv.dim() != 4 or kv.shape[0] != 2 or kv.shape[1] != cap or kv.shape[2:] != kv0.shape[2:] or kv.stride(3) != 1 \
+                        or kv.stride()[1:] != kv0.stride()[1:]:
+                    raise ValueError("DecodeBatch: the caches must share kv groups, head_dim and their row and group strides")
+            if ip.local_len > cap:
+                raise ValueError("DecodeBatch: a row holds more tokens than its cache has rows")
+        self.rows = rows
+        self.device = kv0.device
+        self.kv_row_stride, self.kv_group_stride = kv0.stride(1), kv0.stride(2)
+        self.caps_host = [ip.key_value_memory_dict[self.layer_numbers[0]].shape[1] for ip in rows]
+        self.caps = torch.tensor(self.caps_host, dtype=torch.int32).to(self.device)
+        table = [[[ip.key_value_memory_dict[ln][0].data_ptr(), ip.key_value_memory_dict[ln][1].data_ptr()] for ip in rows]
+                 for ln in self.layer_numbers]
+        self.kv_ptrs = torch.tensor(table, dtype=torch.int64).to(self.device)           # [layers, B, 2]
+        self.host_lens = [int(ip.local_len) for ip in rows]
+        self._step = torch.zeros(2, len(rows), dtype=torch.int32, device=self.device)   # one upload per step: lens, append_rows
+        self.lens, self.append_rows = self._step[0], self._step[1]
+        self.max_len = 0
+        self.active = None                   # the rows of the prepared step; None: no step is prepared
+        self.consumed_tokens = None
+        self.sequence_len_offset = 0
+        self.use_kv_cache = True
+
+    def __len__(self):
+        return len(self.rows)
+
+    def step_rows(self, active):
+        active = [bool(a) for a in active]
+        if len(active) != len(self.rows):
+            raise ValueError(f"step_rows: {len(self.rows)} flags expected")
+        for b, a in enumerate(active):
+            if a and self.host_lens[b] + 1 > self.caps_host[b]:
+                raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
+        lens = [self.host_lens[b] + 1 if a else 0 for b, a in enumerate(active)]
+        rows = [self.host_lens[b] if a else -1 for b, a in enumerate(active)]
+        self._step.copy_(torch.tensor([lens, rows], dtype=torch.int32))                 # host -> device; nothing is read back
+        self.max_len = max(lens)
+        self.active = active
+        return self.max_len
+
+    def advance(self):
+        for b, a in enumerate(self.active or ()):
+            if a:
+                ip = self.rows[b]
+                self.host_lens[b] += 1
+                ip.local_len = self.host_lens[b]
+                ip.decode_steps += 1
+                ip.sequence_len_offset += 1
+                ip._graph = None             # a captured token step holds row counters of its own
+        self.active = None
+
+
 class ForwardStep:
     """M/inference/text_generation/forward_step.py (ForwardStep.__init__ wrapper :27-39 and
     _no_pipelining_forward_step :42-57): owns the InferenceParams, calls the model, advances

@@ -260,6 +260,10 @@ PROTOTYPES = {
     "vita_beam_attn_fwd": (_i, [_p, _l, _l, _l, _p, _p, _l, _l, _l, _p, _p, _l, _p, _i, _i, _i, _i, _i, _f, _p, _p, C.c_size_t, _p]),
     "vita_beam_candidates_workspace_bytes": (_l, [_l, _l]),
     "vita_beam_candidates": (_i, [_p, _l, _l, _l, _p, _f, _i, _p, _p, _p, _l, _p]),
+    # batched decode on per-request caches (generation.py:33-280)
+    "vita_decode_attn_batch_partial": (_i, [_p, _l, _l, _l, _p, _l, _l, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
+    "vita_decode_attn_batch_merge": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "vita_rope_append_rows": (_i, [_p, _l, _i, _i, _i, _i, _p, _p, _p, _l, _l, _p, _p, _p]),
     # FP8 (e4m3) KV cache for the cached decode
     "vita_kv8_store": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _p, _l, _l, _p, _p, _l, _l, _l, _p, _l, _p]),
     "vita_decode_attn_partial_kv8": (_i, [_p, _l, _l, _p, _p, _l, _l, _p, _p, _l, _l, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p]),

@@ -1118,6 +1118,78 @@ def decode_attn_merge(pm: torch.Tensor, pl: torch.Tensor, po: torch.Tensor, fina
 
 
 # ------------------------------------------------------------------------------------------------
+# batched decode on per-request caches (M/inference/text_generation/generation.py:33-280 at batch_size > 1)
+# ------------------------------------------------------------------------------------------------
+def _batch_tables(kv_ptrs: torch.Tensor, caps: torch.Tensor, rows: int, what: str):
+    if kv_ptrs.dtype != torch.int64 or tuple(kv_ptrs.shape) != (rows, 2) or not kv_ptrs.is_contiguous():
+        raise ValueError(f"{what}: kv_ptrs must be contiguous int64 [{rows}, 2] (K base, V base per row)")
+    if caps.dtype != torch.int32 or tuple(caps.shape) != (rows,) or not caps.is_contiguous():
+        raise ValueError(f"{what}: caps must be contiguous int32 [{rows}]")
+
+
+def decode_attn_batch(q: torch.Tensor, kv_ptrs: torch.Tensor, kv_row_stride: int, kv_group_stride: int, lens: torch.Tensor,
+                      caps: torch.Tensor, max_len: int, softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                      parts: Optional[tuple] = None) -> torch.Tensor:
+    """The contexts [B, H, d] of B <= 8 rows, each attending to a cache of its own.  q [B, G, qpg, d] — a view into the mixed QKV
+    rows; kv_ptrs int64 [B, 2] on the device: the addresses of row b's bf16 K and V cache [cap_b, G, d], which share
+    kv_row_stride / kv_group_stride (elements); lens / caps int32 [B] on the device: row b attends to min(lens[b], caps[b]) rows,
+    0 = an idle row (its context is zero, its cache is not read).  max_len (host) is an upper bound of lens and only sizes the
+    grid.  Row b has the bits of decode_attn_partial + decode_attn_merge on its own cache at decode_splits(lens[b]).
+    parts = (pm, pl, po) fp32 [B, n, H], [B, n, H], [B, n, H, d] with n >= decode_splits(max_len): scratch to reuse."""
+    if q.dim() != 4 or q.stride(3) != 1:
+        raise ValueError("decode_attn_batch: q [B, G, qpg, d] with a unit inner stride")
+    B, G, qpg, d = q.shape
+    _batch_tables(kv_ptrs, caps, B, "decode_attn_batch")
+    if lens.dtype != torch.int32 or tuple(lens.shape) != (B,) or not lens.is_contiguous():
+        raise ValueError(f"decode_attn_batch: lens must be contiguous int32 [{B}]")
+    H = G * qpg
+    n = decode_splits(int(max_len))
+    if parts is None:
+        pm = torch.empty(B, n, H, dtype=torch.float32, device=q.device)
+        pl = torch.empty(B, n, H, dtype=torch.float32, device=q.device)
+        po = torch.empty(B, n, H, d, dtype=torch.float32, device=q.device)
+    else:
+        pm, pl, po = parts
+        for t_ in (pm, pl, po):
+            if t_.dtype != torch.float32 or not t_.is_contiguous() or t_.numel() < B * n * H * (d if t_ is po else 1):
+                raise ValueError("decode_attn_batch: parts must be contiguous fp32 scratch of B * n_splits * H (* d) elements")
+    ctx = torch.empty(B, H, d, dtype=BF16, device=q.device) if out is None else out
+    if tuple(ctx.shape) != (B, H, d) or not ctx.is_contiguous():
+        raise ValueError("decode_attn_batch: out must be contiguous [B, H, d]")
+    scale = 1.0 / math.sqrt(d) if softmax_scale is None else softmax_scale
+    L = _L.load()
+    _L.check(L.vita_decode_attn_batch_partial(_dev(q, "q", BF16), q.stride(0), q.stride(1), q.stride(2), _dev(kv_ptrs, "kv_ptrs"),
+                                              int(kv_row_stride), int(kv_group_stride), _dev(lens, "lens"), _dev(caps, "caps"), B, n,
+                                              G, qpg, d, float(scale), _dev(pm, "pm"), _dev(pl, "pl"), _dev(po, "po"), _stream()),
+             "vita_decode_attn_batch_partial")
+    _L.check(L.vita_decode_attn_batch_merge(_dev(pm, "pm"), _dev(pl, "pl"), _dev(po, "po"), _dev(lens, "lens"), _dev(caps, "caps"),
+                                            B, n, H, d, _dev(ctx, "out", BF16), _stream()), "vita_decode_attn_batch_merge")
+    return ctx
+
+
+def rope_append_rows(mixed_qkv: torch.Tensor, groups: int, q_per_group: int, head_dim: int, cos: torch.Tensor, sin: torch.Tensor,
+                     kv_ptrs: torch.Tensor, kv_row_stride: int, kv_group_stride: int, append_rows: torch.Tensor,
+                     caps: torch.Tensor) -> torch.Tensor:
+    """rope_qkv_ on the B <= 8 rows of mixed_qkv [B, groups * (qpg + 2) * d] (cos / sin bf16 [B, d / 2]: a position per row), and row
+    b's rotated K and its V stored to row append_rows[b] (int32 [B], device) of the cache kv_ptrs[b] names; a row that is negative
+    or >= caps[b] is rotated and not stored."""
+    if mixed_qkv.dim() != 2 or mixed_qkv.stride(1) != 1 or mixed_qkv.shape[1] != groups * (q_per_group + 2) * head_dim:
+        raise ValueError("rope_append_rows: mixed_qkv must be [rows, groups * (qpg + 2) * head_dim] with a unit inner stride")
+    B = mixed_qkv.shape[0]
+    _batch_tables(kv_ptrs, caps, B, "rope_append_rows")
+    if append_rows.dtype != torch.int32 or tuple(append_rows.shape) != (B,) or not append_rows.is_contiguous():
+        raise ValueError(f"rope_append_rows: append_rows must be contiguous int32 [{B}]")
+    for t_, name in ((cos, "cos"), (sin, "sin")):
+        if tuple(t_.shape) != (B, head_dim // 2) or not t_.is_contiguous():
+            raise ValueError(f"rope_append_rows: {name} must be contiguous [{B}, {head_dim // 2}]")
+    _L.check(_L.load().vita_rope_append_rows(_dev(mixed_qkv, "mixed_qkv", BF16), mixed_qkv.stride(0), B, groups, q_per_group, head_dim,
+                                             _dev(cos, "cos", BF16), _dev(sin, "sin", BF16), _dev(kv_ptrs, "kv_ptrs"),
+                                             int(kv_row_stride), int(kv_group_stride), _dev(append_rows, "append_rows"),
+                                             _dev(caps, "caps"), _stream()), "vita_rope_append_rows")
+    return mixed_qkv
+
+
+# ------------------------------------------------------------------------------------------------
 # FP8 (e4m3) KV cache for the cached decode (include/vita_hip.h: vita_kv8_*; DESIGN.md 4.5)
 # ------------------------------------------------------------------------------------------------
 KV8_DTYPE = torch.float8_e4m3fn          # OCP e4m3fn, what gfx950 converts natively (not MI300's fnuz)
