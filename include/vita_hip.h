@@ -721,6 +721,36 @@ int vita_rope_append_rows(void* mixed, int64_t mixed_row_stride, int n_rows, int
                           const void* sin, const void* kv_ptrs, int64_t kv_row_stride, int64_t kv_group_stride,
                           const int32_t* append_rows, const int32_t* caps, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Several continuations of ONE prefilled prompt in one step: 1 .. 8 rows whose first prefix_len tokens are the same (questions
+ * about one video), CP = 1, TP = 1.  Stands behind the loop of generate_tokens_probs_and_return_on_first_stage,
+ * M/inference/text_generation/generation.py:33-280, at batch_size > 1, which prefills every row over the whole prompt and keeps a
+ * cache per row: here the common prefix is prefilled and cached once and read once per kv group and step for all rows.
+ *
+ * vita_prefix_batch_attn_fwd: the contexts out [n_rows][n_q_heads][128] (bf16, dense) of the rows' query heads (read in place from
+ *   the mixed QKV rows, addressed as for vita_beam_attn_fwd).  Row b sees the rows [0, prefix_len) of k_cache / v_cache (strides as
+ *   for vita_flash_attn_extend_fwd; never written, rows behind prefix_len never read) and the first
+ *   min(max(tail_lens[b], 0), tail_cap) rows of its own bf16 tail [tail_cap][n_kv_heads][128].  tail_ptrs is [n_rows][2] of 64-bit
+ *   addresses in device memory (K base, V base of row b's tail, 16-byte aligned): the table of vita_decode_attn_batch_partial, so
+ *   one table serves vita_rope_append_rows and this entry; tail_row_stride / tail_group_stride (elements, multiples of 8) are
+ *   common to all rows.  tail_lens is int32 [n_rows] in device memory: the host passes no length and reads nothing back.
+ *   tail_lens[b] <= 0: an idle row — it gets the attention over the prefix alone, and neither its tail nor its table entry is read.
+ *   The prefix pass is vita_beam_attn_fwd's launch, the tail pass runs vita_beam_attn_fwd's tail arithmetic on the row's own keys,
+ *   and the merge is the same: row b has the bits of row b of vita_beam_attn_fwd with n_rows beams, an identity ancestry table,
+ *   n_gen = tail_lens[b] and the same tail data, whatever the other rows' lengths are.  The workspace
+ *   (vita_prefix_batch_attn_workspace_bytes, 16-byte aligned; 0 for a shape the entry refuses) holds the fp32 partials.
+ * Nothing is launched on a refusal: a null pointer, n_rows < 1, prefix_len <= 0, a scale that is not positive and finite,
+ * tail_cap < 0, a workspace that is too short: VITA_ERR_INVALID_ARG; n_rows > 8, n_q_heads / n_kv_heads > 8, head_dim != 128, a
+ * stride that is not a multiple of 8, a base that is not 16-byte aligned: VITA_ERR_UNSUPPORTED.
+ * M/inference/text_generation/generation.py:33-280 */
+size_t vita_prefix_batch_attn_workspace_bytes(int n_rows, int n_q_heads, int64_t prefix_len);
+/* M/inference/text_generation/generation.py:33-280 */
+int vita_prefix_batch_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                               const void* k_cache, const void* v_cache, int64_t kv_row_stride, int64_t kv_group_stride,
+                               int64_t prefix_len, const void* tail_ptrs, int64_t tail_row_stride, int64_t tail_group_stride,
+                               const int32_t* tail_lens, int tail_cap, int n_rows, int n_q_heads, int n_kv_heads, int head_dim,
+                               float softmax_scale, void* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* out[n] = bf16(a[n] + b[n]) (n % 8 == 0): the residual add that follows the tensor-parallel all-reduce of a
  * row-parallel linear's output (RowParallelLinear + bias_dropout_add, TP > 1 only; at TP = 1 the add is the GEMM's
  * RESIDUAL epilogue).

@@ -245,21 +245,25 @@ bool extend_shape_ok(int64_t t, int n_q_heads, int64_t n_keys) { return t > 0 &&
 constexpr int kBeamMax = 8;
 constexpr int kBeamMaxSplits = kMaxSplits - 1;          // extend_merge_kernel: one lane per part, the tail partial is one of them
 
-template <int QPG>
-__global__ __launch_bounds__(256) void beam_tail_kernel(const bf16_t* __restrict__ q, int64_t q_rs, int64_t q_gs, int64_t q_hs,
-                                                        const bf16_t* __restrict__ kt, const bf16_t* __restrict__ vt,
-                                                        const int* __restrict__ anc, int64_t tail_cap, int B, int n_gen,
-                                                        float scale_log2, float* __restrict__ pm, float* __restrict__ pl,
-                                                        float* __restrict__ po, int64_t part_base) {
+// The tail pass of ONE (row, kv group) — the key loop, the softmax step, the cross-wave fold and the partial record — has one owner:
+// beam_tail_kernel and prefix_batch_tail_kernel (grid: row b x kv group g) run these statements and differ only in how a key index
+// becomes an address: make_key_off(b, g, sub) is called once, where the loop's invariants are formed, and returns key_off(key), the
+// element offset of key < n_keys — its 128-wide row of this group, the lane's 8 elements — behind kt / vt.  n_keys <= 0 writes the
+// merge's neutral element and reads neither kt / vt nor anything key_off names.
+template <int QPG, class MakeKeyOff>
+__device__ __forceinline__ void tail_partial_body(const bf16_t* __restrict__ q, int64_t q_rs, int64_t q_gs, int64_t q_hs,
+                                                  const bf16_t* __restrict__ kt, const bf16_t* __restrict__ vt, int n_keys,
+                                                  MakeKeyOff make_key_off, int B, float scale_log2, float* __restrict__ pm,
+                                                  float* __restrict__ pl, float* __restrict__ po, int64_t part_base) {
   constexpr int ITS = 4;                                  // K / V row loads in flight per lane
   constexpr int kWaveKeys = ITS * 4;
   __shared__ float wm[4][QPG], wl[4][QPG];
   __shared__ float wo[4][QPG][D];
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int sub = lane & 15, kq = lane >> 4;
-  const int b = blockIdx.x, g = blockIdx.y, G = gridDim.y;
+  const int b = blockIdx.x, g = blockIdx.y;
   const int64_t rec0 = part_base + (int64_t)g * QPG * B + b;          // record of head h: rec0 + h * B
-  if (n_gen <= 0) {                                       // no generated token yet: the merge's neutral element
+  if (n_keys <= 0) {                                      // no key of its own yet: the merge's neutral element
     if (t < QPG) { pm[rec0 + (int64_t)t * B] = -1.0e30f; pl[rec0 + (int64_t)t * B] = 0.f; }
     if (t < D)
       for (int h = 0; h < QPG; ++h) po[(rec0 + (int64_t)h * B) * D + t] = 0.f;
@@ -280,21 +284,17 @@ __global__ __launch_bounds__(256) void beam_tail_kernel(const bf16_t* __restrict
 #pragma unroll
     for (int i = 0; i < 8; ++i) acc[h][i] = 0.f;
   }
-  const int64_t slot_stride = (int64_t)G * D, step_stride = (int64_t)B * slot_stride;
-  const int* my_anc = anc + (int64_t)b * tail_cap;
-  const int64_t goff = (int64_t)g * D + sub * 8;
+  const auto key_off = make_key_off(b, g, sub);
 
-  for (int key0 = wave * kWaveKeys; key0 < n_gen; key0 += 4 * kWaveKeys) {
+  for (int key0 = wave * kWaveKeys; key0 < n_keys; key0 += 4 * kWaveKeys) {
     u32x4 kr[ITS], vr[ITS];
 #pragma unroll
     for (int it = 0; it < ITS; ++it) {
       const int key = key0 + it * 4 + kq;
       kr[it] = u32x4{0u, 0u, 0u, 0u};
       vr[it] = u32x4{0u, 0u, 0u, 0u};
-      if (key < n_gen) {
-        int slot = my_anc[key];
-        slot = slot < 0 ? 0 : (slot >= B ? B - 1 : slot);            // a corrupt table gives wrong numbers, never a stray address
-        const int64_t off = (int64_t)key * step_stride + (int64_t)slot * slot_stride + goff;
+      if (key < n_keys) {
+        const int64_t off = key_off(key);
         kr[it] = *reinterpret_cast<const u32x4*>(kt + off);
         vr[it] = *reinterpret_cast<const u32x4*>(vt + off);
       }
@@ -309,12 +309,12 @@ __global__ __launch_bounds__(256) void beam_tail_kernel(const bf16_t* __restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) sv = dot2_bf16(qp[h][j], kr[it][j], sv);
         sv = row16_allreduce_sum(sv) * scale_log2;
-        sv = (key0 + it * 4 + kq < n_gen) ? sv : -INFINITY;
+        sv = (key0 + it * 4 + kq < n_keys) ? sv : -INFINITY;
         p[h][it] = sv;
         tm = fmaxf(tm, sv);
       }
       tm = fmaxf(tm, __shfl_xor(tm, 16));
-      tm = fmaxf(tm, __shfl_xor(tm, 32));                  // finite: key0 < n_gen
+      tm = fmaxf(tm, __shfl_xor(tm, 32));                  // finite: key0 < n_keys
       const float mnew = fmaxf(mrun[h], tm);
       const float alpha = __builtin_amdgcn_exp2f(mrun[h] - mnew);        // exp2(-inf) = 0 on the first tile
       mrun[h] = mnew;
@@ -369,6 +369,49 @@ __global__ __launch_bounds__(256) void beam_tail_kernel(const bf16_t* __restrict
       if (t == 0) { pm[rec0 + (int64_t)h * B] = M; pl[rec0 + (int64_t)h * B] = L; }
     }
   }
+}
+
+template <int QPG>
+__global__ __launch_bounds__(256) void beam_tail_kernel(const bf16_t* __restrict__ q, int64_t q_rs, int64_t q_gs, int64_t q_hs,
+                                                        const bf16_t* __restrict__ kt, const bf16_t* __restrict__ vt,
+                                                        const int* __restrict__ anc, int64_t tail_cap, int B, int n_gen,
+                                                        float scale_log2, float* __restrict__ pm, float* __restrict__ pl,
+                                                        float* __restrict__ po, int64_t part_base) {
+  const int G = gridDim.y;
+  auto make_key_off = [=](int b, int g, int sub) __attribute__((always_inline)) {
+    const int64_t slot_stride = (int64_t)G * D, step_stride = (int64_t)B * slot_stride;
+    const int* my_anc = anc + (int64_t)b * tail_cap;
+    const int64_t goff = (int64_t)g * D + sub * 8;
+    return [=](int key) __attribute__((always_inline)) {
+      int slot = my_anc[key];
+      slot = slot < 0 ? 0 : (slot >= B ? B - 1 : slot);              // a corrupt table gives wrong numbers, never a stray address
+      return (int64_t)key * step_stride + (int64_t)slot * slot_stride + goff;
+    };
+  };
+  tail_partial_body<QPG>(q, q_rs, q_gs, q_hs, kt, vt, n_gen, make_key_off, B, scale_log2, pm, pl, po, part_base);
+}
+
+// ---- several continuations of one prefilled prompt (M/inference/text_generation/generation.py:33-280 at batch_size > 1, the rows
+// sharing their first prefix_len tokens).  The prefix pass is the beams': query row b = continuation b.  Row b's own tokens live in a
+// tail of its own, [tail_cap][kv groups][128] behind tail_ptrs[b] = {K base, V base} (the table of decode_attn_batch_partial_kernel),
+// and it holds min(max(tail_lens[b], 0), tail_cap) of them: the length is read on the device, clamped before it bounds an address,
+// and an idle row (length <= 0) reads neither its table entry nor its tail.
+template <int QPG>
+__global__ __launch_bounds__(256) void prefix_batch_tail_kernel(const bf16_t* __restrict__ q, int64_t q_rs, int64_t q_gs, int64_t q_hs,
+                                                                const bf16_t* const* __restrict__ tail_ptrs, int64_t tail_rs,
+                                                                int64_t tail_gs, const int* __restrict__ tail_lens, int tail_cap,
+                                                                int B, float scale_log2, float* __restrict__ pm,
+                                                                float* __restrict__ pl, float* __restrict__ po, int64_t part_base) {
+  const int b = blockIdx.x;
+  int n = tail_lens[b];
+  n = n < 0 ? 0 : (n > tail_cap ? tail_cap : n);
+  const bf16_t* kt = n > 0 ? tail_ptrs[2 * b] : nullptr;
+  const bf16_t* vt = n > 0 ? tail_ptrs[2 * b + 1] : nullptr;
+  auto make_key_off = [=](int, int g, int sub) __attribute__((always_inline)) {
+    const int64_t goff = (int64_t)g * tail_gs + sub * 8;
+    return [=](int key) __attribute__((always_inline)) { return (int64_t)key * tail_rs + goff; };
+  };
+  tail_partial_body<QPG>(q, q_rs, q_gs, q_hs, kt, vt, n, make_key_off, B, scale_log2, pm, pl, po, part_base);
 }
 
 // key splits of the prefix pass: extend_splits' rule for t = B rows (a function of the shapes only), at most kBeamMaxSplits
@@ -459,46 +502,61 @@ extern "C" size_t vita_beam_attn_workspace_bytes(int n_beams, int n_q_heads, int
   return (size_t)(beam_splits(n_beams, n_q_heads, prefix_len) + 1) * (size_t)n_q_heads * (size_t)n_beams * (D + 2) * sizeof(float);
 }
 
-extern "C" int vita_beam_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
-                                  const void* k_cache, const void* v_cache, int64_t kv_row_stride, int64_t kv_group_stride,
-                                  int64_t prefix_len, const void* k_tail, const void* v_tail, int64_t tail_cap,
-                                  const int32_t* ancestry, int n_beams, int n_gen, int n_q_heads, int n_kv_heads, int head_dim,
-                                  float softmax_scale, void* out, void* workspace, size_t workspace_bytes, void* stream) {
-  if (!q || !k_cache || !v_cache || !out || !workspace) return VITA_ERR_INVALID_ARG;
-  if (n_beams < 1 || n_q_heads <= 0 || n_kv_heads <= 0 || n_q_heads % n_kv_heads || prefix_len <= 0) return VITA_ERR_INVALID_ARG;
-  if (n_gen < 0 || tail_cap < 0 || n_gen > tail_cap || (n_gen > 0 && (!k_tail || !v_tail || !ancestry))) return VITA_ERR_INVALID_ARG;
-  if (!(softmax_scale > 0.f) || !(softmax_scale < INFINITY) || kv_row_stride <= 0) return VITA_ERR_INVALID_ARG;
-  const int qpg = n_q_heads / n_kv_heads;
-  if (head_dim != D || qpg > 8 || !beam_shape_ok(n_beams, n_q_heads, prefix_len)) return VITA_ERR_UNSUPPORTED;
-  const int64_t strides[] = {q_row_stride, q_group_stride, q_head_stride, kv_row_stride, kv_group_stride};
+namespace {
+
+// What vita_beam_attn_fwd and vita_prefix_batch_attn_fwd share: B query rows in the mixed QKV buffer, one read-only prefix, a tail
+// partial behind the prefix splits.  The checks of the common arguments (the entry's own stand between the two), the prefix launch
+// and the merge each have one owner.
+struct PrefixArgs {
+  const void* q; int64_t q_rs, q_gs, q_hs;
+  const void *k, *v; int64_t kv_rs, kv_gs, prefix_len;
+  int n_rows, n_q_heads, n_kv_heads, head_dim;
+  float scale;
+  void *out, *ws; size_t ws_bytes;
+};
+
+int prefix_args_invalid(const PrefixArgs& p) {
+  if (!p.q || !p.k || !p.v || !p.out || !p.ws) return VITA_ERR_INVALID_ARG;
+  if (p.n_rows < 1 || p.n_q_heads <= 0 || p.n_kv_heads <= 0 || p.n_q_heads % p.n_kv_heads || p.prefix_len <= 0) return VITA_ERR_INVALID_ARG;
+  // positive and finite, read off the bits: this file is compiled with -fno-honor-nans, which folds a NaN away from float compares
+  unsigned scale_bits;
+  __builtin_memcpy(&scale_bits, &p.scale, sizeof scale_bits);
+  if (scale_bits == 0u || scale_bits >= 0x7f800000u || p.kv_rs <= 0) return VITA_ERR_INVALID_ARG;
+  return VITA_OK;
+}
+
+int prefix_args_unsupported(const PrefixArgs& p) {
+  if (p.head_dim != D || p.n_q_heads / p.n_kv_heads > 8 || !beam_shape_ok(p.n_rows, p.n_q_heads, p.prefix_len)) return VITA_ERR_UNSUPPORTED;
+  const int64_t strides[] = {p.q_rs, p.q_gs, p.q_hs, p.kv_rs, p.kv_gs};
   for (int64_t s : strides)
     if (s & 7) return VITA_ERR_UNSUPPORTED;            // 16-byte vector loads / LDS-DMA pieces
-  if (kv_row_stride * KVT > 0x7fffffffLL) return VITA_ERR_UNSUPPORTED;   // 32-bit lane offsets inside a tile
-  const uintptr_t bases = (uintptr_t)q | (uintptr_t)k_cache | (uintptr_t)v_cache | (uintptr_t)out | (uintptr_t)k_tail |
-                          (uintptr_t)v_tail | (uintptr_t)workspace;
-  if (bases & 15) return VITA_ERR_UNSUPPORTED;
-  if ((uintptr_t)ancestry & 3) return VITA_ERR_UNSUPPORTED;
+  if (p.kv_rs * KVT > 0x7fffffffLL) return VITA_ERR_UNSUPPORTED;   // 32-bit lane offsets inside a tile
+  const uintptr_t bases = (uintptr_t)p.q | (uintptr_t)p.k | (uintptr_t)p.v | (uintptr_t)p.out | (uintptr_t)p.ws;
+  return (bases & 15) ? VITA_ERR_UNSUPPORTED : VITA_OK;
+}
 
-  ExtArgs a;
-  a.q = (const bf16_t*)q; a.q_rs = q_row_stride; a.q_gs = q_group_stride; a.q_hs = q_head_stride;
-  a.k = (const bf16_t*)k_cache; a.v = (const bf16_t*)v_cache; a.kv_rs = kv_row_stride; a.kv_gs = kv_group_stride;
-  a.o = (bf16_t*)out; a.o_rs = (int64_t)n_q_heads * D; a.o_hs = D;
+// flash_extend_kernel<true> over the prefix, every key visible to every row; the partials stay in the workspace, one more part kept
+// free behind the splits for the tail pass
+int prefix_pass(const PrefixArgs& p, ExtArgs& a, hipStream_t st) {
+  a.q = (const bf16_t*)p.q; a.q_rs = p.q_rs; a.q_gs = p.q_gs; a.q_hs = p.q_hs;
+  a.k = (const bf16_t*)p.k; a.v = (const bf16_t*)p.v; a.kv_rs = p.kv_rs; a.kv_gs = p.kv_gs;
+  a.o = (bf16_t*)p.out; a.o_rs = (int64_t)p.n_q_heads * D; a.o_hs = D;
   a.lse = nullptr;
-  a.t = n_beams; a.G = qpg; a.n_kv_heads = n_kv_heads;
+  a.t = p.n_rows; a.G = p.n_q_heads / p.n_kv_heads; a.n_kv_heads = p.n_kv_heads;
   a.n_q_tiles = 1;                                              // B * qpg <= 64 stacked rows: one query tile
-  a.n_keys = (int)prefix_len; a.n_full = (int)prefix_len;       // every prefix key is visible to every beam
+  a.n_keys = (int)p.prefix_len; a.n_full = (int)p.prefix_len;   // every prefix key is visible to every row
   a.q_pos0 = 0; a.key_pos0 = 0; a.key_pos_step = 1;
-  a.n_splits = beam_splits(n_beams, n_q_heads, prefix_len);
-  const int64_t key_tiles = (prefix_len + KVT - 1) / KVT;
+  a.n_splits = beam_splits(p.n_rows, p.n_q_heads, p.prefix_len);
+  const int64_t key_tiles = (p.prefix_len + KVT - 1) / KVT;
   a.tiles_per_split = (int)((key_tiles + a.n_splits - 1) / a.n_splits);
   a.quant_m = 1;                                                // the partials are always merged: see the kernel's main loop
   a.partial_out = 1;
-  a.scale_log2e = softmax_scale * LOG2E;
-  const int64_t n_rec = (int64_t)n_q_heads * n_beams;
+  a.scale_log2e = p.scale * LOG2E;
+  const int64_t n_rec = (int64_t)p.n_q_heads * p.n_rows;
   const int n_parts = a.n_splits + 1;
   const size_t need = (size_t)n_parts * (size_t)n_rec * (D + 2) * sizeof(float);
-  if (workspace_bytes < need) return VITA_ERR_INVALID_ARG;
-  a.po = (float*)workspace;                                     // [parts][heads][B][128], then m and l [parts][heads][B]
+  if (p.ws_bytes < need) return VITA_ERR_INVALID_ARG;
+  a.po = (float*)p.ws;                                          // [parts][heads][B][128], then m and l [parts][heads][B]
   a.pm = a.po + (int64_t)n_parts * n_rec * D;
   a.pl = a.pm + (int64_t)n_parts * n_rec;
 
@@ -507,26 +565,95 @@ extern "C" int vita_beam_attn_fwd(const void* q, int64_t q_row_stride, int64_t q
   vita_device_once(attr_set, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_extend_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   });
+  hipLaunchKernelGGL(flash_extend_kernel<true>, dim3((unsigned)(p.n_kv_heads * a.n_splits)), dim3(512), lds, st, a);
+  return vita_check_launch();
+}
+
+int prefix_merge(const ExtArgs& a, hipStream_t st) {
+  const int64_t n_rec = (int64_t)a.n_kv_heads * a.G * a.t;
+  hipLaunchKernelGGL(extend_merge_kernel, dim3((unsigned)((n_rec + 3) / 4)), dim3(256), 0, st, a.pm, a.pl, a.po, a.n_splits + 1, n_rec,
+                     a.t, a.o, a.o_rs, a.o_hs, (float*)nullptr);
+  return vita_check_launch();
+}
+
+}  // namespace
+
+extern "C" int vita_beam_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                                  const void* k_cache, const void* v_cache, int64_t kv_row_stride, int64_t kv_group_stride,
+                                  int64_t prefix_len, const void* k_tail, const void* v_tail, int64_t tail_cap,
+                                  const int32_t* ancestry, int n_beams, int n_gen, int n_q_heads, int n_kv_heads, int head_dim,
+                                  float softmax_scale, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+  const PrefixArgs p = {q, q_row_stride, q_group_stride, q_head_stride, k_cache, v_cache, kv_row_stride, kv_group_stride, prefix_len,
+                        n_beams, n_q_heads, n_kv_heads, head_dim, softmax_scale, out, workspace, workspace_bytes};
+  int rc = prefix_args_invalid(p);
+  if (rc != VITA_OK) return rc;
+  if (n_gen < 0 || tail_cap < 0 || n_gen > tail_cap || (n_gen > 0 && (!k_tail || !v_tail || !ancestry))) return VITA_ERR_INVALID_ARG;
+  rc = prefix_args_unsupported(p);
+  if (rc != VITA_OK) return rc;
+  if (((uintptr_t)k_tail | (uintptr_t)v_tail) & 15) return VITA_ERR_UNSUPPORTED;
+  if ((uintptr_t)ancestry & 3) return VITA_ERR_UNSUPPORTED;
+
+  ExtArgs a;
   hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(flash_extend_kernel<true>, dim3((unsigned)(n_kv_heads * a.n_splits)), dim3(512), lds, st, a);
-  int rc = vita_check_launch();
+  rc = prefix_pass(p, a, st);
   if (rc != VITA_OK) return rc;
   const dim3 tgrid((unsigned)n_beams, (unsigned)n_kv_heads);
   const float sl2 = softmax_scale * LOG2E;
-  const int64_t part_base = (int64_t)a.n_splits * n_rec;
+  const int64_t part_base = (int64_t)a.n_splits * n_q_heads * n_beams;
 #define VITA_BEAM_TAIL(Q)                                                                                                         \
   case Q:                                                                                                                         \
     hipLaunchKernelGGL(beam_tail_kernel<Q>, tgrid, dim3(256), 0, st, a.q, a.q_rs, a.q_gs, a.q_hs, (const bf16_t*)k_tail,           \
                        (const bf16_t*)v_tail, (const int*)ancestry, tail_cap, n_beams, n_gen, sl2, a.pm, a.pl, a.po, part_base);  \
     break;
-  switch (qpg) {
+  switch (a.G) {
     VITA_BEAM_TAIL(1) VITA_BEAM_TAIL(2) VITA_BEAM_TAIL(3) VITA_BEAM_TAIL(4) VITA_BEAM_TAIL(5) VITA_BEAM_TAIL(6) VITA_BEAM_TAIL(7)
     VITA_BEAM_TAIL(8)
   }
 #undef VITA_BEAM_TAIL
   rc = vita_check_launch();
   if (rc != VITA_OK) return rc;
-  hipLaunchKernelGGL(extend_merge_kernel, dim3((unsigned)((n_rec + 3) / 4)), dim3(256), 0, st, a.pm, a.pl, a.po, n_parts, n_rec,
-                     a.t, a.o, a.o_rs, a.o_hs, (float*)nullptr);
-  return vita_check_launch();
+  return prefix_merge(a, st);
+}
+
+extern "C" size_t vita_prefix_batch_attn_workspace_bytes(int n_rows, int n_q_heads, int64_t prefix_len) {
+  return vita_beam_attn_workspace_bytes(n_rows, n_q_heads, prefix_len);       // the same parts: the prefix splits and one tail partial
+}
+
+extern "C" int vita_prefix_batch_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                                          const void* k_cache, const void* v_cache, int64_t kv_row_stride, int64_t kv_group_stride,
+                                          int64_t prefix_len, const void* tail_ptrs, int64_t tail_row_stride,
+                                          int64_t tail_group_stride, const int32_t* tail_lens, int tail_cap, int n_rows, int n_q_heads,
+                                          int n_kv_heads, int head_dim, float softmax_scale, void* out, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  const PrefixArgs p = {q, q_row_stride, q_group_stride, q_head_stride, k_cache, v_cache, kv_row_stride, kv_group_stride, prefix_len,
+                        n_rows, n_q_heads, n_kv_heads, head_dim, softmax_scale, out, workspace, workspace_bytes};
+  int rc = prefix_args_invalid(p);
+  if (rc != VITA_OK) return rc;
+  if (!tail_ptrs || !tail_lens || tail_cap < 0 || tail_row_stride < 0 || tail_group_stride < 0) return VITA_ERR_INVALID_ARG;
+  rc = prefix_args_unsupported(p);
+  if (rc != VITA_OK) return rc;
+  if ((tail_row_stride | tail_group_stride) & 7) return VITA_ERR_UNSUPPORTED;          // 16-byte vector loads of the tail rows
+  if (((uintptr_t)tail_ptrs & 7) || ((uintptr_t)tail_lens & 3)) return VITA_ERR_UNSUPPORTED;
+
+  ExtArgs a;
+  hipStream_t st = (hipStream_t)stream;
+  rc = prefix_pass(p, a, st);
+  if (rc != VITA_OK) return rc;
+  const dim3 tgrid((unsigned)n_rows, (unsigned)n_kv_heads);
+  const float sl2 = softmax_scale * LOG2E;
+  const int64_t part_base = (int64_t)a.n_splits * n_q_heads * n_rows;
+#define VITA_PREFIX_TAIL(Q)                                                                                                        \
+  case Q:                                                                                                                          \
+    hipLaunchKernelGGL(prefix_batch_tail_kernel<Q>, tgrid, dim3(256), 0, st, a.q, a.q_rs, a.q_gs, a.q_hs,                           \
+                       (const bf16_t* const*)tail_ptrs, tail_row_stride, tail_group_stride, (const int*)tail_lens, tail_cap,       \
+                       n_rows, sl2, a.pm, a.pl, a.po, part_base);                                                                  \
+    break;
+  switch (a.G) {
+    VITA_PREFIX_TAIL(1) VITA_PREFIX_TAIL(2) VITA_PREFIX_TAIL(3) VITA_PREFIX_TAIL(4) VITA_PREFIX_TAIL(5) VITA_PREFIX_TAIL(6)
+    VITA_PREFIX_TAIL(7) VITA_PREFIX_TAIL(8)
+  }
+#undef VITA_PREFIX_TAIL
+  rc = vita_check_launch();
+  if (rc != VITA_OK) return rc;
+  return prefix_merge(a, st);
 }

@@ -141,7 +141,8 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
                                                     do_sample=False, top_k=0, top_p=0.0, temperature=1.0,
                                                     use_eod_token_for_early_termination=True, external_inputs=None,
                                                     *, use_kv_cache=True, logit_mask=True, termination_id=None,
-                                                    reference_compat=False, token_selector=None, kv_cache_dtype=None):
+                                                    reference_compat=False, token_selector=None, kv_cache_dtype=None,
+                                                    shared_prefix_len=None):
     """Generator with the reference's contract (:33-280): `tokens` [1, max_sequence_length] holds the prompt
     (length lengths[0]) followed by padding and is filled in place; yields (tokens[:, :ctx+1], lengths,
     output_log_probs) per generated token.  args.use_kv_cache / args.logit_mask / the tokenizer's eod are keyword
@@ -158,9 +159,18 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
     kv_cache_dtype: "bf16" or "fp8_e4m3" for this request's cache; None: the model's setting (GPTVLModel.kv_cache_dtype).
 
     tokens [b, max_sequence_length] with b = 2 .. 8 and lengths [b] (CP = 1, TP = 1, bf16 cache): _generate_batched below — every
-    row is prefilled alone, then all started rows advance in ONE step of the model per token."""
+    row is prefilled alone, then all started rows advance in ONE step of the model per token.
+
+    shared_prefix_len=P (b = 2 .. 8 rows whose first P tokens are the same — several questions about one video; CP = 1, TP = 1,
+    bf16 cache): _generate_shared_prefix below — tokens[0, :P] is prefilled ONCE and every row reads that cache.  None: nothing
+    changes."""
     from .inference_params import ForwardStep
     batch_size, max_sequence_length = tokens.shape
+    if shared_prefix_len is not None:
+        yield from _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_output_log_probs, do_sample, top_k, top_p,
+                                           temperature, use_eod_token_for_early_termination, external_inputs, use_kv_cache, logit_mask,
+                                           termination_id, reference_compat, token_selector, kv_cache_dtype)
+        return
     if batch_size > 1:
         yield from _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample, top_k, top_p, temperature,
                                      use_eod_token_for_early_termination, external_inputs, use_kv_cache, logit_mask, termination_id,
@@ -309,6 +319,98 @@ def _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample
         for b in range(B):
             if lens[b] == context_length:
                 last_token_logits[b] = prefill_logits[b]
+        live_t = torch.tensor(live, dtype=torch.bool, device=dev)
+        if return_output_log_probs:
+            output_log_probs[:, context_length - 1, :] = float("nan")
+        if any(live):
+            if token_selector is not None:
+                new_sample = token_selector(last_token_logits, context_length).view(-1)
+            else:
+                _, new_sample = _sample_strategy(last_token_logits, do_sample=do_sample, top_k=top_k, top_p=top_p,
+                                                 temperature=temperature)
+            tokens[live_t, context_length] = new_sample[live_t]                             # :217-219, finished rows left alone
+            if return_output_log_probs:
+                output_log_probs[live_t, context_length - 1, :] = torch.log_softmax(last_token_logits[live_t].float(), dim=1)
+            if use_eod_token_for_early_termination and termination_id is not None:        # :239-246
+                for b, hit in enumerate((new_sample == termination_id).tolist()):
+                    done[b] = done[b] or (hit and live[b])
+        yield tokens[:, : context_length + 1], lengths, output_log_probs
+        if all(done):
+            break
+
+
+def _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_output_log_probs, do_sample, top_k, top_p, temperature,
+                            use_eod_token_for_early_termination, external_inputs, use_kv_cache, logit_mask, termination_id,
+                            reference_compat, token_selector, kv_cache_dtype):
+    """The loop of :33-280 for tokens [B, max_sequence_length] and lengths [B], B = 2 .. 8, whose rows share their first P =
+    shared_prefix_len tokens (CP = 1, TP = 1, bf16 cache).  The generator walks context_length from P to max_sequence_length and
+    yields (tokens[:, :context_length + 1], lengths, output_log_probs); row b is written from position lengths[b] on (started =
+    lengths <= context_length, :217-219) and its prompt is never overwritten.
+
+    tokens[0:1, :P] is prefilled ONCE at batch 1 — with its logit mask, and external_inputs in the batch-1 form (one dict or None,
+    feeding that prefill only) — and inference_params.SharedPrefixBatch puts a tail of max_sequence_length - P rows per row behind
+    that cache, which is never written again.  The prefill's last-row logits serve every row at context_length == P.  Behind that
+    every row that is not finished is active in ONE step of the model, fed tokens[:, context_length - 1] at position
+    context_length - 1: a row still inside its own prompt (lengths[b] > context_length) is teacher-forced one token per step, as
+    the reference teacher-forces the longer prompts, and its sampled token is dropped.  token_selector gets [B, V] logits and
+    returns [B]; the entries of rows that are not written mean nothing.  Termination is :239-246, sticky per row as in
+    _generate_batched; a finished row goes idle and the loop ends when every row is done.  output_log_probs[b, p] is filled where
+    row b is live (started and not finished) and is NaN at the other positions from P - 1 on.
+
+    Every refusal is raised before anything is launched: B outside 2 .. 8, P < 1, lengths[b] < P, prefixes that differ (ValueError),
+    use_kv_cache=False (ValueError), CP or TP > 1, an FP8 cache (NotImplementedError)."""
+    from .inference_params import BATCH_MAX, BATCH_MIN, ForwardStep, SharedPrefixBatch
+    if tokens.dim() != 2 or not BATCH_MIN <= tokens.shape[0] <= BATCH_MAX:
+        raise ValueError(f"shared_prefix_len takes tokens [B, S] with B = {BATCH_MIN} .. {BATCH_MAX}")
+    B, max_sequence_length = tokens.shape
+    if isinstance(shared_prefix_len, bool) or not isinstance(shared_prefix_len, int) or shared_prefix_len < 1:
+        raise ValueError("shared_prefix_len must be an integer >= 1")
+    P = shared_prefix_len
+    if not use_kv_cache:
+        raise ValueError("the shared-prefix decode loop runs on a KV cache (use_kv_cache=True)")
+    if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1:
+        raise NotImplementedError("the shared-prefix decode loop is built for CP = 1 and TP = 1")
+    if (kv_cache_dtype or getattr(model, "kv_cache_dtype", "bf16")) != "bf16":
+        raise NotImplementedError("a shared prefix on an FP8 KV cache is not built (the prefix attention reads a bf16 cache)")
+    if external_inputs is not None and not isinstance(external_inputs, dict):
+        raise ValueError("external_inputs must be None or one dict (it feeds the one prefill of the shared prefix)")
+    lens = [int(v) for v in lengths.reshape(-1).tolist()]
+    if len(lens) != B:
+        raise ValueError(f"lengths must hold {B} entries")
+    if min(lens) < P:
+        raise ValueError(f"every row must hold the shared prefix: lengths >= shared_prefix_len = {P}")
+    if min(lens) >= max_sequence_length or max(lens) > max_sequence_length:
+        raise ValueError("context length + tokens_to_generate too large")                  # :85-86
+    if not bool((tokens[:, :P] == tokens[:1, :P]).all()):
+        raise ValueError(f"the rows' first {P} tokens differ: they are not one shared prefix")
+    dev = tokens.device
+    position_ids = torch.arange(max_sequence_length, dtype=torch.long, device=dev)[None]
+    forward_step = ForwardStep(model, 1, max_sequence_length, external_inputs=None)       # the prefix, once, at batch 1
+    ip = forward_step.inference_params
+    ip.kv_cache_dtype = kv_cache_dtype
+    ip.prefill_valid_tokens = P
+    ip.external_inputs = external_inputs or None
+    tokens_in = tokens[:1, :P]
+    if logit_mask:
+        ip.logit_mask, _ = build_logit_mask(tokens_in, P, reference_compat)
+    logits = forward_step(tokens_in, position_ids[:, :P], None)
+    ip.logit_mask = None
+    prefill_logits = logits[0, -1, :] if logit_mask else logits[0, P - 1, :]
+    batch = SharedPrefixBatch(ip, B, max_sequence_length - P)
+    vocab = prefill_logits.shape[-1]
+    output_log_probs = None
+    if return_output_log_probs:
+        output_log_probs = torch.empty((B, max_sequence_length - 1, vocab), dtype=torch.float32, device=dev)
+    done = [False] * B
+    for context_length in range(P, max_sequence_length):
+        live = [lens[b] <= context_length and not done[b] for b in range(B)]
+        if context_length == P:
+            last_token_logits = prefill_logits[None, :].expand(B, vocab).clone()
+        else:
+            batch.step_rows([not d for d in done])
+            logits = model(tokens[:, context_length - 1: context_length],
+                           position_ids[:, context_length - 1: context_length].expand(B, 1), None, inference_params=batch)
+            last_token_logits = logits[:, -1, :].clone()
         live_t = torch.tensor(live, dtype=torch.bool, device=dev)
         if return_output_log_probs:
             output_log_probs[:, context_length - 1, :] = float("nan")

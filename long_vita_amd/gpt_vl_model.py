@@ -20,7 +20,7 @@ import torch
 
 from . import context_parallel, ops, parallel_state as mpu, tracing, training_utils
 from .dot_product_attention import DotProductAttention
-from .inference_params import DecodeBatch, check_decode_weight_dtype, check_kv_cache_dtype
+from .inference_params import DecodeBatch, SharedPrefixBatch, check_decode_weight_dtype, check_kv_cache_dtype
 from .language_model_embedding import LanguageModelEmbedding
 from .layers import ColumnParallelLinear
 from .rotary_pos_embedding import RotaryEmbedding
@@ -278,6 +278,8 @@ class GPTVLModel:
         ip = inference_params
         if isinstance(ip, DecodeBatch):
             return self._batch_forward(input_ids, position_ids, ip)
+        if isinstance(ip, SharedPrefixBatch):
+            return self._prefix_batch_forward(input_ids, position_ids, ip)
         if ip is not None:
             if getattr(ip, "external_inputs", None) is not None and not ip.key_value_memory_dict:   # :261-266
                 external_inputs = ip.external_inputs
@@ -785,6 +787,59 @@ class GPTVLModel:
             m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
             ctx = ops.decode_attn_batch(m4[:, :, : c.qpg], ptrs, batch.kv_row_stride, batch.kv_group_stride, batch.lens, batch.caps,
                                         batch.max_len, out=ws["ctx"], parts=ws["parts"])
+            ops.gemv_rows(ctx.view(B, -1), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+            act = ops.gemv_rows(h, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], eps=c.eps)
+            ops.gemv_rows(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+        batch.advance()
+        return ops.rmsnorm(h, self.p["final_ln"], c.eps)
+
+    def _prefix_batch_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], batch: SharedPrefixBatch) -> torch.Tensor:
+        """One token for each of B = 2 .. 8 continuations of ONE prefilled prompt in ONE step (the loop of
+        M/inference/text_generation/generation.py:33-280 at batch_size > 1, the rows sharing their first tokens): tokens [B, 1] at
+        positions [B, 1] behind the prefix that was prefilled and cached once (inference_params.SharedPrefixBatch).  _batch_forward
+        with the rows' K / V appended to their own tails and ops.prefix_batch_attn over the shared prefix — read once per kv group for
+        all rows — and each row's tail.  The rows SharedPrefixBatch.step_rows marked active advance; an idle row's tail is neither
+        written nor read and its logits mean nothing.  Without a prepared step every row is active.  Nothing is read back to the
+        host.  CP = 1 and TP = 1; the bf16 weights are read whatever decode_weight_dtype says.  Returns [B, 1, vocab]."""
+        c = self.cfg
+        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
+            raise NotImplementedError("the shared-prefix decode step is built for CP = 1 and TP = 1")
+        B = len(batch)
+        if tuple(input_ids.shape) != (B, 1):
+            raise ValueError(f"the shared-prefix decode step takes tokens [{B}, 1]")
+        if position_ids is None:
+            position = torch.tensor(batch.positions(), dtype=torch.long, device=input_ids.device)
+        elif tuple(position_ids.shape) != (B, 1):
+            raise ValueError(f"the shared-prefix decode step takes positions [{B}, 1]")
+        else:
+            position = position_ids[:, 0].contiguous()
+        if batch.active is None:
+            batch.step_rows([True] * B)                          # raises before any launch when a tail is full
+        batch.consumed_tokens = 1
+        rows = self._prefix_batch_token(input_ids[:, 0].contiguous(), position, batch)
+        logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)   # <= 16 rows: vita_gemm_skinny_bf16
+        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)   # as the token step (no-op at 0 / 0)
+        return logits.contiguous()                                                        # [B, 1, vocab]
+
+    def _prefix_batch_token(self, tokens: torch.Tensor, position: torch.Tensor, batch: SharedPrefixBatch) -> torch.Tensor:
+        """The prepared step of `batch` through the layers: tokens [B] and positions [B] int64 -> final-normed hidden [B, hidden]
+        (_batch_token on one shared prefix and a tail per row)."""
+        c = self.cfg
+        B = len(batch)
+        ws = self._ws.get(("prefix_batch", B))
+        if ws is None:
+            e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=tokens.device)  # noqa: E731
+            ws = self._ws[("prefix_batch", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn)}
+        h = ops.row_gather(self.p["embed"], tokens, check_bounds=False)                   # [B, hidden]
+        cos, sin = ops.rope_table(position, self.rotary_pos_emb.inv_freq)
+        for li, lp in enumerate(self.p["layers"]):
+            kv, ptrs = batch.prefix.key_value_memory_dict[li + 1], batch.tail_ptrs[li]
+            qkv = ops.gemv_rows(h, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], eps=c.eps)
+            ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs, batch.tail_row_stride, batch.tail_group_stride,
+                                 batch.append_rows, batch.caps)
+            m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
+            ctx = ops.prefix_batch_attn(m4[:, :, : c.qpg], kv[0], kv[1], batch.prefix_len, ptrs, batch.tail_row_stride,
+                                        batch.tail_group_stride, batch.lens, batch.tail_cap, out=ws["ctx"])
             ops.gemv_rows(ctx.view(B, -1), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
             act = ops.gemv_rows(h, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], eps=c.eps)
             ops.gemv_rows(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)

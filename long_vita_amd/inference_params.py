@@ -223,6 +223,88 @@ class DecodeBatch:
         self.active = None
 
 
+class SharedPrefixBatch:
+    """2 .. 8 continuations of ONE prefilled batch-1 request that advance one token each in ONE step of the model
+    (GPTVLModel._prefix_batch_forward; the loop of M/inference/text_generation/generation.py:33-280 at batch_size > 1 for rows that
+    share their first tokens; CP = 1, TP = 1, bf16 cache).  The prefix is `ip`'s own cache, rows [0, ip.local_len): read by every
+    row, never written, never copied.  Row b's own tokens go to its tail, tails[layer, 0 / 1, b] = [tail_cap, kv_groups, head_dim]
+    (one allocation); the kernels reach the tails through tail_ptrs [layers, n_rows, 2] (int64 on the device: K base and V base,
+    built once) with caps [n_rows] = tail_cap, the table and capacities ops.rope_append_rows takes.
+
+    step_rows(active) / advance() keep DecodeBatch's contract: an active row appends at its tail length and attends to the prefix
+    and tail length + 1 rows, an inactive one gets append = -1 and len = 0 (its tail is neither written nor read).  lens /
+    append_rows (int32, device) are one upload from the host mirror host_lens; nothing is read back.  Row b's next token sits at
+    position prefix_len + host_lens[b]."""
+
+    def __init__(self, ip, n_rows: int, tail_cap: int):
+        if not isinstance(ip, InferenceParams):
+            raise ValueError("SharedPrefixBatch: the prefix is the InferenceParams of a prefilled batch-1 request")
+        if ip.kv_cache_is_fp8:
+            raise NotImplementedError("a shared prefix on an FP8 KV cache is not built (the prefix attention reads a bf16 cache)")
+        if ip.beams is not None:
+            raise ValueError("SharedPrefixBatch: the prefix holds beam state")
+        if not ip.key_value_memory_dict or ip.local_len < 1:
+            raise ValueError("SharedPrefixBatch: the prefix is the InferenceParams of a prefilled batch-1 request (its cache is empty)")
+        n_rows, tail_cap = int(n_rows), int(tail_cap)
+        if not BATCH_MIN <= n_rows <= BATCH_MAX:
+            raise ValueError(f"SharedPrefixBatch takes {BATCH_MIN} .. {BATCH_MAX} rows, got {n_rows}")
+        if tail_cap < 1:
+            raise ValueError("SharedPrefixBatch: tail_cap >= 1")
+        self.layer_numbers = list(ip.key_value_memory_dict)
+        kv0 = ip.key_value_memory_dict[self.layer_numbers[0]]
+        for kv in ip.key_value_memory_dict.values():
+            if kv.dtype != torch.bfloat16:
+                raise ValueError("SharedPrefixBatch: the cache must be bf16")
+            if kv.dim() != 4 or kv.shape[0] != 2 or kv.shape != kv0.shape or kv.stride(3) != 1 or kv.stride() != kv0.stride() \
+                    or kv.device != kv0.device:
+                raise ValueError("SharedPrefixBatch: the layers' caches must be [2, capacity, kv groups, head_dim] with the same strides")
+        if ip.local_len > kv0.shape[1]:
+            raise ValueError("SharedPrefixBatch: the prefix holds more tokens than its cache has rows")
+        self.prefix, self.prefix_len = ip, int(ip.local_len)
+        self.n_rows, self.tail_cap = n_rows, tail_cap
+        self.device = kv0.device
+        groups, head_dim = kv0.shape[2], kv0.shape[3]
+        self.tails = torch.empty(len(self.layer_numbers), 2, n_rows, tail_cap, groups, head_dim, dtype=kv0.dtype, device=self.device)
+        self.tail_row_stride, self.tail_group_stride = groups * head_dim, head_dim
+        table = [[[self.tails[i, 0, b].data_ptr(), self.tails[i, 1, b].data_ptr()] for b in range(n_rows)]
+                 for i in range(len(self.layer_numbers))]
+        self.tail_ptrs = torch.tensor(table, dtype=torch.int64).to(self.device)            # [layers, n_rows, 2]
+        self.caps = torch.full((n_rows,), tail_cap, dtype=torch.int32).to(self.device)
+        self.host_lens = [0] * n_rows                    # tail rows stored per row
+        self._step = torch.zeros(2, n_rows, dtype=torch.int32, device=self.device)      # one upload per step: lens, append_rows
+        self.lens, self.append_rows = self._step[0], self._step[1]
+        self.active = None                   # the rows of the prepared step; None: no step is prepared
+        self.consumed_tokens = None
+        self.sequence_len_offset = ip.sequence_len_offset
+        self.use_kv_cache = True
+
+    def __len__(self):
+        return self.n_rows
+
+    def positions(self):
+        """The position of every row's next token."""
+        return [self.prefix_len + n for n in self.host_lens]
+
+    def step_rows(self, active):
+        active = [bool(a) for a in active]
+        if len(active) != self.n_rows:
+            raise ValueError(f"step_rows: {self.n_rows} flags expected")
+        for b, a in enumerate(active):
+            if a and self.host_lens[b] + 1 > self.tail_cap:
+                raise RuntimeError("the rows' tail cache is full (max_sequence_length reached)")
+        lens = [self.host_lens[b] + 1 if a else 0 for b, a in enumerate(active)]
+        rows = [self.host_lens[b] if a else -1 for b, a in enumerate(active)]
+        self._step.copy_(torch.tensor([lens, rows], dtype=torch.int32))                 # host -> device; nothing is read back
+        self.active = active
+        return max(lens)
+
+    def advance(self):
+        for b, a in enumerate(self.active or ()):
+            if a:
+                self.host_lens[b] += 1
+        self.active = None
+
+
 class ForwardStep:
     """M/inference/text_generation/forward_step.py (ForwardStep.__init__ wrapper :27-39 and
     _no_pipelining_forward_step :42-57): owns the InferenceParams, calls the model, advances

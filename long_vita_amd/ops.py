@@ -1400,6 +1400,48 @@ def beam_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pre
     return o
 
 
+def prefix_batch_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, prefix_len: int, tail_ptrs: torch.Tensor,
+                      tail_row_stride: int, tail_group_stride: int, tail_lens: torch.Tensor, tail_cap: int,
+                      softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The contexts [B, Hq, D] of B <= 8 continuations of one prefilled prompt.  q [B, Hkv, G, D] — a view into the mixed QKV rows;
+    k_cache / v_cache [cap, Hkv, D] views whose rows [0, prefix_len) every row sees (read once for all of them, never written);
+    tail_ptrs int64 [B, 2] on the device: the addresses of row b's own bf16 K and V tail [tail_cap, Hkv, D], which share
+    tail_row_stride / tail_group_stride (elements) — the table rope_append_rows takes; tail_lens int32 [B] on the device: row b
+    sees the first min(max(tail_lens[b], 0), tail_cap) rows of its tail, 0 = an idle row (the prefix alone; its tail is not read).
+    Row b has the bits of row b of beam_attn with B beams, an identity ancestry and n_gen = tail_lens[b] on the same tail data."""
+    if q.dim() != 4 or k_cache.dim() != 3:
+        raise ValueError("prefix_batch_attn: q [B, Hkv, G, D], caches [cap, Hkv, D]")
+    B, Hkv, G, D = q.shape
+    if k_cache.shape[1:] != (Hkv, D) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
+        raise ValueError("prefix_batch_attn: k / v cache views must be [cap, Hkv, D] with the same strides")
+    if q.stride(3) != 1 or k_cache.stride(2) != 1:
+        raise ValueError("head_dim must be contiguous")
+    prefix_len, tail_cap = int(prefix_len), int(tail_cap)
+    if prefix_len > k_cache.shape[0]:
+        raise ValueError("prefix_len exceeds the cache rows")
+    if tail_ptrs.dtype != torch.int64 or tuple(tail_ptrs.shape) != (B, 2) or not tail_ptrs.is_contiguous():
+        raise ValueError(f"prefix_batch_attn: tail_ptrs must be contiguous int64 [{B}, 2] (K base, V base per row)")
+    if tail_lens.dtype != torch.int32 or tuple(tail_lens.shape) != (B,) or not tail_lens.is_contiguous():
+        raise ValueError(f"prefix_batch_attn: tail_lens must be contiguous int32 [{B}]")
+    Hq = Hkv * G
+    o = torch.empty((B, Hq, D), dtype=BF16, device=q.device) if out is None else out
+    if tuple(o.shape) != (B, Hq, D) or not o.is_contiguous():
+        raise ValueError("out must be contiguous [B, Hq, D]")
+    for t_, name in ((q, "q"), (tail_ptrs, "tail_ptrs"), (tail_lens, "tail_lens")):
+        _dev(t_, name)
+    h = _L.load()
+    nbytes = h.vita_prefix_batch_attn_workspace_bytes(B, Hq, prefix_len)
+    ws = _extend_workspace(max(nbytes, 16), q.device)
+    _L.check(h.vita_prefix_batch_attn_fwd(_dev(q, "q", BF16), q.stride(0), q.stride(1), q.stride(2), _dev(k_cache, "k_cache", BF16),
+                                          _dev(v_cache, "v_cache", BF16), k_cache.stride(0), k_cache.stride(1), prefix_len,
+                                          _dev(tail_ptrs, "tail_ptrs"), int(tail_row_stride), int(tail_group_stride),
+                                          _dev(tail_lens, "tail_lens"), tail_cap, B, Hq, Hkv, D,
+                                          float(softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)),
+                                          _dev(o, "out", BF16), _dev(ws, "workspace", torch.float32), nbytes, _stream()),
+             "vita_prefix_batch_attn_fwd")
+    return o
+
+
 def beam_candidates(logits: torch.Tensor, beam_scores: torch.Tensor, n_out: int, temperature: float = 1.0, cols: Optional[int] = None):
     """The n_out best continuations of bf16 logits [rows, ld] (cols valid columns): score = log_softmax(logits / temperature) +
     beam_scores[row] in fp32.  Returns (flat index row * cols + col int64 [n_out], score fp32 [n_out]) on the device, by descending
