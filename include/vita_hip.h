@@ -844,6 +844,12 @@ int vita_decode_layer_attn_kv8(const vita_decode_layer_params* p, const vita_kv8
  *   x is RMS-normalised first (gamma [K], eps) with the arithmetic the fused layer entries use on the bf16 path.  The products are
  *   summed in fp32, a run's scale multiplies a lane's finished partial sum, nothing is rounded to bf16 in front of the epilogue.
  *   Rows behind N and columns behind K are never read.
+ * vita_gemv_rows_w8: vita_gemv_w8 for the rows x[b][K], b < rows <= 8, of the multi-row decode steps (x, y, R through their row
+ *   strides ldx, ldy, ldr in elements, as vita_gemv_rows_bf16): y[b][N] = epilogue(dequant(codes, scales)[N,K] . x[b][K]).  Every code
+ *   row and its scales are read once for all input rows, and row b has the bits of vita_gemv_w8 (gamma = NULL) on row b.  No folded
+ *   RMSNorm: the caller normalises the rows once with vita_rmsnorm_fwd.  RESIDUAL: y may alias R.  rows > 8, K % 128 != 0,
+ *   ldx % 8 != 0, ldx < K, ldy < N, ldc_bytes % 16 != 0 or < K, misaligned x / codes / scales: VITA_ERR_UNSUPPORTED.  Nothing behind
+ *   code row N (2 N for SWIGLU), column K or input row rows - 1 is read.
  * vita_decode_layer_attn_w8 / vita_decode_layer_mlp_w8: vita_decode_layer_attn / _mlp with the four GEMVs of the layer reading
  *   the codes and scales of `w` (dense: row stride K); qkv_w, o_w, fc1_w and fc2_w of the parameter struct are not read.
  *   kv8 != NULL: the cache is the FP8 cache it describes, as for vita_decode_layer_attn_kv8; NULL: the bf16 cache of the
@@ -860,6 +866,10 @@ int vita_w8_quantize(const void* W, int64_t ldw, int64_t N, int64_t K, void* cod
 /* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
 int vita_gemv_w8(const void* x, const void* codes, int64_t ldc_bytes, const void* scales, void* y, int64_t N, int64_t K,
                  int epilogue, const void* bias, const void* R, const void* gamma, float eps, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 for up to 8 rows (beam search M/inference/text_generation/generation.py:283-471,
+ * the batch_size > 1 decode loop :33-280) */
+int vita_gemv_rows_w8(const void* x, int64_t ldx, int rows, const void* codes, int64_t ldc_bytes, const void* scales, void* y,
+                      int64_t ldy, int64_t N, int64_t K, int epilogue, const void* bias, const void* R, int64_t ldr, void* stream);
 /* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
 int vita_decode_layer_attn_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, const vita_kv8_cache* kv8, void* stream);
 /* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */

@@ -259,7 +259,8 @@ def _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample
     InferenceParams, logit mask, cache (capacity from max_sequence_length) and external_inputs (None, or a list of B dicts / None)
     — which is the same causal computation, and the prefill's last-row logits choose the token of step context_length ==
     lengths[b].  Behind that the rows with lengths[b] < context_length that are not finished are the active rows of ONE batched
-    step of the model (inference_params.DecodeBatch: the weights are streamed once), fed tokens[:, context_length - 1] at position
+    step of the model (inference_params.DecodeBatch: the weights are streamed once — the FP8 copies with the model's
+    decode_weight_dtype = "fp8_e4m3", as in the shared-prefix and beam steps), fed tokens[:, context_length - 1] at position
     context_length - 1; a row with lengths[b] > context_length is idle.  token_selector gets [B, V] logits and returns [B]; the
     entries of rows that are not written mean nothing.  Termination is :239-246: done = (new_sample == termination_id) & started,
     sticky per row, and the loop ends when every row is done.  A finished row goes idle: the reference keeps generating behind

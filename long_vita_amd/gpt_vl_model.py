@@ -78,9 +78,10 @@ class GPTVLModel:
         # what a prefill's KV cache holds: "bf16", or "fp8_e4m3" = e4m3 codes + one fp32 scale per (row, kv group), 0.516 of the
         # bytes (CP = 1, TP = 1).  An InferenceParams with a kv_cache_dtype of its own overrides it
         self.kv_cache_dtype = os.environ.get("VITA_KV_CACHE_DTYPE", "bf16")
-        # what the cached token step (CP = 1, TP = 1) reads the four linears of every layer from: "bf16", or "fp8_e4m3" = e4m3 codes +
-        # one fp32 scale per 128 K elements of a weight row, 0.516 of the bytes.  The quantised copies are built at the
-        # first token step and kept in self._w8 next to the bf16 weights, which prefill, extend and the beam step go on reading
+        # what the cached token step and the multi-row steps (beam, batched, shared-prefix; CP = 1, TP = 1) read the four linears of
+        # every layer from: "bf16", or "fp8_e4m3" = e4m3 codes + one fp32 scale per 128 K elements of a weight row, 0.516 of the bytes
+        # (DESIGN.md 4.5).  The quantised copies are built at the first such step and kept in self._w8 next to the bf16 weights, which
+        # prefill, extend and the head go on reading
         self._w8 = None
         self.decode_weight_dtype = os.environ.get("VITA_DECODE_WEIGHT_DTYPE", "bf16")
 
@@ -106,8 +107,8 @@ class GPTVLModel:
 
     def _w8_layers(self, refresh: bool = False):
         """The quantised copies of every layer's four weights, [{name: (codes, scales)}], or None with the switch at "bf16".  Built
-        on the device when first asked for (the first cached token step); refresh (the start of a request) re-quantises, in place,
-        every copy whose source has another data_ptr() or _version than the one it was made from."""
+        on the device when first asked for (the first cached token or multi-row step); refresh (the start of a request) re-quantises,
+        in place, every copy whose source has another data_ptr() or _version than the one it was made from."""
         if getattr(self, "_decode_weight_dtype", "bf16") != "fp8_e4m3":
             return None
         if mpu.get_context_parallel_world_size() > 1 or mpu.get_tensor_model_parallel_world_size() > 1 or self.force_cp_path:
@@ -127,6 +128,19 @@ class GPTVLModel:
                     q[name] = ops.w8_quantize(w, *reuse)
                     src[name] = tag
         return self._w8
+
+    def _rows_gemv(self, w8, li: int, x: torch.Tensor, name: str, epilogue: int, bias=None, gamma=None, xn=None, **kw):
+        """Linear `name` of layer li on the rows x [B <= 8, K] of a multi-row step (_beam_forward, _batch_token, _prefix_batch_token):
+        the one owner of their FP8 / bf16 choice.  w8 = self._w8_layers(), taken once per step.  None: ops.gemv_rows on the bf16
+        weight, the RMSNorm (gamma) folded into the kernel.  Else ops.rmsnorm into the workspace rows xn, then ops.gemv_rows_w8 on
+        the codes and scales the batch-1 step reads: the arithmetic of the unfused batch-1 FP8 step (_decode_token), bit for bit."""
+        if w8 is None:
+            if gamma is not None:
+                kw.update(gamma=gamma, eps=self.cfg.eps)
+            return ops.gemv_rows(x, self.p["layers"][li][name], epilogue, bias, **kw)
+        if gamma is not None:
+            x = ops.rmsnorm(x, gamma, self.cfg.eps, out=xn)
+        return ops.gemv_rows_w8(x, *w8[li][name], epilogue, bias, **kw)
 
     # ---------------------------------------------------------------------------------------------
     @classmethod
@@ -692,7 +706,9 @@ class GPTVLModel:
         at the same position, behind the prompt that was prefilled and cached ONCE (ip.begin_beams).  The weights and the prompt's
         K / V are streamed once for all B rows: RMSNorm folded into the multi-row GEMVs, RoPE of the B rows, their K / V stored as
         one contiguous block at tail step n_gen, ops.beam_attn over the shared prefix and each beam's own steps, then the head for
-        B rows.  CP = 1 and TP = 1; the fused C layer entries and the captured token step stay batch 1.  Returns [B, 1, vocab]."""
+        B rows.  decode_weight_dtype = "fp8_e4m3": the four linears read the FP8 copies (_rows_gemv: ops.rmsnorm once per norm, then
+        ops.gemv_rows_w8); the head stays bf16.  CP = 1 and TP = 1; the fused C layer entries and the captured token step stay
+        batch 1.  Returns [B, 1, vocab]."""
         c = self.cfg
         if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1:
             raise NotImplementedError("the beam step is built for CP = 1 and TP = 1")
@@ -713,21 +729,23 @@ class GPTVLModel:
         ws = self._ws.get(("beam", B))
         if ws is None:
             e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=input_ids.device)  # noqa: E731
-            ws = self._ws[("beam", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn)}
+            ws = self._ws[("beam", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn),
+                                          "x": e(B, c.hidden)}
+        w8 = self._w8_layers()                                  # FP8 weights: ops.gemv_rows_w8 in place of ops.gemv_rows (_rows_gemv)
         h = ops.row_gather(self.p["embed"], input_ids[:, 0].contiguous())                 # [B, hidden]
         cos, sin = ops.rope_table(position.expand(B).contiguous(), self.rotary_pos_emb.inv_freq)
         L = ip.beam_prefix_len
         for li, lp in enumerate(self.p["layers"]):
             kv, tail = ip.key_value_memory_dict[li + 1], ip.beam_tails[li + 1]
-            qkv = ops.gemv_rows(h, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], eps=c.eps)
+            qkv = self._rows_gemv(w8, li, h, "qkv_w", ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], xn=ws["x"])
             ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, None, 1)
             m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
             tail[0, step].copy_(m4[:, :, c.qpg])
             tail[1, step].copy_(m4[:, :, c.qpg + 1])
             ctx = ops.beam_attn(m4[:, :, : c.qpg], kv[0], kv[1], L, tail[0], tail[1], ip.beam_ancestry, step + 1, out=ws["ctx"])
-            ops.gemv_rows(ctx.view(B, -1), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
-            act = ops.gemv_rows(h, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], eps=c.eps)
-            ops.gemv_rows(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+            self._rows_gemv(w8, li, ctx.view(B, -1), "o_w", ops.EPI_RESIDUAL, residual=h, out=h)
+            act = self._rows_gemv(w8, li, h, "fc1_w", ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], xn=ws["x"])
+            self._rows_gemv(w8, li, act, "fc2_w", ops.EPI_RESIDUAL, residual=h, out=h)
         ip.beam_n_gen = step + 1
         ip.decode_steps += 1
         rows = ops.rmsnorm(h, self.p["final_ln"], c.eps)
@@ -742,9 +760,10 @@ class GPTVLModel:
         of the B rows at their own positions with each row's K / V appended to its own cache (ops.rope_append_rows), the split
         attention of every row over its own length (ops.decode_attn_batch), then the head for B rows.  The rows DecodeBatch.step_rows
         marked active advance; an idle row's cache is neither written nor read and its logits mean nothing.  Without a prepared
-        step every row is active.  Nothing is read back to the host.  CP = 1 and TP = 1; the bf16 weights are read whatever
-        decode_weight_dtype says (as the beam step does); the fused C layer entries and the captured token step stay batch 1.
-        Returns [B, 1, vocab]; row b's hidden state has the bits of the unfused batch-1 token step on request b."""
+        step every row is active.  Nothing is read back to the host.  CP = 1 and TP = 1; with decode_weight_dtype = "fp8_e4m3" the
+        four linears read the FP8 copies the batch-1 step reads (_rows_gemv), the head stays bf16; the fused C layer entries and the
+        captured token step stay batch 1.  Returns [B, 1, vocab]; row b's hidden state has the bits of the unfused batch-1 token
+        step on request b, under either weight format."""
         c = self.cfg
         if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
             raise NotImplementedError("the batched decode step is built for CP = 1 and TP = 1")
@@ -775,21 +794,23 @@ class GPTVLModel:
             e = lambda *shape, dt=torch.bfloat16: torch.empty(*shape, dtype=dt, device=tokens.device)  # noqa: E731
             n, H, D = ops.DECODE_MAX_SPLITS, c.heads, c.head_dim
             ws = self._ws[("batch", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn),
+                                           "x": e(B, c.hidden),
                                            "parts": (e(B, n, H, dt=torch.float32), e(B, n, H, dt=torch.float32),
                                                      e(B, n, H, D, dt=torch.float32))}
+        w8 = self._w8_layers()                                  # FP8 weights: ops.gemv_rows_w8 in place of ops.gemv_rows (_rows_gemv)
         h = ops.row_gather(self.p["embed"], tokens, check_bounds=False)                   # [B, hidden]
         cos, sin = ops.rope_table(position, self.rotary_pos_emb.inv_freq)
         for li, lp in enumerate(self.p["layers"]):
             ptrs = batch.kv_ptrs[li]
-            qkv = ops.gemv_rows(h, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], eps=c.eps)
+            qkv = self._rows_gemv(w8, li, h, "qkv_w", ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], xn=ws["x"])
             ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs, batch.kv_row_stride, batch.kv_group_stride,
                                  batch.append_rows, batch.caps)
             m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
             ctx = ops.decode_attn_batch(m4[:, :, : c.qpg], ptrs, batch.kv_row_stride, batch.kv_group_stride, batch.lens, batch.caps,
                                         batch.max_len, out=ws["ctx"], parts=ws["parts"])
-            ops.gemv_rows(ctx.view(B, -1), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
-            act = ops.gemv_rows(h, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], eps=c.eps)
-            ops.gemv_rows(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+            self._rows_gemv(w8, li, ctx.view(B, -1), "o_w", ops.EPI_RESIDUAL, residual=h, out=h)
+            act = self._rows_gemv(w8, li, h, "fc1_w", ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], xn=ws["x"])
+            self._rows_gemv(w8, li, act, "fc2_w", ops.EPI_RESIDUAL, residual=h, out=h)
         batch.advance()
         return ops.rmsnorm(h, self.p["final_ln"], c.eps)
 
@@ -800,7 +821,8 @@ class GPTVLModel:
         with the rows' K / V appended to their own tails and ops.prefix_batch_attn over the shared prefix — read once per kv group for
         all rows — and each row's tail.  The rows SharedPrefixBatch.step_rows marked active advance; an idle row's tail is neither
         written nor read and its logits mean nothing.  Without a prepared step every row is active.  Nothing is read back to the
-        host.  CP = 1 and TP = 1; the bf16 weights are read whatever decode_weight_dtype says.  Returns [B, 1, vocab]."""
+        host.  CP = 1 and TP = 1; with decode_weight_dtype = "fp8_e4m3" the four linears read the FP8 copies (_rows_gemv), the head
+        stays bf16.  Returns [B, 1, vocab]."""
         c = self.cfg
         if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
             raise NotImplementedError("the shared-prefix decode step is built for CP = 1 and TP = 1")
@@ -829,19 +851,21 @@ class GPTVLModel:
         ws = self._ws.get(("prefix_batch", B))
         if ws is None:
             e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=tokens.device)  # noqa: E731
-            ws = self._ws[("prefix_batch", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn)}
+            ws = self._ws[("prefix_batch", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn),
+                                                  "x": e(B, c.hidden)}
+        w8 = self._w8_layers()                                  # FP8 weights: ops.gemv_rows_w8 in place of ops.gemv_rows (_rows_gemv)
         h = ops.row_gather(self.p["embed"], tokens, check_bounds=False)                   # [B, hidden]
         cos, sin = ops.rope_table(position, self.rotary_pos_emb.inv_freq)
         for li, lp in enumerate(self.p["layers"]):
             kv, ptrs = batch.prefix.key_value_memory_dict[li + 1], batch.tail_ptrs[li]
-            qkv = ops.gemv_rows(h, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], eps=c.eps)
+            qkv = self._rows_gemv(w8, li, h, "qkv_w", ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], xn=ws["x"])
             ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs, batch.tail_row_stride, batch.tail_group_stride,
                                  batch.append_rows, batch.caps)
             m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
             ctx = ops.prefix_batch_attn(m4[:, :, : c.qpg], kv[0], kv[1], batch.prefix_len, ptrs, batch.tail_row_stride,
                                         batch.tail_group_stride, batch.lens, batch.tail_cap, out=ws["ctx"])
-            ops.gemv_rows(ctx.view(B, -1), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
-            act = ops.gemv_rows(h, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], eps=c.eps)
-            ops.gemv_rows(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+            self._rows_gemv(w8, li, ctx.view(B, -1), "o_w", ops.EPI_RESIDUAL, residual=h, out=h)
+            act = self._rows_gemv(w8, li, h, "fc1_w", ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], xn=ws["x"])
+            self._rows_gemv(w8, li, act, "fc2_w", ops.EPI_RESIDUAL, residual=h, out=h)
         batch.advance()
         return ops.rmsnorm(h, self.p["final_ln"], c.eps)

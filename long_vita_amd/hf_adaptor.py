@@ -162,8 +162,9 @@ class LongVITAForCausalLM:
 
     @property
     def decode_weight_dtype(self) -> str:
-        """What the cached token step reads the decoder layers' linears from: "bf16" (default) or "fp8_e4m3" (e4m3 codes + a scale per
-        128 K elements of a weight row, kept next to the bf16 weights).  Lives on the model
+        """What the cached token step and the multi-row steps (beam, batched, shared-prefix) read the decoder layers' linears from:
+        "bf16" (default) or "fp8_e4m3" (e4m3 codes + a scale per 128 K elements of a weight row, kept next to the bf16 weights, which
+        prefill, extend and the head go on reading).  Lives on the model
         (GPTVLModel.decode_weight_dtype)."""
         return self.model.decode_weight_dtype
 

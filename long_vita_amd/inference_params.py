@@ -36,8 +36,9 @@ DECODE_WEIGHT_DTYPES = ("bf16", "fp8_e4m3")
 
 
 def check_decode_weight_dtype(name, allow_none: bool = False):
-    """What the cached token step reads the four linears of a decoder layer from: "bf16" (the default) or "fp8_e4m3" (OCP e4m3fn
-    codes + one fp32 scale per 128 consecutive K elements of a weight row).  Anything else is a ValueError."""
+    """What the cached token step and the multi-row steps (beam, batched, shared-prefix) read the four linears of a decoder layer
+    from: "bf16" (the default) or "fp8_e4m3" (OCP e4m3fn codes + one fp32 scale per 128 consecutive K elements of a weight row,
+    DESIGN.md 4.5).  Anything else is a ValueError."""
     if name is None and allow_none:
         return None
     if name not in DECODE_WEIGHT_DTYPES:

@@ -274,6 +274,7 @@ PROTOTYPES = {
     # FP8 (e4m3) decoder weights for the cached token step
     "vita_w8_quantize": (_i, [_p, _l, _l, _l, _p, _l, _p, _p]),
     "vita_gemv_w8": (_i, [_p, _p, _l, _p, _p, _l, _l, _i, _p, _p, _p, _f, _p]),
+    "vita_gemv_rows_w8": (_i, [_p, _l, _i, _p, _l, _p, _p, _l, _l, _l, _i, _p, _p, _l, _p]),
     "vita_decode_layer_attn_w8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(W8Layer), C.POINTER(Kv8Cache), _p]),
     "vita_decode_layer_mlp_w8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(W8Layer), _p]),
 }

@@ -1361,6 +1361,31 @@ def gemv_rows(x: torch.Tensor, w: torch.Tensor, epilogue: int = EPI_NONE, bias: 
     return y
 
 
+def gemv_rows_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+                 residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemv_rows over FP8 weights: y[b] = epilogue(dequant(codes, scales) . x[b]) for the rows of x [rows <= 8, K]; every code row and
+    its scales are read once for all of them, and row b has the bits of gemv_w8(x[b]) without gamma (normalise the rows with rmsnorm
+    first).  SWIGLU: codes of cat[gate, up], N = code rows / 2.  residual [rows, N], out [rows, N] (unit inner stride; out may alias
+    residual)."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("gemv_rows_w8: x must be [rows, K] with a unit inner stride")
+    rows, K = x.shape
+    n_rows, Kc = _w8_views(codes, scales, "gemv_rows_w8")
+    if Kc != K:
+        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, K = {K} expected")
+    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
+    y = torch.empty(rows, N, dtype=BF16, device=x.device) if out is None else out
+    if tuple(y.shape) != (rows, N) or y.stride(1) != 1:
+        raise ValueError("gemv_rows_w8: out must be [rows, N] with a unit inner stride")
+    if residual is not None and (tuple(residual.shape) != (rows, N) or residual.stride(1) != 1):
+        raise ValueError("gemv_rows_w8: residual must be [rows, N] with a unit inner stride")
+    _L.check(_L.load().vita_gemv_rows_w8(_dev(x, "x", BF16), x.stride(0), rows, _dev(codes, "codes"), codes.stride(0),
+                                         _dev(scales, "scales", torch.float32), _dev(y, "out", BF16), y.stride(0), N, K, epilogue,
+                                         _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
+                                         residual.stride(0) if residual is not None else 0, _stream()), "vita_gemv_rows_w8")
+    return y
+
+
 def beam_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, prefix_len: int, k_tail: torch.Tensor,
               v_tail: torch.Tensor, ancestry: torch.Tensor, n_gen: int, softmax_scale: Optional[float] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
