@@ -571,7 +571,11 @@ int vita_attn_delta(const void* o, const void* d_o, float* delta, int64_t rows, 
  * vita_flash_attn_fwd (chunk_len % 128 == 0).  q/k/v are the forward's (rotated) inputs, lse its
  * log-sum-exp output [n_q_heads, n_q_rows], delta from vita_attn_delta.  dk/dv are written for EVERY
  * key row of the visible K/V buffer (under context parallelism: the gathered layout, to be
- * reduce-scattered by the caller). */
+ * reduce-scattered by the caller).
+ * Alignment (anything else is VITA_ERR_UNSUPPORTED, refused before a launch): q / k / v / d_o 16-byte aligned with every stride a
+ * multiple of 8 elements (16-byte loads); lse / delta / q_seg_start / k_seg_end 4-byte aligned; the outputs a pass writes (dq; dk and
+ * dv) 8-byte aligned with every stride a multiple of 4 elements (8-byte stores).  Outputs that are also 16-byte aligned with strides
+ * of 8 elements take the 64-row kernels where the geometry allows them; the others run on the general kernels. */
 typedef struct {
   const void* q; int64_t q_row_stride, q_head_stride, q_group_stride;
   const void* k; int64_t k_row_stride, k_head_stride;

@@ -538,6 +538,17 @@ extern "C" int vita_flash_attn_bwd_parts(const vita_attn_bwd_params* p, int part
                              p->do_head_stride};
   for (int64_t s : strides)
     if (s & 7) return VITA_ERR_UNSUPPORTED;
+  // every kernel reads q / d_o / k / v 16 bytes at a time (bf16x8 loads, 16-byte LDS-DMA pieces) and lse / delta / the segment tables as
+  // 4-byte words; the general kernels store dq / dk / dv 8 bytes at a time (the 64-row kernels 16: their _eligible() hands an output that
+  // is only 8-byte aligned to the general ones).  Refused here, before anything is launched.
+  if (((uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v | (uintptr_t)p->d_o) & 15) return VITA_ERR_UNSUPPORTED;
+  if (((uintptr_t)p->lse | (uintptr_t)p->delta | (uintptr_t)p->q_seg_start | (uintptr_t)p->k_seg_end) & 3) return VITA_ERR_UNSUPPORTED;
+  if ((parts & VITA_ATTN_BWD_DQ) &&
+      (((uintptr_t)p->dq & 7) || ((p->dq_row_stride | p->dq_head_stride | p->dq_group_stride) & 3)))
+    return VITA_ERR_UNSUPPORTED;
+  if ((parts & VITA_ATTN_BWD_DKV) &&
+      ((((uintptr_t)p->dk | (uintptr_t)p->dv) & 7) || ((p->dk_row_stride | p->dk_head_stride | p->dv_row_stride | p->dv_head_stride) & 3)))
+    return VITA_ERR_UNSUPPORTED;
   BwdArgs a;
   const int G = p->n_q_heads / p->n_kv_heads;
   a.q = (const bf16_t*)p->q; a.q_rs = p->q_row_stride; a.q_hs = p->q_head_stride;
