@@ -755,6 +755,40 @@ int vita_prefix_batch_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_gr
                                const int32_t* tail_lens, int tail_cap, int n_rows, int n_q_heads, int n_kv_heads, int head_dim,
                                float softmax_scale, void* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The rows' own prompt tokens behind the shared prefix in ONE pass (the rows' questions about one video): what the loop above
+ * teacher-forces one token per step, M/inference/text_generation/generation.py:33-280, as vita_flash_attn_extend_fwd does for one
+ * request — but a row's keys are not contiguous: the prefix lives in the prefix request's cache, the row's own tokens in its tail.
+ *
+ * vita_prefix_extend_attn_fwd: the contexts out [n_tokens][n_q_heads][128] (bf16, dense) of n_tokens query rows of the mixed QKV
+ *   buffer (addressed as for vita_flash_attn_extend_fwd).  The rows belong to n_rows <= 8 segments, one per continuation row b:
+ *   segments is int32 [n_rows][3] in device memory = (first query row, count_b, tail0_b), tail0_b the rows b's tail held before this
+ *   pass.  Query i of segment b sees the rows [0, prefix_len) of k_cache / v_cache (never written; rows behind prefix_len never
+ *   read) and the rows [0, tail0_b + i] of row b's tail, reached through tail_ptrs / tail_row_stride / tail_group_stride / tail_cap
+ *   as in vita_prefix_batch_attn_fwd; the new tokens' rotated K / V are already in the tail at rows [tail0_b, tail0_b + count_b),
+ *   and nothing behind them is read.  count_b = 0: an idle row — neither its tail nor its entry of tail_ptrs is read.  A query row
+ *   no segment names gets the attention over the prefix alone.  Every triple is clamped on the device before it forms an address:
+ *   first into [0, n_tokens], tail0 into [0, tail_cap], count into [0, min(max_count, n_tokens - first, tail_cap - tail0)].
+ *   n_tokens and max_count (the largest count) are host arguments: they size the grids.  The prefix pass is
+ *   vita_flash_attn_extend_fwd's kernel over the prefix with every key visible (key splits by vita_beam_attn_fwd's rule for n_tokens
+ *   rows); the tail pass is ONE launch of the same kernel for all segments (MFMA, the diagonal at the segment's first query) that
+ *   writes one more part; the merge is vita_beam_attn_fwd's.  Both passes take two bf16 terms of P while n_tokens * (n_q_heads /
+ *   n_kv_heads) <= 256 and one beyond, as vita_flash_attn_extend_fwd does; no intermediate context is rounded to bf16.  The
+ *   workspace (vita_prefix_extend_attn_workspace_bytes, 16-byte aligned; 0 for a shape the entry refuses) holds the fp32 partials.
+ * Nothing is launched on a refusal and out stays untouched: a null pointer, n_rows < 1, n_tokens < 1, max_count < 0,
+ * prefix_len <= 0, a scale that is not positive and finite, tail_cap < 0, a workspace that is too short: VITA_ERR_INVALID_ARG;
+ * n_rows > 8, n_tokens > 32768, n_q_heads / n_kv_heads > 8, head_dim != 128, a stride that is not a multiple of 8, a base that is
+ * not 16-byte aligned: VITA_ERR_UNSUPPORTED.
+ * M/inference/text_generation/generation.py:33-280 */
+size_t vita_prefix_extend_attn_workspace_bytes(int64_t n_tokens, int n_q_heads, int64_t prefix_len);
+/* M/inference/text_generation/generation.py:33-280 */
+int vita_prefix_extend_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                                const void* k_cache, const void* v_cache, int64_t kv_row_stride, int64_t kv_group_stride,
+                                int64_t prefix_len, const void* tail_ptrs, int64_t tail_row_stride, int64_t tail_group_stride,
+                                int tail_cap, const int32_t* segments, int n_rows, int64_t n_tokens, int max_count, int n_q_heads,
+                                int n_kv_heads, int head_dim, float softmax_scale, void* out, void* workspace,
+                                size_t workspace_bytes, void* stream);
+
 /* out[n] = bf16(a[n] + b[n]) (n % 8 == 0): the residual add that follows the tensor-parallel all-reduce of a
  * row-parallel linear's output (RowParallelLinear + bias_dropout_add, TP > 1 only; at TP = 1 the add is the GEMM's
  * RESIDUAL epilogue).

@@ -47,7 +47,50 @@ struct ExtArgs {
   int quant_m;                   // running max kept on integers (log2 domain): see the kernel's main loop
   int partial_out;               // write the fp32 partials even with one split (the beam step merges them with its tail partial)
   float scale_log2e;
+  // the segment launch alone (flash_extend_kernel<., true>, vita_prefix_extend_attn_fwd): see segment_args
+  const bf16_t* const* tail_ptrs; const int* seg;
+  int n_seg, seg_max_count, tail_cap;
 };
+
+// ---- the segment launch: up to 8 continuation rows b, each with count_b NEW tokens behind tail0_b rows of its own tail ---------------
+// seg [n_seg][3] (int32, device) = (first query row, count, tail0).  Every triple is clamped before it forms an address: first into
+// [0, t], tail0 into [0, tail_cap], count into [0, min(seg_max_count, t - first, tail_cap - tail0)].
+struct Segment { int first, count, tail0; };
+__device__ __forceinline__ Segment clamped_segment(const ExtArgs& p, int b) {
+  Segment s = {p.seg[3 * b], p.seg[3 * b + 1], p.seg[3 * b + 2]};
+  s.first = min(max(s.first, 0), p.t);
+  s.tail0 = min(max(s.tail0, 0), p.tail_cap);
+  s.count = min(min(max(s.count, 0), p.seg_max_count), min(p.t - s.first, p.tail_cap - s.tail0));
+  return s;
+}
+// The launch's arguments (t = all query rows, n_splits = the part the launch writes, kv strides = the tails') as those of segment sg
+// alone: its queries against its tail, rows [0, tail0) visible to all of them and the diagonal behind.  A segment with count > 0 reads
+// its entry of tail_ptrs; nothing else does.
+__device__ __forceinline__ ExtArgs segment_args(const ExtArgs& p, int b, const Segment& sg) {
+  ExtArgs s = p;
+  s.q = p.q + (int64_t)sg.first * p.q_rs;
+  s.k = p.tail_ptrs[2 * b]; s.v = p.tail_ptrs[2 * b + 1];
+  s.t = sg.count;
+  s.n_full = sg.tail0; s.n_keys = sg.tail0 + sg.count;
+  s.q_pos0 = 0; s.key_pos0 = 0; s.key_pos_step = 1;
+  return s;
+}
+// Query rows no segment names get the merge's neutral element in the launch's part (the blocks behind the last segment)
+__device__ __forceinline__ void fill_unnamed_rows(const ExtArgs& p, int block, int n_blocks) {
+  const int64_t heads = (int64_t)p.n_kv_heads * p.G, n_rec = heads * p.t;
+  for (int64_t i = (int64_t)block * 512 + threadIdx.x; i < n_rec; i += (int64_t)n_blocks * 512) {
+    const int row = (int)(i % p.t);
+    bool named = false;
+    for (int b = 0; b < p.n_seg; ++b) {
+      const Segment sg = clamped_segment(p, b);
+      named = named || (row >= sg.first && row < sg.first + sg.count);
+    }
+    if (named) continue;
+    const int64_t rec = (int64_t)p.n_splits * n_rec + i;
+    p.pm[rec] = -1.0e30f; p.pl[rec] = 0.f;
+    for (int d = 0; d < 128; d += 4) *reinterpret_cast<f32x4*>(p.po + rec * 128 + d) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
 
 // last visible key of query row i (-1: none)
 __device__ __forceinline__ int last_visible_key(const ExtArgs& p, int i) {
@@ -62,8 +105,21 @@ __device__ __forceinline__ int last_visible_key(const ExtArgs& p, int i) {
 // of a single bf16 p is the largest error of the whole kernel (it does not average out: the error sum has the size of the output sum).
 // Used when all stacked rows fit ONE query tile (t * G <= 256: a launch that streams K/V once, the decode kernels' regime); it costs
 // 16 more MFMAs per tile (48 instead of 32).  Longer launches keep the prefill kernels' single bf16 term.
-template <bool SPLIT_P>
-__global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
+// SEG: the segment launch, grid (kv head, query tile of the longest segment, segment b — and one more index for fill_unnamed_rows).  A
+// workgroup runs this same body on segment_args; its partial goes to part n_splits of the LAUNCH's records, at row first_b + i.
+template <bool SPLIT_P, bool SEG = false>
+__global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs launch) {
+  ExtArgs seg_args;
+  int seg_first = 0;
+  if constexpr (SEG) {
+    const int b = blockIdx.z;
+    if (b == launch.n_seg) { fill_unnamed_rows(launch, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y); return; }
+    const Segment sg = clamped_segment(launch, b);
+    if ((int)blockIdx.y * QTILE >= sg.count * launch.G) return;          // an idle row (count 0) among them
+    seg_args = segment_args(launch, b, sg);
+    seg_first = sg.first;
+  }
+  const ExtArgs& p = SEG ? seg_args : launch;
   using T = fwd8::Tile<D>;
   constexpr int DS = T::DS, DB = T::DB, SLOTB = T::SLOTB;
 
@@ -77,8 +133,8 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
   // ---- work decomposition: block = (kv head, key split, query tile), late (long) query tiles first -----------------------------
   int bid = blockIdx.x;
   const int kvh = bid % p.n_kv_heads; bid /= p.n_kv_heads;
-  const int split = bid % p.n_splits;
-  const int qt = p.n_q_tiles - 1 - bid / p.n_splits;
+  const int split = SEG ? 0 : bid % p.n_splits;
+  const int qt = SEG ? (int)blockIdx.y : p.n_q_tiles - 1 - bid / p.n_splits;
   const int G = p.G;
   const int n_stack = p.t * G;                                  // stacked rows of this kv group
   const int s_wg = qt * QTILE, s_wave = s_wg + wave * 32;
@@ -170,7 +226,8 @@ __global__ __launch_bounds__(512, 2) void flash_extend_kernel(ExtArgs p) {
     fwd8::store_row_bf16<D>(p.o + (int64_t)my_row * p.o_rs + (int64_t)head * p.o_hs, o_acc, l_tot > 0.f ? 1.0f / l_tot : 0.f, hi);
     if (p.lse && hi == 0) p.lse[(int64_t)head * p.t + my_row] = fwd8::lse_natural(m_run, l_tot);
   } else {
-    const int64_t rec = ((int64_t)split * (p.n_kv_heads * G) + head) * p.t + my_row;
+    const int64_t rec = SEG ? ((int64_t)launch.n_splits * (p.n_kv_heads * G) + head) * launch.t + seg_first + my_row
+                            : ((int64_t)split * (p.n_kv_heads * G) + head) * p.t + my_row;
     float* po = p.po + rec * D;
 #pragma unroll
     for (int db = 0; db < DB; ++db) {
@@ -425,8 +482,10 @@ int beam_splits(int n_beams, int n_q_heads, int64_t prefix_len) {
   return splits;
 }
 
-bool beam_shape_ok(int n_beams, int n_q_heads, int64_t prefix_len) {
-  return n_beams >= 1 && n_beams <= kBeamMax && n_q_heads > 0 && prefix_len > 0 && prefix_len <= 0x7fffffffLL - 256;
+constexpr int kPrefixExtendMaxTokens = 1 << 15;         // query rows of one ragged pass (vita_prefix_extend_attn_fwd)
+
+bool beam_shape_ok(int n_beams, int n_q_heads, int64_t prefix_len, int max_rows = kBeamMax) {
+  return n_beams >= 1 && n_beams <= max_rows && n_q_heads > 0 && prefix_len > 0 && prefix_len <= 0x7fffffffLL - 256;
 }
 
 }  // namespace
@@ -525,8 +584,9 @@ int prefix_args_invalid(const PrefixArgs& p) {
   return VITA_OK;
 }
 
-int prefix_args_unsupported(const PrefixArgs& p) {
-  if (p.head_dim != D || p.n_q_heads / p.n_kv_heads > 8 || !beam_shape_ok(p.n_rows, p.n_q_heads, p.prefix_len)) return VITA_ERR_UNSUPPORTED;
+int prefix_args_unsupported(const PrefixArgs& p, int max_rows = kBeamMax) {
+  if (p.head_dim != D || p.n_q_heads / p.n_kv_heads > 8 || !beam_shape_ok(p.n_rows, p.n_q_heads, p.prefix_len, max_rows))
+    return VITA_ERR_UNSUPPORTED;
   const int64_t strides[] = {p.q_rs, p.q_gs, p.q_hs, p.kv_rs, p.kv_gs};
   for (int64_t s : strides)
     if (s & 7) return VITA_ERR_UNSUPPORTED;            // 16-byte vector loads / LDS-DMA pieces
@@ -535,15 +595,16 @@ int prefix_args_unsupported(const PrefixArgs& p) {
   return (bases & 15) ? VITA_ERR_UNSUPPORTED : VITA_OK;
 }
 
-// flash_extend_kernel<true> over the prefix, every key visible to every row; the partials stay in the workspace, one more part kept
-// free behind the splits for the tail pass
+// flash_extend_kernel over the prefix, every key visible to every row (<true> while the stacked rows fit one query tile: the beams
+// and the batched step always, a ragged pass of n_rows * G <= 256); the partials stay in the workspace, one more part kept free behind
+// the splits for the tail pass
 int prefix_pass(const PrefixArgs& p, ExtArgs& a, hipStream_t st) {
   a.q = (const bf16_t*)p.q; a.q_rs = p.q_rs; a.q_gs = p.q_gs; a.q_hs = p.q_hs;
   a.k = (const bf16_t*)p.k; a.v = (const bf16_t*)p.v; a.kv_rs = p.kv_rs; a.kv_gs = p.kv_gs;
   a.o = (bf16_t*)p.out; a.o_rs = (int64_t)p.n_q_heads * D; a.o_hs = D;
   a.lse = nullptr;
   a.t = p.n_rows; a.G = p.n_q_heads / p.n_kv_heads; a.n_kv_heads = p.n_kv_heads;
-  a.n_q_tiles = 1;                                              // B * qpg <= 64 stacked rows: one query tile
+  a.n_q_tiles = (p.n_rows * a.G + QTILE - 1) / QTILE;            // 1 for B <= 8 rows (B * qpg <= 64 stacked rows)
   a.n_keys = (int)p.prefix_len; a.n_full = (int)p.prefix_len;   // every prefix key is visible to every row
   a.q_pos0 = 0; a.key_pos0 = 0; a.key_pos_step = 1;
   a.n_splits = beam_splits(p.n_rows, p.n_q_heads, p.prefix_len);
@@ -564,8 +625,11 @@ int prefix_pass(const PrefixArgs& p, ExtArgs& a, hipStream_t st) {
   static std::atomic<unsigned long long> attr_set{0};
   vita_device_once(attr_set, [&] {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_extend_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_extend_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
   });
-  hipLaunchKernelGGL(flash_extend_kernel<true>, dim3((unsigned)(p.n_kv_heads * a.n_splits)), dim3(512), lds, st, a);
+  const dim3 grid((unsigned)(p.n_kv_heads * a.n_q_tiles * a.n_splits));
+  if (a.n_q_tiles == 1) hipLaunchKernelGGL(flash_extend_kernel<true>, grid, dim3(512), lds, st, a);
+  else hipLaunchKernelGGL(flash_extend_kernel<false>, grid, dim3(512), lds, st, a);
   return vita_check_launch();
 }
 
@@ -653,6 +717,61 @@ extern "C" int vita_prefix_batch_attn_fwd(const void* q, int64_t q_row_stride, i
     VITA_PREFIX_TAIL(7) VITA_PREFIX_TAIL(8)
   }
 #undef VITA_PREFIX_TAIL
+  rc = vita_check_launch();
+  if (rc != VITA_OK) return rc;
+  return prefix_merge(a, st);
+}
+
+// ---- a ragged pass behind the shared prefix: count_b new tokens of every continuation row b in one launch set ------------------------
+// The prefix pass with t = n_tokens query rows, the segment launch of flash_extend_kernel for every row's new tokens over its own
+// tail (part n_splits), the merge.  Both launches take two bf16 terms of P while n_tokens * G <= 256, one beyond (SPLIT_P's rule).
+extern "C" size_t vita_prefix_extend_attn_workspace_bytes(int64_t n_tokens, int n_q_heads, int64_t prefix_len) {
+  if (n_tokens > kPrefixExtendMaxTokens || !beam_shape_ok((int)n_tokens, n_q_heads, prefix_len, kPrefixExtendMaxTokens)) return 0;
+  return (size_t)(beam_splits((int)n_tokens, n_q_heads, prefix_len) + 1) * (size_t)n_q_heads * (size_t)n_tokens * (D + 2) * sizeof(float);
+}
+
+extern "C" int vita_prefix_extend_attn_fwd(const void* q, int64_t q_row_stride, int64_t q_group_stride, int64_t q_head_stride,
+                                           const void* k_cache, const void* v_cache, int64_t kv_row_stride, int64_t kv_group_stride,
+                                           int64_t prefix_len, const void* tail_ptrs, int64_t tail_row_stride,
+                                           int64_t tail_group_stride, int tail_cap, const int32_t* segments, int n_rows,
+                                           int64_t n_tokens, int max_count, int n_q_heads, int n_kv_heads, int head_dim,
+                                           float softmax_scale, void* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_tokens < 1) return VITA_ERR_INVALID_ARG;
+  if (n_tokens > kPrefixExtendMaxTokens) return VITA_ERR_UNSUPPORTED;
+  const PrefixArgs p = {q, q_row_stride, q_group_stride, q_head_stride, k_cache, v_cache, kv_row_stride, kv_group_stride, prefix_len,
+                        (int)n_tokens, n_q_heads, n_kv_heads, head_dim, softmax_scale, out, workspace, workspace_bytes};
+  int rc = prefix_args_invalid(p);
+  if (rc != VITA_OK) return rc;
+  if (!tail_ptrs || !segments || n_rows < 1 || max_count < 0 || tail_cap < 0 || tail_row_stride <= 0 || tail_group_stride < 0)
+    return VITA_ERR_INVALID_ARG;
+  if (workspace_bytes < vita_prefix_extend_attn_workspace_bytes(n_tokens, n_q_heads, prefix_len)) return VITA_ERR_INVALID_ARG;
+  rc = prefix_args_unsupported(p, kPrefixExtendMaxTokens);
+  if (rc != VITA_OK) return rc;
+  if (n_rows > kBeamMax) return VITA_ERR_UNSUPPORTED;
+  if ((tail_row_stride | tail_group_stride) & 7) return VITA_ERR_UNSUPPORTED;          // LDS-DMA pieces of the tail rows
+  if (tail_row_stride * KVT > 0x7fffffffLL) return VITA_ERR_UNSUPPORTED;               // 32-bit lane offsets inside a tile
+  if (((uintptr_t)tail_ptrs & 7) || ((uintptr_t)segments & 3)) return VITA_ERR_UNSUPPORTED;
+
+  ExtArgs a;
+  hipStream_t st = (hipStream_t)stream;
+  rc = prefix_pass(p, a, st);
+  if (rc != VITA_OK) return rc;
+  ExtArgs s = a;                                                  // t = n_tokens and n_splits = the part to write stay the launch's
+  s.kv_rs = tail_row_stride; s.kv_gs = tail_group_stride;
+  s.tail_ptrs = (const bf16_t* const*)tail_ptrs; s.seg = (const int*)segments;
+  s.n_seg = n_rows; s.tail_cap = tail_cap;
+  s.seg_max_count = (int)(max_count < n_tokens ? max_count : n_tokens);
+  s.n_q_tiles = s.seg_max_count > 0 ? (s.seg_max_count * a.G + QTILE - 1) / QTILE : 1;
+  s.tiles_per_split = (tail_cap + KVT - 1) / KVT + 1;             // one split: every tile of a tail
+  constexpr int lds = 2 * 2 * KVT * D * 2;
+  static std::atomic<unsigned long long> attr_set{0};
+  vita_device_once(attr_set, [&] {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_extend_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&flash_extend_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  });
+  const dim3 sgrid((unsigned)n_kv_heads, (unsigned)s.n_q_tiles, (unsigned)n_rows + 1);
+  if (a.n_q_tiles == 1) hipLaunchKernelGGL((flash_extend_kernel<true, true>), sgrid, dim3(512), lds, st, s);
+  else hipLaunchKernelGGL((flash_extend_kernel<false, true>), sgrid, dim3(512), lds, st, s);
   rc = vita_check_launch();
   if (rc != VITA_OK) return rc;
   return prefix_merge(a, st);

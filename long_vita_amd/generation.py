@@ -142,7 +142,7 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
                                                     use_eod_token_for_early_termination=True, external_inputs=None,
                                                     *, use_kv_cache=True, logit_mask=True, termination_id=None,
                                                     reference_compat=False, token_selector=None, kv_cache_dtype=None,
-                                                    shared_prefix_len=None):
+                                                    shared_prefix_len=None, prefill_suffixes=False):
     """Generator with the reference's contract (:33-280): `tokens` [1, max_sequence_length] holds the prompt
     (length lengths[0]) followed by padding and is filled in place; yields (tokens[:, :ctx+1], lengths,
     output_log_probs) per generated token.  args.use_kv_cache / args.logit_mask / the tokenizer's eod are keyword
@@ -163,13 +163,16 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
 
     shared_prefix_len=P (b = 2 .. 8 rows whose first P tokens are the same — several questions about one video; CP = 1, TP = 1,
     bf16 cache): _generate_shared_prefix below — tokens[0, :P] is prefilled ONCE and every row reads that cache.  None: nothing
-    changes."""
+    changes.  prefill_suffixes=True (with shared_prefix_len only): the rows' own prompt tokens behind the prefix are fed in ONE
+    ragged pass right after the prefill instead of one teacher-forced token per step; what is yielded keeps its number and widths."""
     from .inference_params import ForwardStep
     batch_size, max_sequence_length = tokens.shape
+    if prefill_suffixes and shared_prefix_len is None:
+        raise ValueError("prefill_suffixes feeds the rows' prompts behind a shared prefix: it needs shared_prefix_len")
     if shared_prefix_len is not None:
         yield from _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_output_log_probs, do_sample, top_k, top_p,
                                            temperature, use_eod_token_for_early_termination, external_inputs, use_kv_cache, logit_mask,
-                                           termination_id, reference_compat, token_selector, kv_cache_dtype)
+                                           termination_id, reference_compat, token_selector, kv_cache_dtype, bool(prefill_suffixes))
         return
     if batch_size > 1:
         yield from _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample, top_k, top_p, temperature,
@@ -342,7 +345,7 @@ def _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample
 
 def _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_output_log_probs, do_sample, top_k, top_p, temperature,
                             use_eod_token_for_early_termination, external_inputs, use_kv_cache, logit_mask, termination_id,
-                            reference_compat, token_selector, kv_cache_dtype):
+                            reference_compat, token_selector, kv_cache_dtype, prefill_suffixes=False):
     """The loop of :33-280 for tokens [B, max_sequence_length] and lengths [B], B = 2 .. 8, whose rows share their first P =
     shared_prefix_len tokens (CP = 1, TP = 1, bf16 cache).  The generator walks context_length from P to max_sequence_length and
     yields (tokens[:, :context_length + 1], lengths, output_log_probs); row b is written from position lengths[b] on (started =
@@ -357,6 +360,12 @@ def _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_ou
     returns [B]; the entries of rows that are not written mean nothing.  Termination is :239-246, sticky per row as in
     _generate_batched; a finished row goes idle and the loop ends when every row is done.  output_log_probs[b, p] is filled where
     row b is live (started and not finished) and is NaN at the other positions from P - 1 on.
+
+    prefill_suffixes: right behind the prefill ONE ragged pass (SharedPrefixBatch.extend_rows, GPTVLModel._prefix_extend_forward)
+    feeds tokens[b, P:lengths[b]] of every row with lengths[b] > P, concatenated in row order.  A row still inside its prompt is
+    then IDLE, not teacher-forced; at context_length == lengths[b] its logits are its row of the pass (the prefill's last row for a
+    row without a suffix, as ever), and a step of the model runs only when some unfinished row has lengths[b] < context_length.
+    The yields, termination, the NaN log-prob rows inside prompts and token_selector are the same.
 
     Every refusal is raised before anything is launched: B outside 2 .. 8, P < 1, lengths[b] < P, prefixes that differ (ValueError),
     use_kv_cache=False (ValueError), CP or TP > 1, an FP8 cache (NotImplementedError)."""
@@ -403,10 +412,28 @@ def _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_ou
     if return_output_log_probs:
         output_log_probs = torch.empty((B, max_sequence_length - 1, vocab), dtype=torch.float32, device=dev)
     done = [False] * B
+    pass_logits = None
+    if prefill_suffixes and max(lens) > P:
+        batch.extend_rows([n - P for n in lens])
+        fed = [b for b in range(B) if lens[b] > P]
+        pass_logits = model(torch.cat([tokens[b, P: lens[b]] for b in fed])[None],
+                            torch.cat([position_ids[0, P: lens[b]] for b in fed])[None], None, inference_params=batch)[:, -1, :]
     for context_length in range(P, max_sequence_length):
         live = [lens[b] <= context_length and not done[b] for b in range(B)]
         if context_length == P:
             last_token_logits = prefill_logits[None, :].expand(B, vocab).clone()
+        elif prefill_suffixes:
+            active = [lens[b] < context_length and not done[b] for b in range(B)]
+            if any(active):
+                batch.step_rows(active)
+                logits = model(tokens[:, context_length - 1: context_length],
+                               position_ids[:, context_length - 1: context_length].expand(B, 1), None, inference_params=batch)
+                last_token_logits = logits[:, -1, :].clone()
+            else:
+                last_token_logits = torch.zeros(B, vocab, dtype=prefill_logits.dtype, device=dev)
+            for b in range(B):
+                if lens[b] == context_length:
+                    last_token_logits[b] = pass_logits[b]
         else:
             batch.step_rows([not d for d in done])
             logits = model(tokens[:, context_length - 1: context_length],

@@ -293,6 +293,8 @@ class GPTVLModel:
         if isinstance(ip, DecodeBatch):
             return self._batch_forward(input_ids, position_ids, ip)
         if isinstance(ip, SharedPrefixBatch):
+            if ip.pass_segments is not None:             # extend_rows prepared a ragged pass
+                return self._prefix_extend_forward(input_ids, position_ids, ip)
             return self._prefix_batch_forward(input_ids, position_ids, ip)
         if ip is not None:
             if getattr(ip, "external_inputs", None) is not None and not ip.key_value_memory_dict:   # :261-266
@@ -869,3 +871,62 @@ class GPTVLModel:
             self._rows_gemv(w8, li, act, "fc2_w", ops.EPI_RESIDUAL, residual=h, out=h)
         batch.advance()
         return ops.rmsnorm(h, self.p["final_ln"], c.eps)
+
+    def _prefix_extend_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], batch: SharedPrefixBatch) -> torch.Tensor:
+        """The rows' own prompt tokens behind the shared prefix in ONE pass (what the reference's loop teacher-forces one token per
+        step, M/inference/text_generation/generation.py:33-280): the pass SharedPrefixBatch.extend_rows(counts) prepared.  tokens
+        [1, n] are the rows' new tokens concatenated in row order, positions [1, n] (None: behind the prefix and each row's tail).
+        _extend_forward's layers on n rows — ops.rmsnorm, ops.gemm, ops.rope_qkv_: bf16 GEMMs whatever decode_weight_dtype says, as
+        the prefill and the extend — with each segment's K / V copied to its tail at [tail0, tail0 + count) and
+        ops.prefix_extend_attn over the prefix (read once per kv group for all n rows) and each row's tail.  The head runs for each
+        segment's LAST row only.  Returns [B, 1, vocab]; the logits of an idle row (count 0) mean nothing.  CP = 1 and TP = 1."""
+        c = self.cfg
+        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
+            raise NotImplementedError("the shared-prefix decode step is built for CP = 1 and TP = 1")
+        segs = batch.pass_segments
+        B, n = len(batch), sum(s[1] for s in segs)
+        if tuple(input_ids.shape) != (1, n):
+            raise ValueError(f"the prepared pass takes tokens [1, {n}]: the rows' new tokens in row order")
+        dev = input_ids.device
+        if position_ids is None:
+            position = torch.tensor([batch.prefix_len + tail0 + i for _, count, tail0 in segs for i in range(count)], dtype=torch.long,
+                                    device=dev)
+        elif tuple(position_ids.shape) != (1, n):
+            raise ValueError(f"the prepared pass takes positions [1, {n}]")
+        else:
+            position = position_ids[0].contiguous()
+        batch.consumed_tokens = n
+        ws = self._ws.get(("prefix_extend", n))
+        if ws is None:
+            e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=dev)  # noqa: E731
+            self._ws = {k: v for k, v in self._ws.items() if not (isinstance(k, tuple) and k[0] == "prefix_extend")}   # one size
+            ws = self._ws[("prefix_extend", n)] = {"x": e(n, c.hidden), "qkv": e(n, c.qkv_out), "ctx": e(n, c.heads, c.head_dim),
+                                                   "act": e(n, c.ffn)}
+        last = torch.tensor([first + count - 1 if count else 0 for first, count, _ in segs], dtype=torch.long, device=dev)
+        with tracing.range("prefix extend: embedding"):
+            h = ops.row_gather(self.p["embed"], input_ids[0].contiguous())                # [n, hidden]
+        cos, sin = ops.rope_table(position, self.rotary_pos_emb.inv_freq)
+        for li, lp in enumerate(self.p["layers"]):
+            with tracing.range(f"prefix extend: layer {li}"):
+                kv, tails = batch.prefix.key_value_memory_dict[li + 1], batch.tails[li]
+                x = ops.rmsnorm(h, lp["ln1"], c.eps, out=ws["x"])
+                qkv = ops.gemm(x, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"])
+                ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, None, 1)
+                m4 = qkv.view(n, c.kv_groups, c.qpg + 2, c.head_dim)
+                for b, (first, count, tail0) in enumerate(segs):
+                    if count:
+                        tails[0, b, tail0: tail0 + count].copy_(m4[first: first + count, :, c.qpg])
+                        tails[1, b, tail0: tail0 + count].copy_(m4[first: first + count, :, c.qpg + 1])
+                ctx = ops.prefix_extend_attn(m4[:, :, : c.qpg], kv[0], kv[1], batch.prefix_len, batch.tail_ptrs[li], batch.tail_row_stride,
+                                             batch.tail_group_stride, batch.tail_cap, segs, out=ws["ctx"], table=batch.segments)
+                ops.gemm(ctx.view(n, c.heads * c.head_dim), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+                x = ops.rmsnorm(h, lp["ln2"], c.eps, out=ws["x"])
+                act = ops.gemm(x, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"])
+                ops.gemm(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+        batch.advance()
+        rows = ops.rmsnorm(ops.row_gather(h, last), self.p["final_ln"], c.eps)
+        logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)
+        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)
+        if bool(torch.isnan(logits.float().sum())):                                       # as the extend (gpt_vl_model.py:393-396)
+            raise ValueError("found NaN in local forward logits calculation")
+        return logits.contiguous()                                                        # [B, 1, vocab]

@@ -235,7 +235,12 @@ class SharedPrefixBatch:
     step_rows(active) / advance() keep DecodeBatch's contract: an active row appends at its tail length and attends to the prefix
     and tail length + 1 rows, an inactive one gets append = -1 and len = 0 (its tail is neither written nor read).  lens /
     append_rows (int32, device) are one upload from the host mirror host_lens; nothing is read back.  Row b's next token sits at
-    position prefix_len + host_lens[b]."""
+    position prefix_len + host_lens[b].
+
+    extend_rows(counts) prepares a ragged PASS instead (GPTVLModel._prefix_extend_forward): counts[b] >= 0 new tokens of row b, fed
+    concatenated in row order, so row b's first query row is sum(counts[:b]).  segments (int32 [n_rows, 3] on the device: first
+    query row, count, tail0 = the tail rows the row already held) is one upload per pass; pass_segments is its host mirror.
+    advance() moves host_lens by the counts.  A prepared step and a prepared pass exclude each other."""
 
     def __init__(self, ip, n_rows: int, tail_cap: int):
         if not isinstance(ip, InferenceParams):
@@ -275,6 +280,8 @@ class SharedPrefixBatch:
         self._step = torch.zeros(2, n_rows, dtype=torch.int32, device=self.device)      # one upload per step: lens, append_rows
         self.lens, self.append_rows = self._step[0], self._step[1]
         self.active = None                   # the rows of the prepared step; None: no step is prepared
+        self.segments = torch.zeros(n_rows, 3, dtype=torch.int32, device=self.device)   # one upload per pass
+        self.pass_segments = None            # [[first, count, tail0]] of the prepared pass; None: no pass is prepared
         self.consumed_tokens = None
         self.sequence_len_offset = ip.sequence_len_offset
         self.use_kv_cache = True
@@ -287,6 +294,8 @@ class SharedPrefixBatch:
         return [self.prefix_len + n for n in self.host_lens]
 
     def step_rows(self, active):
+        if self.pass_segments is not None:
+            raise ValueError("step_rows: a pass is prepared (extend_rows) and has not run")
         active = [bool(a) for a in active]
         if len(active) != self.n_rows:
             raise ValueError(f"step_rows: {self.n_rows} flags expected")
@@ -299,7 +308,31 @@ class SharedPrefixBatch:
         self.active = active
         return max(lens)
 
+    def extend_rows(self, counts):
+        """Prepare a pass of counts[b] >= 0 new tokens per row; returns their sum (the query rows of the pass)."""
+        if self.active is not None:
+            raise ValueError("extend_rows: a step is prepared (step_rows) and has not run")
+        counts = [int(n) for n in counts]
+        if len(counts) != self.n_rows:
+            raise ValueError(f"extend_rows: {self.n_rows} counts expected")
+        if min(counts) < 0 or sum(counts) < 1:
+            raise ValueError("extend_rows: counts >= 0 and at least one new token")
+        for b, n in enumerate(counts):
+            if self.host_lens[b] + n > self.tail_cap:
+                raise RuntimeError("the rows' tail cache is full (max_sequence_length reached)")
+        table, first = [], 0
+        for b, n in enumerate(counts):
+            table.append([first, n, self.host_lens[b]])
+            first += n
+        self.segments.copy_(torch.tensor(table, dtype=torch.int32))                     # host -> device; nothing is read back
+        self.pass_segments = table
+        return first
+
     def advance(self):
+        if self.pass_segments is not None:
+            for b, (_, n, _) in enumerate(self.pass_segments):
+                self.host_lens[b] += n
+            self.pass_segments = None
         for b, a in enumerate(self.active or ()):
             if a:
                 self.host_lens[b] += 1

@@ -267,6 +267,10 @@ PROTOTYPES = {
     # several continuations of one prefilled prefix (generation.py:33-280, shared_prefix_len)
     "vita_prefix_batch_attn_workspace_bytes": (C.c_size_t, [_i, _i, _l]),
     "vita_prefix_batch_attn_fwd": (_i, [_p, _l, _l, _l, _p, _p, _l, _l, _l, _p, _l, _l, _p, _i, _i, _i, _i, _i, _f, _p, _p, C.c_size_t, _p]),
+    # the rows' own prompt tokens behind that prefix in one pass (generation.py:33-280, prefill_suffixes)
+    "vita_prefix_extend_attn_workspace_bytes": (C.c_size_t, [_l, _i, _l]),
+    "vita_prefix_extend_attn_fwd": (_i, [_p, _l, _l, _l, _p, _p, _l, _l, _l, _p, _l, _l, _i, _p, _i, _l, _i, _i, _i, _i, _f, _p, _p,
+                                         C.c_size_t, _p]),
     # FP8 (e4m3) KV cache for the cached decode
     "vita_kv8_store": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _p, _l, _l, _p, _p, _l, _l, _l, _p, _l, _p]),
     "vita_decode_attn_partial_kv8": (_i, [_p, _l, _l, _p, _p, _l, _l, _p, _p, _l, _l, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p]),

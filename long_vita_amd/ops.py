@@ -1467,6 +1467,77 @@ def prefix_batch_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     return o
 
 
+def prefix_extend_segments(segments, n_tokens: int, tail_cap: int):
+    """The host check of a ragged pass's segment table: segments = one (first query row, count, tail0) per continuation row, as host
+    integers.  counts >= 0, first + count <= n_tokens, tail0 >= 0, tail0 + count <= tail_cap, and the query ranges of the rows with
+    count > 0 do not overlap.  Returns ([[first, count, tail0], ...], the largest count)."""
+    rows = [[int(v) for v in s] for s in segments]
+    if not 1 <= len(rows) <= BEAM_MAX or any(len(s) != 3 for s in rows):
+        raise ValueError(f"prefix_extend_attn: 1 .. {BEAM_MAX} segments (first query row, count, tail0)")
+    for first, count, tail0 in rows:
+        if count < 0 or first < 0 or tail0 < 0:
+            raise ValueError("prefix_extend_attn: first, count and tail0 of a segment must be >= 0")
+        if first + count > n_tokens:
+            raise ValueError(f"prefix_extend_attn: a segment reaches beyond the {n_tokens} query rows")
+        if tail0 + count > tail_cap:
+            raise ValueError(f"prefix_extend_attn: tail0 + count exceeds the tail capacity {tail_cap}")
+    end = 0
+    for first, count, _ in sorted(s for s in rows if s[1] > 0):
+        if first < end:
+            raise ValueError("prefix_extend_attn: the segments' query rows overlap")
+        end = first + count
+    return rows, max(s[1] for s in rows)
+
+
+def prefix_extend_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, prefix_len: int, tail_ptrs: torch.Tensor,
+                       tail_row_stride: int, tail_group_stride: int, tail_cap: int, segments, softmax_scale: Optional[float] = None,
+                       out: Optional[torch.Tensor] = None, table: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The contexts [n, Hq, D] of n query rows that are the NEW tokens of B <= 8 continuations of one prefilled prompt, all in one
+    pass.  q [n, Hkv, G, D] — a view into the mixed QKV rows; k_cache / v_cache [cap, Hkv, D] views whose rows [0, prefix_len) every
+    query sees (never written); tail_ptrs / strides / tail_cap: the rows' tails as for prefix_batch_attn.  segments: B host triples
+    (first query row, count, tail0) — query i of segment b also sees rows [0, tail0 + i] of row b's tail, which already holds the new
+    tokens' rotated K / V at [tail0, tail0 + count); count 0 = an idle row (its tail is not read); a query row no segment names
+    gets the prefix alone.  The triples are checked here (prefix_extend_segments).  table: the same triples as int32 [B, 3] on the
+    device, when the caller uploaded them already (one upload per pass, not per layer); None: uploaded here."""
+    if q.dim() != 4 or k_cache.dim() != 3:
+        raise ValueError("prefix_extend_attn: q [n, Hkv, G, D], caches [cap, Hkv, D]")
+    n, Hkv, G, D = q.shape
+    if k_cache.shape[1:] != (Hkv, D) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
+        raise ValueError("prefix_extend_attn: k / v cache views must be [cap, Hkv, D] with the same strides")
+    if q.stride(3) != 1 or k_cache.stride(2) != 1:
+        raise ValueError("head_dim must be contiguous")
+    prefix_len, tail_cap = int(prefix_len), int(tail_cap)
+    if prefix_len > k_cache.shape[0]:
+        raise ValueError("prefix_len exceeds the cache rows")
+    if tail_cap < 0:
+        raise ValueError("prefix_extend_attn: tail_cap >= 0")
+    rows, max_count = prefix_extend_segments(segments, n, tail_cap)
+    B = len(rows)
+    if tail_ptrs.dtype != torch.int64 or tuple(tail_ptrs.shape) != (B, 2) or not tail_ptrs.is_contiguous():
+        raise ValueError(f"prefix_extend_attn: tail_ptrs must be contiguous int64 [{B}, 2] (K base, V base per row)")
+    if table is None:
+        table = torch.tensor(rows, dtype=torch.int32).to(q.device)
+    elif table.dtype != torch.int32 or tuple(table.shape) != (B, 3) or not table.is_contiguous():
+        raise ValueError(f"prefix_extend_attn: table must be contiguous int32 [{B}, 3]")
+    Hq = Hkv * G
+    o = torch.empty((n, Hq, D), dtype=BF16, device=q.device) if out is None else out
+    if tuple(o.shape) != (n, Hq, D) or not o.is_contiguous():
+        raise ValueError("out must be contiguous [n, Hq, D]")
+    for t_, name in ((q, "q"), (tail_ptrs, "tail_ptrs"), (table, "table")):
+        _dev(t_, name)
+    h = _L.load()
+    nbytes = h.vita_prefix_extend_attn_workspace_bytes(n, Hq, prefix_len)
+    ws = _extend_workspace(max(nbytes, 16), q.device)
+    _L.check(h.vita_prefix_extend_attn_fwd(_dev(q, "q", BF16), q.stride(0), q.stride(1), q.stride(2), _dev(k_cache, "k_cache", BF16),
+                                           _dev(v_cache, "v_cache", BF16), k_cache.stride(0), k_cache.stride(1), prefix_len,
+                                           _dev(tail_ptrs, "tail_ptrs"), int(tail_row_stride), int(tail_group_stride), tail_cap,
+                                           _dev(table, "table"), B, n, max_count, Hq, Hkv, D,
+                                           float(softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(D)),
+                                           _dev(o, "out", BF16), _dev(ws, "workspace", torch.float32), nbytes, _stream()),
+             "vita_prefix_extend_attn_fwd")
+    return o
+
+
 def beam_candidates(logits: torch.Tensor, beam_scores: torch.Tensor, n_out: int, temperature: float = 1.0, cols: Optional[int] = None):
     """The n_out best continuations of bf16 logits [rows, ld] (cols valid columns): score = log_softmax(logits / temperature) +
     beam_scores[row] in fp32.  Returns (flat index row * cols + col int64 [n_out], score fp32 [n_out]) on the device, by descending
