@@ -270,6 +270,10 @@ int vita_gemm_skinny_bf16(const void* A, int64_t lda, const void* W, int64_t ldw
  * o_group_stride likewise.
  * lse (fp32 [batch, n_q_heads, n_q_rows], natural log) may be NULL.
  * All tables are HOST pointers (<= 64 chunks); they are copied into kernel arguments.
+ * Alignment (anything else is VITA_ERR_UNSUPPORTED, refused before a launch): q / k / v 16-byte aligned with every stride a multiple
+ * of 8 elements (16-byte loads); o 8-byte aligned with every stride a multiple of 4 elements (8-byte stores); lse and q_seg_start
+ * 4-byte aligned.  An o that is also 16-byte aligned with strides of 8 elements takes the 64-row kernels where the geometry allows
+ * them; the others run on the general kernel.
  * ------------------------------------------------------------------------------------------- */
 typedef struct {
   const void* q; int64_t q_batch_stride, q_row_stride, q_head_stride, q_group_stride;

@@ -265,6 +265,12 @@ static int flash_attn_fwd_impl(const vita_attn_params* p, const int32_t* win_til
   for (int64_t s : strides)
     if (s & 7) return VITA_ERR_UNSUPPORTED;          // 16-byte vector loads
   if ((p->o_batch_stride & 3) || (p->o_row_stride & 3) || (p->o_head_stride & 3) || (p->o_group_stride & 3)) return VITA_ERR_UNSUPPORTED;
+  // every kernel reads q 16 bytes at a time (bf16x8 loads) and k / v in 16-byte LDS-DMA pieces, stores lse and reads the segment table as
+  // 4-byte words; the general kernel stores o 8 bytes at a time (the 64-row kernels 16: their _eligible() hands an output that is only
+  // 8-byte aligned to the general one).  Refused here, before anything is launched.
+  if (((uintptr_t)p->q | (uintptr_t)p->k | (uintptr_t)p->v) & 15) return VITA_ERR_UNSUPPORTED;
+  if ((uintptr_t)p->o & 7) return VITA_ERR_UNSUPPORTED;
+  if (((uintptr_t)p->lse | (uintptr_t)p->q_seg_start) & 3) return VITA_ERR_UNSUPPORTED;
 
   AttnArgs a;
   a.q = (const bf16_t*)p->q; a.q_bs = p->q_batch_stride; a.q_rs = p->q_row_stride; a.q_hs = p->q_head_stride;
