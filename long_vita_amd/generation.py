@@ -249,6 +249,66 @@ def generate_tokens_probs_and_return_on_first_stage(model, tokens, lengths, retu
             break
 
 
+def _prefill_alone(model, tokens_in, position_ids, max_sequence_length, kv_cache_dtype, external_inputs, logit_mask, reference_compat):
+    """One prompt tokens_in [1, n], whole, at batch 1: the batch-1 path on a ForwardStep / InferenceParams of its own, with its logit
+    mask, cache (capacity from max_sequence_length) and external_inputs.  Returns (the InferenceParams, the last row's logits [V])."""
+    from .inference_params import ForwardStep
+    n = tokens_in.shape[1]
+    forward_step = ForwardStep(model, 1, max_sequence_length, external_inputs=None)
+    ip = forward_step.inference_params
+    ip.kv_cache_dtype = kv_cache_dtype
+    ip.prefill_valid_tokens = n
+    ip.external_inputs = external_inputs or None
+    if logit_mask:
+        ip.logit_mask, _ = build_logit_mask(tokens_in, n, reference_compat)
+    logits = forward_step(tokens_in, position_ids[:, :n], None)
+    ip.logit_mask = None
+    return ip, (logits[0, -1, :] if logit_mask else logits[0, n - 1, :])
+
+
+def _step_rows(model, batch, tokens, position_ids, context_length, active):
+    """ONE step of the model for the rows of `batch` flagged active, fed tokens[:, context_length - 1] at position context_length - 1.
+    Returns the logits [B, V], a copy; an idle row's mean nothing."""
+    batch.step_rows(active)
+    logits = model(tokens[:, context_length - 1: context_length],
+                   position_ids[:, context_length - 1: context_length].expand(tokens.shape[0], 1), None, inference_params=batch)
+    return logits[:, -1, :].clone()
+
+
+def _step_rows_past_prompt(model, batch, tokens, position_ids, context_length, lens, done, stored):
+    """_step_rows for the unfinished rows past their prompt (lens[b] < context_length), zeros when there is none; a row AT the end of
+    its prompt (lens[b] == context_length) gets stored[b], the logits the pass over its prompt left."""
+    active = [lens[b] < context_length and not done[b] for b in range(len(lens))]
+    if any(active):
+        last_token_logits = _step_rows(model, batch, tokens, position_ids, context_length, active)
+    else:
+        last_token_logits = torch.zeros(len(lens), stored[0].shape[-1], dtype=stored[0].dtype, device=tokens.device)
+    for b in range(len(lens)):
+        if lens[b] == context_length:
+            last_token_logits[b] = stored[b]
+    return last_token_logits
+
+
+def _write_live_rows(tokens, last_token_logits, live, context_length, done, output_log_probs, token_selector, sampling, termination_id):
+    """What both multi-row loops do with the logits [B, V] of position context_length: the token of every live row (started and not
+    finished) is chosen and written, :217-219; output_log_probs, when kept, gets the live rows' log-probs and NaN for the others;
+    done[b] turns True, for good, when live row b chose termination_id (:239-246; None: no early termination)."""
+    live_t = torch.tensor(live, dtype=torch.bool, device=tokens.device)
+    if output_log_probs is not None:
+        output_log_probs[:, context_length - 1, :] = float("nan")
+    if any(live):
+        if token_selector is not None:
+            new_sample = token_selector(last_token_logits, context_length).view(-1)
+        else:
+            _, new_sample = _sample_strategy(last_token_logits, **sampling)
+        tokens[live_t, context_length] = new_sample[live_t]                                 # finished rows left alone
+        if output_log_probs is not None:
+            output_log_probs[live_t, context_length - 1, :] = torch.log_softmax(last_token_logits[live_t].float(), dim=1)
+        if termination_id is not None:
+            for b, hit in enumerate((new_sample == termination_id).tolist()):
+                done[b] = done[b] or (hit and live[b])
+
+
 def _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample, top_k, top_p, temperature,
                       use_eod_token_for_early_termination, external_inputs, use_kv_cache, logit_mask, termination_id,
                       reference_compat, token_selector, kv_cache_dtype):
@@ -270,7 +330,7 @@ def _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample
     the termination token and truncates afterwards, here those positions keep what the buffer held.  output_log_probs[b, p] is
     filled for p >= lengths[b] - 1 of a live row and is NaN at the other positions from lengths.min() - 1 on (the reference holds
     the log-probs of teacher-forced prompt positions there; this path does not compute them)."""
-    from .inference_params import BATCH_MAX, DecodeBatch, ForwardStep
+    from .inference_params import BATCH_MAX, DecodeBatch
     B, max_sequence_length = tokens.shape
     if B > BATCH_MAX:
         raise ValueError(f"the batched decode loop takes at most {BATCH_MAX} rows")
@@ -291,53 +351,21 @@ def _generate_batched(model, tokens, lengths, return_output_log_probs, do_sample
     position_ids = torch.arange(max_sequence_length, dtype=torch.long, device=dev)[None]
     rows, prefill_logits = [], []
     for b in range(B):                                     # every prompt alone, whole, at batch 1
-        forward_step = ForwardStep(model, 1, max_sequence_length, external_inputs=None)
-        ip = forward_step.inference_params
-        ip.kv_cache_dtype = kv_cache_dtype
-        ip.prefill_valid_tokens = lens[b]
-        ip.external_inputs = (external_inputs[b] or None) if external_inputs is not None else None
-        tokens_in = tokens[b: b + 1, : lens[b]]
-        if logit_mask:
-            ip.logit_mask, _ = build_logit_mask(tokens_in, lens[b], reference_compat)
-        logits = forward_step(tokens_in, position_ids[:, : lens[b]], None)
-        ip.logit_mask = None
-        prefill_logits.append(logits[0, -1, :] if logit_mask else logits[0, lens[b] - 1, :])
+        ip, logits = _prefill_alone(model, tokens[b: b + 1, : lens[b]], position_ids, max_sequence_length, kv_cache_dtype,
+                                    external_inputs[b] if external_inputs is not None else None, logit_mask, reference_compat)
         rows.append(ip)
+        prefill_logits.append(logits)
     batch = DecodeBatch(rows)
-    vocab = prefill_logits[0].shape[-1]
     output_log_probs = None
     if return_output_log_probs:
-        output_log_probs = torch.empty((B, max_sequence_length - 1, vocab), dtype=torch.float32, device=dev)
-    idle_logits = torch.zeros(B, vocab, dtype=prefill_logits[0].dtype, device=dev)
+        output_log_probs = torch.empty((B, max_sequence_length - 1, prefill_logits[0].shape[-1]), dtype=torch.float32, device=dev)
+    sampling = dict(do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature)
     done = [False] * B
     for context_length in range(min(lens), max_sequence_length):
-        active = [lens[b] < context_length and not done[b] for b in range(B)]
         live = [lens[b] <= context_length and not done[b] for b in range(B)]
-        if any(active):
-            batch.step_rows(active)
-            logits = model(tokens[:, context_length - 1: context_length],
-                           position_ids[:, context_length - 1: context_length].expand(B, 1), None, inference_params=batch)
-            last_token_logits = logits[:, -1, :].clone()
-        else:
-            last_token_logits = idle_logits.clone()
-        for b in range(B):
-            if lens[b] == context_length:
-                last_token_logits[b] = prefill_logits[b]
-        live_t = torch.tensor(live, dtype=torch.bool, device=dev)
-        if return_output_log_probs:
-            output_log_probs[:, context_length - 1, :] = float("nan")
-        if any(live):
-            if token_selector is not None:
-                new_sample = token_selector(last_token_logits, context_length).view(-1)
-            else:
-                _, new_sample = _sample_strategy(last_token_logits, do_sample=do_sample, top_k=top_k, top_p=top_p,
-                                                 temperature=temperature)
-            tokens[live_t, context_length] = new_sample[live_t]                             # :217-219, finished rows left alone
-            if return_output_log_probs:
-                output_log_probs[live_t, context_length - 1, :] = torch.log_softmax(last_token_logits[live_t].float(), dim=1)
-            if use_eod_token_for_early_termination and termination_id is not None:        # :239-246
-                for b, hit in enumerate((new_sample == termination_id).tolist()):
-                    done[b] = done[b] or (hit and live[b])
+        last_token_logits = _step_rows_past_prompt(model, batch, tokens, position_ids, context_length, lens, done, prefill_logits)
+        _write_live_rows(tokens, last_token_logits, live, context_length, done, output_log_probs, token_selector, sampling,
+                         termination_id if use_eod_token_for_early_termination else None)
         yield tokens[:, : context_length + 1], lengths, output_log_probs
         if all(done):
             break
@@ -369,7 +397,7 @@ def _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_ou
 
     Every refusal is raised before anything is launched: B outside 2 .. 8, P < 1, lengths[b] < P, prefixes that differ (ValueError),
     use_kv_cache=False (ValueError), CP or TP > 1, an FP8 cache (NotImplementedError)."""
-    from .inference_params import BATCH_MAX, BATCH_MIN, ForwardStep, SharedPrefixBatch
+    from .inference_params import BATCH_MAX, BATCH_MIN, SharedPrefixBatch
     if tokens.dim() != 2 or not BATCH_MIN <= tokens.shape[0] <= BATCH_MAX:
         raise ValueError(f"shared_prefix_len takes tokens [B, S] with B = {BATCH_MIN} .. {BATCH_MAX}")
     B, max_sequence_length = tokens.shape
@@ -395,24 +423,16 @@ def _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_ou
         raise ValueError(f"the rows' first {P} tokens differ: they are not one shared prefix")
     dev = tokens.device
     position_ids = torch.arange(max_sequence_length, dtype=torch.long, device=dev)[None]
-    forward_step = ForwardStep(model, 1, max_sequence_length, external_inputs=None)       # the prefix, once, at batch 1
-    ip = forward_step.inference_params
-    ip.kv_cache_dtype = kv_cache_dtype
-    ip.prefill_valid_tokens = P
-    ip.external_inputs = external_inputs or None
-    tokens_in = tokens[:1, :P]
-    if logit_mask:
-        ip.logit_mask, _ = build_logit_mask(tokens_in, P, reference_compat)
-    logits = forward_step(tokens_in, position_ids[:, :P], None)
-    ip.logit_mask = None
-    prefill_logits = logits[0, -1, :] if logit_mask else logits[0, P - 1, :]
+    ip, prefill_logits = _prefill_alone(model, tokens[:1, :P], position_ids, max_sequence_length, kv_cache_dtype, external_inputs,
+                                        logit_mask, reference_compat)                     # the prefix, once, at batch 1
     batch = SharedPrefixBatch(ip, B, max_sequence_length - P)
     vocab = prefill_logits.shape[-1]
     output_log_probs = None
     if return_output_log_probs:
         output_log_probs = torch.empty((B, max_sequence_length - 1, vocab), dtype=torch.float32, device=dev)
+    sampling = dict(do_sample=do_sample, top_k=top_k, top_p=top_p, temperature=temperature)
     done = [False] * B
-    pass_logits = None
+    pass_logits = prefill_logits[None, :].expand(B, vocab)   # a row without a suffix: the prefill's last row, as ever
     if prefill_suffixes and max(lens) > P:
         batch.extend_rows([n - P for n in lens])
         fed = [b for b in range(B) if lens[b] > P]
@@ -423,37 +443,11 @@ def _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_ou
         if context_length == P:
             last_token_logits = prefill_logits[None, :].expand(B, vocab).clone()
         elif prefill_suffixes:
-            active = [lens[b] < context_length and not done[b] for b in range(B)]
-            if any(active):
-                batch.step_rows(active)
-                logits = model(tokens[:, context_length - 1: context_length],
-                               position_ids[:, context_length - 1: context_length].expand(B, 1), None, inference_params=batch)
-                last_token_logits = logits[:, -1, :].clone()
-            else:
-                last_token_logits = torch.zeros(B, vocab, dtype=prefill_logits.dtype, device=dev)
-            for b in range(B):
-                if lens[b] == context_length:
-                    last_token_logits[b] = pass_logits[b]
+            last_token_logits = _step_rows_past_prompt(model, batch, tokens, position_ids, context_length, lens, done, pass_logits)
         else:
-            batch.step_rows([not d for d in done])
-            logits = model(tokens[:, context_length - 1: context_length],
-                           position_ids[:, context_length - 1: context_length].expand(B, 1), None, inference_params=batch)
-            last_token_logits = logits[:, -1, :].clone()
-        live_t = torch.tensor(live, dtype=torch.bool, device=dev)
-        if return_output_log_probs:
-            output_log_probs[:, context_length - 1, :] = float("nan")
-        if any(live):
-            if token_selector is not None:
-                new_sample = token_selector(last_token_logits, context_length).view(-1)
-            else:
-                _, new_sample = _sample_strategy(last_token_logits, do_sample=do_sample, top_k=top_k, top_p=top_p,
-                                                 temperature=temperature)
-            tokens[live_t, context_length] = new_sample[live_t]                             # :217-219, finished rows left alone
-            if return_output_log_probs:
-                output_log_probs[live_t, context_length - 1, :] = torch.log_softmax(last_token_logits[live_t].float(), dim=1)
-            if use_eod_token_for_early_termination and termination_id is not None:        # :239-246
-                for b, hit in enumerate((new_sample == termination_id).tolist()):
-                    done[b] = done[b] or (hit and live[b])
+            last_token_logits = _step_rows(model, batch, tokens, position_ids, context_length, [not d for d in done])
+        _write_live_rows(tokens, last_token_logits, live, context_length, done, output_log_probs, token_selector, sampling,
+                         termination_id if use_eod_token_for_early_termination else None)
         yield tokens[:, : context_length + 1], lengths, output_log_probs
         if all(done):
             break

@@ -130,8 +130,7 @@ class GPTVLModel:
         return self._w8
 
     def _rows_gemv(self, w8, li: int, x: torch.Tensor, name: str, epilogue: int, bias=None, gamma=None, xn=None, **kw):
-        """Linear `name` of layer li on the rows x [B <= 8, K] of a multi-row step (_beam_forward, _batch_token, _prefix_batch_token):
-        the one owner of their FP8 / bf16 choice.  w8 = self._w8_layers(), taken once per step.  None: ops.gemv_rows on the bf16
+        """Linear `name` of layer li on the rows x [B <= 8, K] of a multi-row step (_rows_token): the one owner of its FP8 / bf16 choice.  w8 = self._w8_layers(), taken once per step.  None: ops.gemv_rows on the bf16
         weight, the RMSNorm (gamma) folded into the kernel.  Else ops.rmsnorm into the workspace rows xn, then ops.gemv_rows_w8 on
         the codes and scales the batch-1 step reads: the arithmetic of the unfused batch-1 FP8 step (_decode_token), bit for bit."""
         if w8 is None:
@@ -696,21 +695,82 @@ class GPTVLModel:
         ip.decode_steps += t
         ip.consumed_tokens = t
         rows = h if logit_mask is None else ops.row_gather(h, ops.mask_to_index(logit_mask.reshape(-1)))
-        rows = ops.rmsnorm(rows, self.p["final_ln"], c.eps)
+        logits = self._head(ops.rmsnorm(rows, self.p["final_ln"], c.eps), check_nan=True)
+        return logits.transpose(0, 1).contiguous()
+
+    def _head(self, rows: torch.Tensor, check_nan: bool = False) -> torch.Tensor:
+        """Final-normed rows [n, hidden] -> logits [n, 1, vocab]: the bf16 head (<= 16 rows: vita_gemm_skinny_bf16) and the logit
+        post-processing of the token step (a no-op at 0 / 0).  check_nan: the prefill's test (gpt_vl_model.py:393-396), a host read."""
+        c = self.cfg
         logits, _ = self.output_layer(rows.view(rows.shape[0], 1, -1), weight=None, logit_mask=None)
         ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)
-        if bool(torch.isnan(logits.float().sum())):                                       # as the prefill (gpt_vl_model.py:393-396)
+        if check_nan and bool(torch.isnan(logits.float().sum())):
             raise ValueError("found NaN in local forward logits calculation")
-        return logits.transpose(0, 1).contiguous()
+        return logits
+
+    def _rows_workspace(self, B: int, device):
+        """The activations of a multi-row step of B rows, shared by the three kinds of step (one runs at a time)."""
+        ws = self._ws.get(("rows", B))
+        if ws is None:
+            c = self.cfg
+            e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=device)  # noqa: E731
+            ws = self._ws[("rows", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn), "x": e(B, c.hidden)}
+        return ws
+
+    def _rows_token(self, tokens: torch.Tensor, position: torch.Tensor, append, attend, advance, check_bounds: bool = False) -> torch.Tensor:
+        """One token for each of B <= 8 rows through the layers (_decode_token for B rows): tokens [B] and positions [B] int64 ->
+        final-normed hidden [B, hidden].  The one layer loop of the beam, batched and shared-prefix steps (_beam_forward,
+        _batch_token, _prefix_batch_token), which differ in where a row's K / V live and supply exactly that:
+          append(li, qkv, cos, sin)   rotates the mixed rows qkv [B, qkv_out] of layer li in place and stores their K / V;
+          attend(li, q, out)          the contexts of q [B, kv_groups, qpg, d], a view into those rows, into out [B, heads, d];
+          advance()                   moves the path's counters on, behind the last layer's launches.
+        Everything else is here.  The weights are streamed once for all B rows: RMSNorm folded into the multi-row GEMVs, then the
+        path's append and attention, o-projection, fc1 + SwiGLU, fc2.  With decode_weight_dtype = "fp8_e4m3" the four linears read
+        the FP8 copies the batch-1 step reads (_rows_gemv: ops.rmsnorm once per norm, then ops.gemv_rows_w8); the head stays bf16.
+        Row b's hidden state has the bits of the unfused batch-1 token step on row b's cache, under either weight format.  CP = 1
+        and TP = 1; the fused C layer entries and the captured token step stay batch 1.  check_bounds: the embedding gather tests
+        the token ids, a host read; without it nothing is read back to the host."""
+        c = self.cfg
+        B = tokens.shape[0]
+        ws = self._rows_workspace(B, tokens.device)
+        w8 = self._w8_layers()                                  # FP8 weights: ops.gemv_rows_w8 in place of ops.gemv_rows (_rows_gemv)
+        h = ops.row_gather(self.p["embed"], tokens, check_bounds=check_bounds)            # [B, hidden]
+        cos, sin = ops.rope_table(position.contiguous(), self.rotary_pos_emb.inv_freq)
+        for li, lp in enumerate(self.p["layers"]):
+            qkv = self._rows_gemv(w8, li, h, "qkv_w", ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], xn=ws["x"])
+            append(li, qkv, cos, sin)
+            attend(li, qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)[:, :, : c.qpg], ws["ctx"])
+            self._rows_gemv(w8, li, ws["ctx"].view(B, -1), "o_w", ops.EPI_RESIDUAL, residual=h, out=h)
+            act = self._rows_gemv(w8, li, h, "fc1_w", ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], xn=ws["x"])
+            self._rows_gemv(w8, li, act, "fc2_w", ops.EPI_RESIDUAL, residual=h, out=h)
+        advance()
+        return ops.rmsnorm(h, self.p["final_ln"], c.eps)
+
+    def _rows_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], batch, what: str, token_step) -> torch.Tensor:
+        """One step of `batch` (a DecodeBatch or a SharedPrefixBatch) as the model's forward: tokens [B, 1] at positions [B, 1]
+        (None: batch.positions()) -> logits [B, 1, vocab].  The rows batch.step_rows marked active advance; an idle row's cache is
+        neither written nor read and its logits mean nothing.  Without a prepared step every row is active."""
+        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
+            raise NotImplementedError(f"the {what} is built for CP = 1 and TP = 1")
+        B = len(batch)
+        if tuple(input_ids.shape) != (B, 1):
+            raise ValueError(f"the {what} takes tokens [{B}, 1]")
+        if position_ids is None:
+            position = torch.tensor(batch.positions(), dtype=torch.long, device=input_ids.device)
+        elif tuple(position_ids.shape) != (B, 1):
+            raise ValueError(f"the {what} takes positions [{B}, 1]")
+        else:
+            position = position_ids[:, 0].contiguous()
+        if batch.active is None:
+            batch.step_rows([True] * B)                          # raises before any launch when a cache or a tail is full
+        batch.consumed_tokens = 1
+        return self._head(token_step(input_ids[:, 0].contiguous(), position, batch)).contiguous()
 
     def _beam_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], ip) -> torch.Tensor:
         """One beam-search step (M/inference/text_generation/generation.py:330-345 with beam_size rows): tokens [B, 1], every row
-        at the same position, behind the prompt that was prefilled and cached ONCE (ip.begin_beams).  The weights and the prompt's
-        K / V are streamed once for all B rows: RMSNorm folded into the multi-row GEMVs, RoPE of the B rows, their K / V stored as
-        one contiguous block at tail step n_gen, ops.beam_attn over the shared prefix and each beam's own steps, then the head for
-        B rows.  decode_weight_dtype = "fp8_e4m3": the four linears read the FP8 copies (_rows_gemv: ops.rmsnorm once per norm, then
-        ops.gemv_rows_w8); the head stays bf16.  CP = 1 and TP = 1; the fused C layer entries and the captured token step stay
-        batch 1.  Returns [B, 1, vocab]."""
+        at the same position, behind the prompt that was prefilled and cached ONCE (ip.begin_beams).  _rows_token with the B rows'
+        K / V stored as one contiguous block at tail step n_gen and ops.beam_attn over the shared prefix and each beam's own steps.
+        Returns [B, 1, vocab]."""
         c = self.cfg
         if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1:
             raise NotImplementedError("the beam step is built for CP = 1 and TP = 1")
@@ -728,149 +788,76 @@ class GPTVLModel:
             position = position_ids.reshape(-1)[:1]
         ip._graph = None
         ip.consumed_tokens = 1
-        ws = self._ws.get(("beam", B))
-        if ws is None:
-            e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=input_ids.device)  # noqa: E731
-            ws = self._ws[("beam", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn),
-                                          "x": e(B, c.hidden)}
-        w8 = self._w8_layers()                                  # FP8 weights: ops.gemv_rows_w8 in place of ops.gemv_rows (_rows_gemv)
-        h = ops.row_gather(self.p["embed"], input_ids[:, 0].contiguous())                 # [B, hidden]
-        cos, sin = ops.rope_table(position.expand(B).contiguous(), self.rotary_pos_emb.inv_freq)
-        L = ip.beam_prefix_len
-        for li, lp in enumerate(self.p["layers"]):
-            kv, tail = ip.key_value_memory_dict[li + 1], ip.beam_tails[li + 1]
-            qkv = self._rows_gemv(w8, li, h, "qkv_w", ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], xn=ws["x"])
+
+        def append(li, qkv, cos, sin):
+            tail = ip.beam_tails[li + 1]
             ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, None, 1)
             m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
             tail[0, step].copy_(m4[:, :, c.qpg])
             tail[1, step].copy_(m4[:, :, c.qpg + 1])
-            ctx = ops.beam_attn(m4[:, :, : c.qpg], kv[0], kv[1], L, tail[0], tail[1], ip.beam_ancestry, step + 1, out=ws["ctx"])
-            self._rows_gemv(w8, li, ctx.view(B, -1), "o_w", ops.EPI_RESIDUAL, residual=h, out=h)
-            act = self._rows_gemv(w8, li, h, "fc1_w", ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], xn=ws["x"])
-            self._rows_gemv(w8, li, act, "fc2_w", ops.EPI_RESIDUAL, residual=h, out=h)
-        ip.beam_n_gen = step + 1
-        ip.decode_steps += 1
-        rows = ops.rmsnorm(h, self.p["final_ln"], c.eps)
-        logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)   # <= 16 rows: vita_gemm_skinny_bf16
-        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)   # as the token step (no-op at 0 / 0)
-        return logits.contiguous()                                                        # [B, 1, vocab]: the rows are the beams
+
+        def attend(li, q, out):
+            kv, tail = ip.key_value_memory_dict[li + 1], ip.beam_tails[li + 1]
+            ops.beam_attn(q, kv[0], kv[1], ip.beam_prefix_len, tail[0], tail[1], ip.beam_ancestry, step + 1, out=out)
+
+        def advance():
+            ip.beam_n_gen = step + 1
+            ip.decode_steps += 1
+
+        rows = self._rows_token(input_ids[:, 0].contiguous(), position.expand(B), append, attend, advance, check_bounds=True)
+        return self._head(rows).contiguous()                                               # [B, 1, vocab]: the rows are the beams
 
     def _batch_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], batch: DecodeBatch) -> torch.Tensor:
         """One token for each of B = 2 .. 8 requests in ONE step (the loop of M/inference/text_generation/generation.py:33-280 at
-        batch_size > 1): tokens [B, 1] at positions [B, 1], every request on the cache its own batch-1 prefill allocated
-        (inference_params.DecodeBatch).  The weights are streamed once for all B rows: RMSNorm folded into the multi-row GEMVs, RoPE
-        of the B rows at their own positions with each row's K / V appended to its own cache (ops.rope_append_rows), the split
-        attention of every row over its own length (ops.decode_attn_batch), then the head for B rows.  The rows DecodeBatch.step_rows
-        marked active advance; an idle row's cache is neither written nor read and its logits mean nothing.  Without a prepared
-        step every row is active.  Nothing is read back to the host.  CP = 1 and TP = 1; with decode_weight_dtype = "fp8_e4m3" the
-        four linears read the FP8 copies the batch-1 step reads (_rows_gemv), the head stays bf16; the fused C layer entries and the
-        captured token step stay batch 1.  Returns [B, 1, vocab]; row b's hidden state has the bits of the unfused batch-1 token
-        step on request b, under either weight format."""
-        c = self.cfg
-        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
-            raise NotImplementedError("the batched decode step is built for CP = 1 and TP = 1")
-        B = len(batch)
-        if tuple(input_ids.shape) != (B, 1):
-            raise ValueError(f"the batched decode step takes tokens [{B}, 1]")
-        if position_ids is None:
-            position = torch.tensor([ip.sequence_len_offset for ip in batch.rows], dtype=torch.long, device=input_ids.device)
-        elif tuple(position_ids.shape) != (B, 1):
-            raise ValueError(f"the batched decode step takes positions [{B}, 1]")
-        else:
-            position = position_ids[:, 0].contiguous()
-        if batch.active is None:
-            batch.step_rows([True] * B)                          # raises before any launch when a cache is full
-        batch.consumed_tokens = 1
-        rows = self._batch_token(input_ids[:, 0].contiguous(), position, batch)
-        logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)   # <= 16 rows: vita_gemm_skinny_bf16
-        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)   # as the token step (no-op at 0 / 0)
-        return logits.contiguous()                                                        # [B, 1, vocab]
+        batch_size > 1), every request on the cache its own batch-1 prefill allocated (inference_params.DecodeBatch): _rows_forward
+        on _batch_token.  Returns [B, 1, vocab]."""
+        return self._rows_forward(input_ids, position_ids, batch, "batched decode step", self._batch_token)
 
     def _batch_token(self, tokens: torch.Tensor, position: torch.Tensor, batch: DecodeBatch) -> torch.Tensor:
-        """The prepared step of `batch` through the layers: tokens [B] and positions [B] int64 -> final-normed hidden [B, hidden]
-        (_decode_token for B rows with a cache each)."""
+        """The prepared step of `batch` through the layers (_rows_token): each row's K / V appended to its own cache
+        (ops.rope_append_rows), the split attention of every row over its own length (ops.decode_attn_batch)."""
         c = self.cfg
         B = len(batch)
-        ws = self._ws.get(("batch", B))
-        if ws is None:
-            e = lambda *shape, dt=torch.bfloat16: torch.empty(*shape, dtype=dt, device=tokens.device)  # noqa: E731
-            n, H, D = ops.DECODE_MAX_SPLITS, c.heads, c.head_dim
-            ws = self._ws[("batch", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn),
-                                           "x": e(B, c.hidden),
-                                           "parts": (e(B, n, H, dt=torch.float32), e(B, n, H, dt=torch.float32),
-                                                     e(B, n, H, D, dt=torch.float32))}
-        w8 = self._w8_layers()                                  # FP8 weights: ops.gemv_rows_w8 in place of ops.gemv_rows (_rows_gemv)
-        h = ops.row_gather(self.p["embed"], tokens, check_bounds=False)                   # [B, hidden]
-        cos, sin = ops.rope_table(position, self.rotary_pos_emb.inv_freq)
-        for li, lp in enumerate(self.p["layers"]):
-            ptrs = batch.kv_ptrs[li]
-            qkv = self._rows_gemv(w8, li, h, "qkv_w", ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], xn=ws["x"])
-            ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs, batch.kv_row_stride, batch.kv_group_stride,
+        parts = self._ws.get(("parts", B))                      # the split attention's partials: this path's alone
+        if parts is None:
+            f32 = lambda *shape: torch.empty(B, ops.DECODE_MAX_SPLITS, c.heads, *shape, dtype=torch.float32, device=tokens.device)  # noqa: E731
+            parts = self._ws[("parts", B)] = (f32(), f32(), f32(c.head_dim))
+        ptrs = batch.kv_ptrs.unbind(0)
+
+        def append(li, qkv, cos, sin):
+            ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs[li], batch.kv_row_stride, batch.kv_group_stride,
                                  batch.append_rows, batch.caps)
-            m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
-            ctx = ops.decode_attn_batch(m4[:, :, : c.qpg], ptrs, batch.kv_row_stride, batch.kv_group_stride, batch.lens, batch.caps,
-                                        batch.max_len, out=ws["ctx"], parts=ws["parts"])
-            self._rows_gemv(w8, li, ctx.view(B, -1), "o_w", ops.EPI_RESIDUAL, residual=h, out=h)
-            act = self._rows_gemv(w8, li, h, "fc1_w", ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], xn=ws["x"])
-            self._rows_gemv(w8, li, act, "fc2_w", ops.EPI_RESIDUAL, residual=h, out=h)
-        batch.advance()
-        return ops.rmsnorm(h, self.p["final_ln"], c.eps)
+
+        def attend(li, q, out):
+            ops.decode_attn_batch(q, ptrs[li], batch.kv_row_stride, batch.kv_group_stride, batch.lens, batch.caps, batch.max_len,
+                                  out=out, parts=parts)
+
+        return self._rows_token(tokens, position, append, attend, batch.advance)
 
     def _prefix_batch_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], batch: SharedPrefixBatch) -> torch.Tensor:
         """One token for each of B = 2 .. 8 continuations of ONE prefilled prompt in ONE step (the loop of
-        M/inference/text_generation/generation.py:33-280 at batch_size > 1, the rows sharing their first tokens): tokens [B, 1] at
-        positions [B, 1] behind the prefix that was prefilled and cached once (inference_params.SharedPrefixBatch).  _batch_forward
-        with the rows' K / V appended to their own tails and ops.prefix_batch_attn over the shared prefix — read once per kv group for
-        all rows — and each row's tail.  The rows SharedPrefixBatch.step_rows marked active advance; an idle row's tail is neither
-        written nor read and its logits mean nothing.  Without a prepared step every row is active.  Nothing is read back to the
-        host.  CP = 1 and TP = 1; with decode_weight_dtype = "fp8_e4m3" the four linears read the FP8 copies (_rows_gemv), the head
-        stays bf16.  Returns [B, 1, vocab]."""
-        c = self.cfg
-        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
-            raise NotImplementedError("the shared-prefix decode step is built for CP = 1 and TP = 1")
-        B = len(batch)
-        if tuple(input_ids.shape) != (B, 1):
-            raise ValueError(f"the shared-prefix decode step takes tokens [{B}, 1]")
-        if position_ids is None:
-            position = torch.tensor(batch.positions(), dtype=torch.long, device=input_ids.device)
-        elif tuple(position_ids.shape) != (B, 1):
-            raise ValueError(f"the shared-prefix decode step takes positions [{B}, 1]")
-        else:
-            position = position_ids[:, 0].contiguous()
-        if batch.active is None:
-            batch.step_rows([True] * B)                          # raises before any launch when a tail is full
-        batch.consumed_tokens = 1
-        rows = self._prefix_batch_token(input_ids[:, 0].contiguous(), position, batch)
-        logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)   # <= 16 rows: vita_gemm_skinny_bf16
-        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)   # as the token step (no-op at 0 / 0)
-        return logits.contiguous()                                                        # [B, 1, vocab]
+        M/inference/text_generation/generation.py:33-280 at batch_size > 1, the rows sharing their first tokens), behind the prefix
+        that was prefilled and cached once (inference_params.SharedPrefixBatch): _rows_forward on _prefix_batch_token.  Returns
+        [B, 1, vocab]."""
+        return self._rows_forward(input_ids, position_ids, batch, "shared-prefix decode step", self._prefix_batch_token)
 
     def _prefix_batch_token(self, tokens: torch.Tensor, position: torch.Tensor, batch: SharedPrefixBatch) -> torch.Tensor:
-        """The prepared step of `batch` through the layers: tokens [B] and positions [B] int64 -> final-normed hidden [B, hidden]
-        (_batch_token on one shared prefix and a tail per row)."""
+        """The prepared step of `batch` through the layers (_rows_token): each row's K / V appended to its own tail
+        (ops.rope_append_rows), ops.prefix_batch_attn over the shared prefix — read once per kv group for all rows — and each row's
+        tail."""
         c = self.cfg
-        B = len(batch)
-        ws = self._ws.get(("prefix_batch", B))
-        if ws is None:
-            e = lambda *shape: torch.empty(*shape, dtype=torch.bfloat16, device=tokens.device)  # noqa: E731
-            ws = self._ws[("prefix_batch", B)] = {"qkv": e(B, c.qkv_out), "ctx": e(B, c.heads, c.head_dim), "act": e(B, c.ffn),
-                                                  "x": e(B, c.hidden)}
-        w8 = self._w8_layers()                                  # FP8 weights: ops.gemv_rows_w8 in place of ops.gemv_rows (_rows_gemv)
-        h = ops.row_gather(self.p["embed"], tokens, check_bounds=False)                   # [B, hidden]
-        cos, sin = ops.rope_table(position, self.rotary_pos_emb.inv_freq)
-        for li, lp in enumerate(self.p["layers"]):
-            kv, ptrs = batch.prefix.key_value_memory_dict[li + 1], batch.tail_ptrs[li]
-            qkv = self._rows_gemv(w8, li, h, "qkv_w", ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"], gamma=lp["ln1"], xn=ws["x"])
-            ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs, batch.tail_row_stride, batch.tail_group_stride,
+        ptrs = batch.tail_ptrs.unbind(0)
+
+        def append(li, qkv, cos, sin):
+            ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs[li], batch.tail_row_stride, batch.tail_group_stride,
                                  batch.append_rows, batch.caps)
-            m4 = qkv.view(B, c.kv_groups, c.qpg + 2, c.head_dim)
-            ctx = ops.prefix_batch_attn(m4[:, :, : c.qpg], kv[0], kv[1], batch.prefix_len, ptrs, batch.tail_row_stride,
-                                        batch.tail_group_stride, batch.lens, batch.tail_cap, out=ws["ctx"])
-            self._rows_gemv(w8, li, ctx.view(B, -1), "o_w", ops.EPI_RESIDUAL, residual=h, out=h)
-            act = self._rows_gemv(w8, li, h, "fc1_w", ops.EPI_SWIGLU, out=ws["act"], gamma=lp["ln2"], xn=ws["x"])
-            self._rows_gemv(w8, li, act, "fc2_w", ops.EPI_RESIDUAL, residual=h, out=h)
-        batch.advance()
-        return ops.rmsnorm(h, self.p["final_ln"], c.eps)
+
+        def attend(li, q, out):
+            kv = batch.prefix.key_value_memory_dict[li + 1]
+            ops.prefix_batch_attn(q, kv[0], kv[1], batch.prefix_len, ptrs[li], batch.tail_row_stride, batch.tail_group_stride,
+                                  batch.lens, batch.tail_cap, out=out)
+
+        return self._rows_token(tokens, position, append, attend, batch.advance)
 
     def _prefix_extend_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], batch: SharedPrefixBatch) -> torch.Tensor:
         """The rows' own prompt tokens behind the shared prefix in ONE pass (what the reference's loop teacher-forces one token per
@@ -884,7 +871,7 @@ class GPTVLModel:
         if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
             raise NotImplementedError("the shared-prefix decode step is built for CP = 1 and TP = 1")
         segs = batch.pass_segments
-        B, n = len(batch), sum(s[1] for s in segs)
+        n = sum(s[1] for s in segs)
         if tuple(input_ids.shape) != (1, n):
             raise ValueError(f"the prepared pass takes tokens [1, {n}]: the rows' new tokens in row order")
         dev = input_ids.device
@@ -925,8 +912,4 @@ class GPTVLModel:
                 ops.gemm(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
         batch.advance()
         rows = ops.rmsnorm(ops.row_gather(h, last), self.p["final_ln"], c.eps)
-        logits, _ = self.output_layer(rows.view(B, 1, -1), weight=None, logit_mask=None)
-        ops.logit_postprocess_(logits, c.output_multiplier_scale, c.output_logit_softcapping)
-        if bool(torch.isnan(logits.float().sum())):                                       # as the extend (gpt_vl_model.py:393-396)
-            raise ValueError("found NaN in local forward logits calculation")
-        return logits.contiguous()                                                        # [B, 1, vocab]
+        return self._head(rows, check_nan=True).contiguous()                              # [B, 1, vocab]

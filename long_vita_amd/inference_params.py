@@ -135,17 +135,55 @@ class InferenceParams:
 BATCH_MIN, BATCH_MAX = 2, 8              # rows of one batched decode step (what vita_gemv_rows_bf16 takes: ops.BEAM_MAX)
 
 
-class DecodeBatch:
+class _RowSteps:
+    """The host mirror of the multi-row steps, behind DecodeBatch and SharedPrefixBatch.  host_lens[b]: the rows stored for row b.
+    step_rows(active) prepares a step: an active row appends at its current length and attends to length + 1, an inactive one gets
+    append = -1 and len = 0 (its rows are neither written nor read).  lens / append_rows (int32, device) are ONE upload (_step) from
+    the mirror; nothing is read back.  advance() — called by the model behind the step's launches — moves the mirror.  The owner
+    sets self.device first and names each row's capacity and what a full row raises."""
+
+    def _begin_rows(self, host_lens, row_caps, full: str):
+        self.host_lens, self._row_caps, self._full = host_lens, row_caps, full
+        self._step = torch.zeros(2, len(host_lens), dtype=torch.int32, device=self.device)   # one upload per step: lens, append_rows
+        self.lens, self.append_rows = self._step[0], self._step[1]
+        self.active = None                   # the rows of the prepared step; None: no step is prepared
+        self.max_len = 0                     # the longest length a row of the prepared step attends to
+
+    def __len__(self):
+        return len(self.host_lens)
+
+    def step_rows(self, active):
+        active = [bool(a) for a in active]
+        if len(active) != len(self):
+            raise ValueError(f"step_rows: {len(self)} flags expected")
+        for b, a in enumerate(active):
+            if a and self.host_lens[b] + 1 > self._row_caps[b]:
+                raise RuntimeError(self._full)
+        lens = [self.host_lens[b] + 1 if a else 0 for b, a in enumerate(active)]
+        rows = [self.host_lens[b] if a else -1 for b, a in enumerate(active)]
+        self._step.copy_(torch.tensor([lens, rows], dtype=torch.int32))                 # host -> device; nothing is read back
+        self.max_len = max(lens)
+        self.active = active
+        return self.max_len
+
+    def advance(self):
+        """One more row stored for every active row; returns those rows."""
+        moved = [b for b, a in enumerate(self.active or ()) if a]
+        for b in moved:
+            self.host_lens[b] += 1
+        self.active = None
+        return moved
+
+
+class DecodeBatch(_RowSteps):
     """2 .. 8 prefilled batch-1 requests that advance one token each in ONE step of the model (GPTVLModel._batch_forward; the loop of
     M/inference/text_generation/generation.py:33-280 at batch_size > 1; CP = 1, TP = 1).  Every request keeps the bf16 cache its own
     prefill allocated, whatever its capacity: the kernels reach the caches through kv_ptrs [layers, B, 2] (int64 on the device: K
     base and V base per layer and row, built once) and caps [B]; the row and group strides are common.  No K / V is copied, so a
     table can be rebuilt when requests join or leave.
 
-    step_rows(active) prepares a step: an active row appends at its current length and attends to length + 1, an inactive one gets
-    append = -1 and len = 0 (its cache is neither written nor read).  lens / append_rows (int32, device) are uploaded from the host
-    mirror; nothing is read back.  advance() — called by the model behind the step's launches — moves the mirror and every active
-    row's local_len / decode_steps / sequence_len_offset, so a row's InferenceParams can go on alone at batch 1.
+    step_rows(active) / advance() are _RowSteps' on the caches' own lengths and capacities; advance() also moves every active row's
+    local_len / decode_steps / sequence_len_offset, so a row's InferenceParams can go on alone at batch 1.
     consumed_tokens / sequence_len_offset are what ForwardStep reads and writes."""
 
     def __init__(self, rows):
@@ -186,45 +224,25 @@ class DecodeBatch:
         table = [[[ip.key_value_memory_dict[ln][0].data_ptr(), ip.key_value_memory_dict[ln][1].data_ptr()] for ip in rows]
                  for ln in self.layer_numbers]
         self.kv_ptrs = torch.tensor(table, dtype=torch.int64).to(self.device)           # [layers, B, 2]
-        self.host_lens = [int(ip.local_len) for ip in rows]
-        self._step = torch.zeros(2, len(rows), dtype=torch.int32, device=self.device)   # one upload per step: lens, append_rows
-        self.lens, self.append_rows = self._step[0], self._step[1]
-        self.max_len = 0
-        self.active = None                   # the rows of the prepared step; None: no step is prepared
+        self._begin_rows([int(ip.local_len) for ip in rows], self.caps_host, "KV cache shard is full (max_sequence_length reached)")
         self.consumed_tokens = None
         self.sequence_len_offset = 0
         self.use_kv_cache = True
 
-    def __len__(self):
-        return len(self.rows)
-
-    def step_rows(self, active):
-        active = [bool(a) for a in active]
-        if len(active) != len(self.rows):
-            raise ValueError(f"step_rows: {len(self.rows)} flags expected")
-        for b, a in enumerate(active):
-            if a and self.host_lens[b] + 1 > self.caps_host[b]:
-                raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
-        lens = [self.host_lens[b] + 1 if a else 0 for b, a in enumerate(active)]
-        rows = [self.host_lens[b] if a else -1 for b, a in enumerate(active)]
-        self._step.copy_(torch.tensor([lens, rows], dtype=torch.int32))                 # host -> device; nothing is read back
-        self.max_len = max(lens)
-        self.active = active
-        return self.max_len
+    def positions(self):
+        """The position of every row's next token."""
+        return [ip.sequence_len_offset for ip in self.rows]
 
     def advance(self):
-        for b, a in enumerate(self.active or ()):
-            if a:
-                ip = self.rows[b]
-                self.host_lens[b] += 1
-                ip.local_len = self.host_lens[b]
-                ip.decode_steps += 1
-                ip.sequence_len_offset += 1
-                ip._graph = None             # a captured token step holds row counters of its own
-        self.active = None
+        for b in super().advance():
+            ip = self.rows[b]
+            ip.local_len = self.host_lens[b]
+            ip.decode_steps += 1
+            ip.sequence_len_offset += 1
+            ip._graph = None                 # a captured token step holds row counters of its own
 
 
-class SharedPrefixBatch:
+class SharedPrefixBatch(_RowSteps):
     """2 .. 8 continuations of ONE prefilled batch-1 request that advance one token each in ONE step of the model
     (GPTVLModel._prefix_batch_forward; the loop of M/inference/text_generation/generation.py:33-280 at batch_size > 1 for rows that
     share their first tokens; CP = 1, TP = 1, bf16 cache).  The prefix is `ip`'s own cache, rows [0, ip.local_len): read by every
@@ -232,10 +250,8 @@ class SharedPrefixBatch:
     (one allocation); the kernels reach the tails through tail_ptrs [layers, n_rows, 2] (int64 on the device: K base and V base,
     built once) with caps [n_rows] = tail_cap, the table and capacities ops.rope_append_rows takes.
 
-    step_rows(active) / advance() keep DecodeBatch's contract: an active row appends at its tail length and attends to the prefix
-    and tail length + 1 rows, an inactive one gets append = -1 and len = 0 (its tail is neither written nor read).  lens /
-    append_rows (int32, device) are one upload from the host mirror host_lens; nothing is read back.  Row b's next token sits at
-    position prefix_len + host_lens[b].
+    step_rows(active) / advance() are _RowSteps' on the tails: an active row appends at its tail length and attends to the prefix
+    and tail length + 1 rows.  Row b's next token sits at position prefix_len + host_lens[b].
 
     extend_rows(counts) prepares a ragged PASS instead (GPTVLModel._prefix_extend_forward): counts[b] >= 0 new tokens of row b, fed
     concatenated in row order, so row b's first query row is sum(counts[:b]).  segments (int32 [n_rows, 3] on the device: first
@@ -276,18 +292,12 @@ class SharedPrefixBatch:
                  for i in range(len(self.layer_numbers))]
         self.tail_ptrs = torch.tensor(table, dtype=torch.int64).to(self.device)            # [layers, n_rows, 2]
         self.caps = torch.full((n_rows,), tail_cap, dtype=torch.int32).to(self.device)
-        self.host_lens = [0] * n_rows                    # tail rows stored per row
-        self._step = torch.zeros(2, n_rows, dtype=torch.int32, device=self.device)      # one upload per step: lens, append_rows
-        self.lens, self.append_rows = self._step[0], self._step[1]
-        self.active = None                   # the rows of the prepared step; None: no step is prepared
+        self._begin_rows([0] * n_rows, [tail_cap] * n_rows, "the rows' tail cache is full (max_sequence_length reached)")
         self.segments = torch.zeros(n_rows, 3, dtype=torch.int32, device=self.device)   # one upload per pass
         self.pass_segments = None            # [[first, count, tail0]] of the prepared pass; None: no pass is prepared
         self.consumed_tokens = None
         self.sequence_len_offset = ip.sequence_len_offset
         self.use_kv_cache = True
-
-    def __len__(self):
-        return self.n_rows
 
     def positions(self):
         """The position of every row's next token."""
@@ -296,17 +306,7 @@ class SharedPrefixBatch:
     def step_rows(self, active):
         if self.pass_segments is not None:
             raise ValueError("step_rows: a pass is prepared (extend_rows) and has not run")
-        active = [bool(a) for a in active]
-        if len(active) != self.n_rows:
-            raise ValueError(f"step_rows: {self.n_rows} flags expected")
-        for b, a in enumerate(active):
-            if a and self.host_lens[b] + 1 > self.tail_cap:
-                raise RuntimeError("the rows' tail cache is full (max_sequence_length reached)")
-        lens = [self.host_lens[b] + 1 if a else 0 for b, a in enumerate(active)]
-        rows = [self.host_lens[b] if a else -1 for b, a in enumerate(active)]
-        self._step.copy_(torch.tensor([lens, rows], dtype=torch.int32))                 # host -> device; nothing is read back
-        self.active = active
-        return max(lens)
+        return super().step_rows(active)
 
     def extend_rows(self, counts):
         """Prepare a pass of counts[b] >= 0 new tokens per row; returns their sum (the query rows of the pass)."""
@@ -333,10 +333,7 @@ class SharedPrefixBatch:
             for b, (_, n, _) in enumerate(self.pass_segments):
                 self.host_lens[b] += n
             self.pass_segments = None
-        for b, a in enumerate(self.active or ()):
-            if a:
-                self.host_lens[b] += 1
-        self.active = None
+        super().advance()
 
 
 class ForwardStep:

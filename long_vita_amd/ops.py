@@ -1386,6 +1386,41 @@ def gemv_rows_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epi
     return y
 
 
+def _prefix_views(what: str, shapes: str, q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, prefix_len: int, dims_ok: bool = True):
+    """What beam_attn, prefix_batch_attn and prefix_extend_attn (`what`) ask of the arguments they share, in front of their own
+    checks: q [rows, Hkv, G, D] — a view into the mixed QKV rows — and the k / v cache views [cap, Hkv, D] with prefix_len <= cap.
+    Returns (rows, Hkv, G, D, prefix_len)."""
+    if q.dim() != 4 or k_cache.dim() != 3 or not dims_ok:
+        raise ValueError(f"{what}: {shapes}")
+    rows, Hkv, G, D = q.shape
+    if k_cache.shape[1:] != (Hkv, D) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
+        raise ValueError(f"{what}: k / v cache views must be [cap, Hkv, D] with the same strides")
+    if q.stride(3) != 1 or k_cache.stride(2) != 1:
+        raise ValueError("head_dim must be contiguous")
+    if int(prefix_len) > k_cache.shape[0]:
+        raise ValueError("prefix_len exceeds the cache rows")
+    return rows, Hkv, G, D, int(prefix_len)
+
+
+def _tail_table(tail_ptrs: torch.Tensor, rows: int, what: str):
+    if tail_ptrs.dtype != torch.int64 or tuple(tail_ptrs.shape) != (rows, 2) or not tail_ptrs.is_contiguous():
+        raise ValueError(f"{what}: tail_ptrs must be contiguous int64 [{rows}, 2] (K base, V base per row)")
+
+
+def _prefix_out(q: torch.Tensor, out: Optional[torch.Tensor], rows: str, Hq: int, prefix_len: int, bytes_entry: str, on_device=()):
+    """Behind those checks: the contexts out [rows, Hq, D] (allocated when None), the tensors in on_device refused when they are on
+    the host, then the library and the op's workspace, sized by its entry bytes_entry.  Returns (out, library, workspace, bytes)."""
+    n, D = q.shape[0], q.shape[3]
+    o = torch.empty((n, Hq, D), dtype=BF16, device=q.device) if out is None else out
+    if tuple(o.shape) != (n, Hq, D) or not o.is_contiguous():
+        raise ValueError(f"out must be contiguous [{rows}, Hq, D]")
+    for t_, name in on_device:
+        _dev(t_, name)
+    h = _L.load()
+    nbytes = getattr(h, bytes_entry)(n, Hq, prefix_len)
+    return o, h, _extend_workspace(max(nbytes, 16), q.device), nbytes
+
+
 def beam_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, prefix_len: int, k_tail: torch.Tensor,
               v_tail: torch.Tensor, ancestry: torch.Tensor, n_gen: int, softmax_scale: Optional[float] = None,
               out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -1393,16 +1428,9 @@ def beam_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pre
     whose rows [0, prefix_len) every beam sees (read once for all of them); k_tail / v_tail [tail_cap, B, Hkv, D] contiguous, the
     beams' generated tokens: beam b's key of step s < n_gen is k_tail[s, ancestry[b, s]] (ancestry int32 [B, tail_cap] on the
     device; entries are clamped into [0, B) by the kernel)."""
-    if q.dim() != 4 or k_cache.dim() != 3 or k_tail.dim() != 4:
-        raise ValueError("beam_attn: q [B, Hkv, G, D], caches [cap, Hkv, D], tails [tail_cap, B, Hkv, D]")
-    B, Hkv, G, D = q.shape
-    if k_cache.shape[1:] != (Hkv, D) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
-        raise ValueError("beam_attn: k / v cache views must be [cap, Hkv, D] with the same strides")
-    if q.stride(3) != 1 or k_cache.stride(2) != 1:
-        raise ValueError("head_dim must be contiguous")
-    prefix_len, n_gen = int(prefix_len), int(n_gen)
-    if prefix_len > k_cache.shape[0]:
-        raise ValueError("prefix_len exceeds the cache rows")
+    B, Hkv, G, D, prefix_len = _prefix_views("beam_attn", "q [B, Hkv, G, D], caches [cap, Hkv, D], tails [tail_cap, B, Hkv, D]", q, k_cache,
+                                             v_cache, prefix_len, k_tail.dim() == 4)
+    n_gen = int(n_gen)
     tail_cap = k_tail.shape[0]
     if tuple(k_tail.shape) != (tail_cap, B, Hkv, D) or v_tail.shape != k_tail.shape or not k_tail.is_contiguous() or not v_tail.is_contiguous():
         raise ValueError("beam_attn: tails must be contiguous [tail_cap, B, Hkv, D]")
@@ -1411,12 +1439,7 @@ def beam_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pre
     if n_gen > tail_cap:
         raise ValueError("n_gen exceeds the tail capacity")
     Hq = Hkv * G
-    o = torch.empty((B, Hq, D), dtype=BF16, device=q.device) if out is None else out
-    if tuple(o.shape) != (B, Hq, D) or not o.is_contiguous():
-        raise ValueError("out must be contiguous [B, Hq, D]")
-    h = _L.load()
-    nbytes = h.vita_beam_attn_workspace_bytes(B, Hq, prefix_len)
-    ws = _extend_workspace(max(nbytes, 16), q.device)
+    o, h, ws, nbytes = _prefix_out(q, out, "B", Hq, prefix_len, "vita_beam_attn_workspace_bytes")
     _L.check(h.vita_beam_attn_fwd(_dev(q, "q", BF16), q.stride(0), q.stride(1), q.stride(2), _dev(k_cache, "k_cache", BF16),
                                   _dev(v_cache, "v_cache", BF16), k_cache.stride(0), k_cache.stride(1), prefix_len,
                                   _dev(k_tail, "k_tail", BF16), _dev(v_tail, "v_tail", BF16), tail_cap, _dev(ancestry, "ancestry"),
@@ -1434,29 +1457,14 @@ def prefix_batch_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Ten
     tail_row_stride / tail_group_stride (elements) — the table rope_append_rows takes; tail_lens int32 [B] on the device: row b
     sees the first min(max(tail_lens[b], 0), tail_cap) rows of its tail, 0 = an idle row (the prefix alone; its tail is not read).
     Row b has the bits of row b of beam_attn with B beams, an identity ancestry and n_gen = tail_lens[b] on the same tail data."""
-    if q.dim() != 4 or k_cache.dim() != 3:
-        raise ValueError("prefix_batch_attn: q [B, Hkv, G, D], caches [cap, Hkv, D]")
-    B, Hkv, G, D = q.shape
-    if k_cache.shape[1:] != (Hkv, D) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
-        raise ValueError("prefix_batch_attn: k / v cache views must be [cap, Hkv, D] with the same strides")
-    if q.stride(3) != 1 or k_cache.stride(2) != 1:
-        raise ValueError("head_dim must be contiguous")
-    prefix_len, tail_cap = int(prefix_len), int(tail_cap)
-    if prefix_len > k_cache.shape[0]:
-        raise ValueError("prefix_len exceeds the cache rows")
-    if tail_ptrs.dtype != torch.int64 or tuple(tail_ptrs.shape) != (B, 2) or not tail_ptrs.is_contiguous():
-        raise ValueError(f"prefix_batch_attn: tail_ptrs must be contiguous int64 [{B}, 2] (K base, V base per row)")
+    B, Hkv, G, D, prefix_len = _prefix_views("prefix_batch_attn", "q [B, Hkv, G, D], caches [cap, Hkv, D]", q, k_cache, v_cache, prefix_len)
+    tail_cap = int(tail_cap)
+    _tail_table(tail_ptrs, B, "prefix_batch_attn")
     if tail_lens.dtype != torch.int32 or tuple(tail_lens.shape) != (B,) or not tail_lens.is_contiguous():
         raise ValueError(f"prefix_batch_attn: tail_lens must be contiguous int32 [{B}]")
     Hq = Hkv * G
-    o = torch.empty((B, Hq, D), dtype=BF16, device=q.device) if out is None else out
-    if tuple(o.shape) != (B, Hq, D) or not o.is_contiguous():
-        raise ValueError("out must be contiguous [B, Hq, D]")
-    for t_, name in ((q, "q"), (tail_ptrs, "tail_ptrs"), (tail_lens, "tail_lens")):
-        _dev(t_, name)
-    h = _L.load()
-    nbytes = h.vita_prefix_batch_attn_workspace_bytes(B, Hq, prefix_len)
-    ws = _extend_workspace(max(nbytes, 16), q.device)
+    o, h, ws, nbytes = _prefix_out(q, out, "B", Hq, prefix_len, "vita_prefix_batch_attn_workspace_bytes",
+                                   ((q, "q"), (tail_ptrs, "tail_ptrs"), (tail_lens, "tail_lens")))
     _L.check(h.vita_prefix_batch_attn_fwd(_dev(q, "q", BF16), q.stride(0), q.stride(1), q.stride(2), _dev(k_cache, "k_cache", BF16),
                                           _dev(v_cache, "v_cache", BF16), k_cache.stride(0), k_cache.stride(1), prefix_len,
                                           _dev(tail_ptrs, "tail_ptrs"), int(tail_row_stride), int(tail_group_stride),
@@ -1499,35 +1507,20 @@ def prefix_extend_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Te
     tokens' rotated K / V at [tail0, tail0 + count); count 0 = an idle row (its tail is not read); a query row no segment names
     gets the prefix alone.  The triples are checked here (prefix_extend_segments).  table: the same triples as int32 [B, 3] on the
     device, when the caller uploaded them already (one upload per pass, not per layer); None: uploaded here."""
-    if q.dim() != 4 or k_cache.dim() != 3:
-        raise ValueError("prefix_extend_attn: q [n, Hkv, G, D], caches [cap, Hkv, D]")
-    n, Hkv, G, D = q.shape
-    if k_cache.shape[1:] != (Hkv, D) or v_cache.shape != k_cache.shape or k_cache.stride() != v_cache.stride():
-        raise ValueError("prefix_extend_attn: k / v cache views must be [cap, Hkv, D] with the same strides")
-    if q.stride(3) != 1 or k_cache.stride(2) != 1:
-        raise ValueError("head_dim must be contiguous")
-    prefix_len, tail_cap = int(prefix_len), int(tail_cap)
-    if prefix_len > k_cache.shape[0]:
-        raise ValueError("prefix_len exceeds the cache rows")
+    n, Hkv, G, D, prefix_len = _prefix_views("prefix_extend_attn", "q [n, Hkv, G, D], caches [cap, Hkv, D]", q, k_cache, v_cache, prefix_len)
+    tail_cap = int(tail_cap)
     if tail_cap < 0:
         raise ValueError("prefix_extend_attn: tail_cap >= 0")
     rows, max_count = prefix_extend_segments(segments, n, tail_cap)
     B = len(rows)
-    if tail_ptrs.dtype != torch.int64 or tuple(tail_ptrs.shape) != (B, 2) or not tail_ptrs.is_contiguous():
-        raise ValueError(f"prefix_extend_attn: tail_ptrs must be contiguous int64 [{B}, 2] (K base, V base per row)")
+    _tail_table(tail_ptrs, B, "prefix_extend_attn")
     if table is None:
         table = torch.tensor(rows, dtype=torch.int32).to(q.device)
     elif table.dtype != torch.int32 or tuple(table.shape) != (B, 3) or not table.is_contiguous():
         raise ValueError(f"prefix_extend_attn: table must be contiguous int32 [{B}, 3]")
     Hq = Hkv * G
-    o = torch.empty((n, Hq, D), dtype=BF16, device=q.device) if out is None else out
-    if tuple(o.shape) != (n, Hq, D) or not o.is_contiguous():
-        raise ValueError("out must be contiguous [n, Hq, D]")
-    for t_, name in ((q, "q"), (tail_ptrs, "tail_ptrs"), (table, "table")):
-        _dev(t_, name)
-    h = _L.load()
-    nbytes = h.vita_prefix_extend_attn_workspace_bytes(n, Hq, prefix_len)
-    ws = _extend_workspace(max(nbytes, 16), q.device)
+    o, h, ws, nbytes = _prefix_out(q, out, "n", Hq, prefix_len, "vita_prefix_extend_attn_workspace_bytes",
+                                   ((q, "q"), (tail_ptrs, "tail_ptrs"), (table, "table")))
     _L.check(h.vita_prefix_extend_attn_fwd(_dev(q, "q", BF16), q.stride(0), q.stride(1), q.stride(2), _dev(k_cache, "k_cache", BF16),
                                            _dev(v_cache, "v_cache", BF16), k_cache.stride(0), k_cache.stride(1), prefix_len,
                                            _dev(tail_ptrs, "tail_ptrs"), int(tail_row_stride), int(tail_group_stride), tail_cap,

@@ -127,8 +127,18 @@ def test_the_switch_selects_the_kernel():
 
 
 def test_the_three_steps_go_through_the_one_owner():
+    """The three steps share ONE layer loop (_rows_token): it makes the four linears' calls and takes the copies once; neither it nor
+    the entries, whose append / attend pieces are nested in them, reach the GEMV kernels on their own, and the entries make no
+    _rows_gemv call at all."""
     import inspect
+    source = lambda name: inspect.getsource(getattr(gpt_vl_model.GPTVLModel, name))  # noqa: E731
+    loop = source("_rows_token")
+    assert loop.count("self._rows_gemv(w8, li, ") == 4 and loop.count("w8 = self._w8_layers()") == 1
+    assert loop.count("_rows_gemv(") == 4 and loop.count("_w8_layers(") == 1
+    entries = ("_beam_forward", "_batch_forward", "_batch_token", "_prefix_batch_forward", "_prefix_batch_token", "_rows_forward")
+    for step in ("_rows_token",) + entries:
+        assert not re.search(r"ops\.gemv_rows(_w8)?\(", source(step)), step
+    for step in entries:
+        assert "_rows_gemv" not in source(step) and "_w8_layers" not in source(step), step
     for step in ("_beam_forward", "_batch_token", "_prefix_batch_token"):
-        src = inspect.getsource(getattr(gpt_vl_model.GPTVLModel, step))
-        assert src.count("self._rows_gemv(w8, li, ") == 4 and src.count("w8 = self._w8_layers()") == 1, step
-        assert not re.search(r"ops\.gemv_rows(_w8)?\(", src), step
+        assert source(step).count("self._rows_token(") == 1, step
