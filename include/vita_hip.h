@@ -918,6 +918,50 @@ int vita_decode_layer_attn_w8(const vita_decode_layer_params* p, const vita_w8_l
 int vita_decode_layer_mlp_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MXFP4 decoder weights for the cached token step (opt-in, CP = 1 and TP = 1): the third value of the switch the
+ * FP8 weights above are the second of, with the same life cycle.  The four linears of a decoder layer are kept a second time as
+ * OCP e2m1 codes [N][K / 2] (two codes per byte: byte j of a row holds element 2 j in bits 0-3 and element 2 j + 1 in bits 4-7; row
+ * stride in BYTES, a multiple of 16, pointer 16-byte aligned) plus one E8M0 scale byte per run of 32 consecutive K elements of a
+ * row, scales [N][K / 32] dense: 0.266 of the bf16 bytes.  The rule (csrc/mx4_rule.h), per run w[0..31]: amax = max |w_i|;
+ * amax == 0: e = 0, else e = the smallest integer with amax <= 6 * 2^e, clamped to [-126, 127]; scale byte = e + 127;
+ * code_i = sign << 3 | idx with idx the index in {0, 0.5, 1, 1.5, 2, 3, 4, 6} nearest to |w_i| / 2^e, ties to the even index, the
+ * sign kept also on a zero; nothing is clamped.  A run with a non-finite element gets scale byte 0xFF and codes 0; the GEMVs read a
+ * scale byte as the float (byte << 23), so such a run makes its outputs non-finite.  The GEMV computes with
+ * grid[idx] * (+-1) * 2^e.  K must be a multiple of 32 (else VITA_ERR_UNSUPPORTED, as for a misaligned code base or stride).
+ *
+ * vita_mx4_quantize: W [N][K] bf16 (row stride ldw in elements, a multiple of 8, pointer 16-byte aligned) -> codes and scales.
+ *   Bytes of a code row behind K / 2 are not written.  Runs once per weight.
+ * vita_gemv_mx4: vita_gemv_w8 over these codes and scales, the same epilogues (SWIGLU: codes and scales of cat[gate, up], 2 N
+ *   rows) and the same folded RMSNorm (gamma != NULL).  The products are summed in fp32, a run's scale multiplies a lane's
+ *   finished 16-element partial sum, nothing is rounded to bf16 in front of the epilogue.  Rows behind N and columns behind K are
+ *   never read.
+ * vita_gemv_rows_mx4: vita_gemv_mx4 for the rows x[b][K], b < rows, 1 <= rows <= 8 (else VITA_ERR_UNSUPPORTED), of the multi-row
+ *   decode steps (x, y, R through their row strides ldx, ldy, ldr in elements): every code row and its scales are read once for all
+ *   input rows, and row b has the bits of vita_gemv_mx4 (gamma = NULL) on row b.  No folded RMSNorm.  RESIDUAL: y may alias R.
+ *   Nothing behind code row N (2 N for SWIGLU), column K or input row rows - 1 is read.
+ * vita_decode_layer_attn_mx4 / vita_decode_layer_mlp_mx4: vita_decode_layer_attn_w8 / _mlp_w8 with the four GEMVs reading the codes
+ *   and scales of `w` (dense: row stride K / 2); kv8 as there.  hidden and ffn must be multiples of 32.
+ * Stand behind the linears of M/core/tensor_parallel/layers.py:825 at sq = 1, under the decode loop
+ * M/inference/text_generation/generation.py:127-131. */
+typedef struct {
+  const void *qkv_codes, *o_codes, *fc1_codes, *fc2_codes;      /* e2m1 pairs [N][K / 2], dense, 16-byte aligned */
+  const void *qkv_scales, *o_scales, *fc1_scales, *fc2_scales;  /* E8M0 bytes [N][K / 32], dense */
+} vita_mx4_layer;
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
+int vita_mx4_quantize(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, int64_t ldc_bytes, void* scales, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
+int vita_gemv_mx4(const void* x, const void* codes, int64_t ldc_bytes, const void* scales, void* y, int64_t N, int64_t K,
+                  int epilogue, const void* bias, const void* R, const void* gamma, float eps, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 for up to 8 rows (beam search M/inference/text_generation/generation.py:283-471,
+ * the batch_size > 1 decode loop :33-280) */
+int vita_gemv_rows_mx4(const void* x, int64_t ldx, int rows, const void* codes, int64_t ldc_bytes, const void* scales, void* y,
+                       int64_t ldy, int64_t N, int64_t K, int epilogue, const void* bias, const void* R, int64_t ldr, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
+int vita_decode_layer_attn_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, const vita_kv8_cache* kv8, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq = 1 (decode loop M/inference/text_generation/generation.py:127-131) */
+int vita_decode_layer_mlp_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Frame / image preprocessing — ImageProcessor.process_images and dynamic_preprocess,
  * H/data/processor/image_processor.py:180-223,404-448, then the bf16 cast of
  * M/tasks/inference/module.py:693.  frames [n][height][width][3] uint8 RGB (frame_stride bytes apart)

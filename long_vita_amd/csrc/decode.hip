@@ -744,3 +744,42 @@ extern "C" int vita_decode_layer_mlp_w8(const vita_decode_layer_params* p, const
   return vita_gemv_w8(p->act, w->fc2_codes, p->ffn, w->fc2_scales, p->h, p->hidden, p->ffn, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr,
                       0.f, st);
 }
+
+// the same layer with MXFP4 weights (mx4.hip): the _w8 entries with the four GEMVs swapped
+extern "C" int vita_decode_layer_attn_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, const vita_kv8_cache* c,
+                                          void* stream) {
+  if (!decode_layer_args_ok(p) || !w || !w->qkv_codes || !w->qkv_scales || !p->ln1 || !p->qkv_b || !p->cos || !p->sin ||
+      !p->part_m || !p->part_l || !p->part_o || (c ? kv8_cache_null(c) : (!p->k_cache || !p->v_cache)))
+    return VITA_ERR_INVALID_ARG;
+  if (p->head_dim != 128 || p->heads / p->kv_groups > 8 || (p->hidden & 31) || p->len < 0 || p->len > p->capacity ||
+      p->append_row >= p->capacity || p->n_splits <= 0 || (c && kv8_cache_misaligned(c)) || ((uintptr_t)w->qkv_codes & 15) ||
+      (((uintptr_t)p->h | (uintptr_t)p->ln1) & 15))
+    return VITA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t qkv_out = (int64_t)(p->heads + 2 * p->kv_groups) * p->head_dim;
+  const int rc = vita_gemv_mx4(p->h, w->qkv_codes, p->hidden / 2, w->qkv_scales, p->qkv, qkv_out, p->hidden, VITA_EPI_BIAS, p->qkv_b,
+                               nullptr, p->ln1, p->eps, st);
+  if (rc != VITA_OK) return rc;
+  return decode_layer_attn_tail(p, c, st);
+}
+
+extern "C" int vita_decode_layer_mlp_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, void* stream) {
+  if (!decode_layer_args_ok(p) || !w || !w->o_codes || !w->o_scales || !w->fc1_codes || !w->fc1_scales || !w->fc2_codes ||
+      !w->fc2_scales || !p->ln2)
+    return VITA_ERR_INVALID_ARG;
+  if (p->head_dim != 128 || (p->hidden & 31) || (p->ffn & 31) ||
+      (((uintptr_t)w->o_codes | (uintptr_t)w->fc1_codes | (uintptr_t)w->fc2_codes) & 15) ||
+      (((uintptr_t)p->h | (uintptr_t)p->ctx | (uintptr_t)p->act | (uintptr_t)p->ln2) & 15))
+    return VITA_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  int rc = decode_layer_merge_ranks(p, st);
+  if (rc != VITA_OK) return rc;
+  const int64_t hd = (int64_t)p->heads * p->head_dim;
+  rc = vita_gemv_mx4(p->ctx, w->o_codes, hd / 2, w->o_scales, p->h, p->hidden, hd, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr, 0.f, st);
+  if (rc != VITA_OK) return rc;
+  rc = vita_gemv_mx4(p->h, w->fc1_codes, p->hidden / 2, w->fc1_scales, p->act, p->ffn, p->hidden, VITA_EPI_SWIGLU, nullptr, nullptr,
+                     p->ln2, p->eps, st);
+  if (rc != VITA_OK) return rc;
+  return vita_gemv_mx4(p->act, w->fc2_codes, p->ffn / 2, w->fc2_scales, p->h, p->hidden, p->ffn, VITA_EPI_RESIDUAL, nullptr, p->h,
+                       nullptr, 0.f, st);
+}

@@ -79,9 +79,10 @@ class GPTVLModel:
         # bytes (CP = 1, TP = 1).  An InferenceParams with a kv_cache_dtype of its own overrides it
         self.kv_cache_dtype = os.environ.get("VITA_KV_CACHE_DTYPE", "bf16")
         # what the cached token step and the multi-row steps (beam, batched, shared-prefix; CP = 1, TP = 1) read the four linears of
-        # every layer from: "bf16", or "fp8_e4m3" = e4m3 codes + one fp32 scale per 128 K elements of a weight row, 0.516 of the bytes
-        # (DESIGN.md 4.5).  The quantised copies are built at the first such step and kept in self._w8 next to the bf16 weights, which
-        # prefill, extend and the head go on reading
+        # every layer from: "bf16", "fp8_e4m3" = e4m3 codes + one fp32 scale per 128 K elements of a weight row, 0.516 of the bytes, or
+        # "mxfp4" = e2m1 codes + one E8M0 scale byte per 32 K elements, 0.266 of the bytes.  The quantised copies, of
+        # one format at a time, are built at the first such step and kept in self._w8 next to the bf16 weights, which prefill, extend
+        # and the head go on reading
         self._w8 = None
         self.decode_weight_dtype = os.environ.get("VITA_DECODE_WEIGHT_DTYPE", "bf16")
 
@@ -99,20 +100,26 @@ class GPTVLModel:
 
     @decode_weight_dtype.setter
     def decode_weight_dtype(self, name: str):
-        self._decode_weight_dtype = check_decode_weight_dtype(name)
-        if name == "bf16":
-            self._w8 = None                  # frees the quantised copies
+        if check_decode_weight_dtype(name) == "bf16" or name != getattr(self, "_decode_weight_dtype", name):
+            self._w8 = None                  # frees the quantised copies: they are of the format the switch leaves
+        self._decode_weight_dtype = name
 
     W8_NAMES = ("qkv_w", "o_w", "fc1_w", "fc2_w")
+
+    @property
+    def _mx4(self) -> bool:
+        """The copies in self._w8 are (to be) MXFP4 codes + scale bytes, not FP8 codes + fp32 scales."""
+        return getattr(self, "_decode_weight_dtype", "bf16") == "mxfp4"
 
     def _w8_layers(self, refresh: bool = False):
         """The quantised copies of every layer's four weights, [{name: (codes, scales)}], or None with the switch at "bf16".  Built
         on the device when first asked for (the first cached token or multi-row step); refresh (the start of a request) re-quantises,
         in place, every copy whose source has another data_ptr() or _version than the one it was made from."""
-        if getattr(self, "_decode_weight_dtype", "bf16") != "fp8_e4m3":
+        if getattr(self, "_decode_weight_dtype", "bf16") == "bf16":
             return None
         if mpu.get_context_parallel_world_size() > 1 or mpu.get_tensor_model_parallel_world_size() > 1 or self.force_cp_path:
-            raise NotImplementedError("the FP8 decoder weights are built for CP = 1 and TP = 1")
+            raise NotImplementedError("the FP8 and MXFP4 decoder weights are built for CP = 1 and TP = 1")
+        quantize, layout = (ops.mx4_quantize, ops.mx4_layout) if self._mx4 else (ops.w8_quantize, ops.w8_layout)
         if getattr(self, "_w8", None) is None:
             self._w8 = [{} for _ in self.p["layers"]]
             self._w8_src = [{} for _ in self.p["layers"]]
@@ -124,22 +131,22 @@ class GPTVLModel:
                 tag = (w.data_ptr(), w._version)
                 if src.get(name) != tag:
                     have = q.get(name)
-                    reuse = have if have is not None and have[0].shape == w.shape else (None, None)
-                    q[name] = ops.w8_quantize(w, *reuse)
+                    reuse = have if have is not None and tuple(have[0].shape) == layout(*w.shape)["codes"] else (None, None)
+                    q[name] = quantize(w, *reuse)
                     src[name] = tag
         return self._w8
 
     def _rows_gemv(self, w8, li: int, x: torch.Tensor, name: str, epilogue: int, bias=None, gamma=None, xn=None, **kw):
         """Linear `name` of layer li on the rows x [B <= 8, K] of a multi-row step (_rows_token): the one owner of its FP8 / bf16 choice.  w8 = self._w8_layers(), taken once per step.  None: ops.gemv_rows on the bf16
-        weight, the RMSNorm (gamma) folded into the kernel.  Else ops.rmsnorm into the workspace rows xn, then ops.gemv_rows_w8 on
-        the codes and scales the batch-1 step reads: the arithmetic of the unfused batch-1 FP8 step (_decode_token), bit for bit."""
+        weight, the RMSNorm (gamma) folded into the kernel.  Else ops.rmsnorm into the workspace rows xn, then ops.gemv_rows_w8 (MXFP4:
+        ops.gemv_rows_mx4) on the codes and scales the batch-1 step reads: the arithmetic of the unfused batch-1 FP8 step (_decode_token), bit for bit."""
         if w8 is None:
             if gamma is not None:
                 kw.update(gamma=gamma, eps=self.cfg.eps)
             return ops.gemv_rows(x, self.p["layers"][li][name], epilogue, bias, **kw)
         if gamma is not None:
             x = ops.rmsnorm(x, gamma, self.cfg.eps, out=xn)
-        return ops.gemv_rows_w8(x, *w8[li][name], epilogue, bias, **kw)
+        return (ops.gemv_rows_mx4 if self._mx4 else ops.gemv_rows_w8)(x, *w8[li][name], epilogue, bias, **kw)
 
     # ---------------------------------------------------------------------------------------------
     @classmethod
@@ -444,7 +451,8 @@ class GPTVLModel:
         cp, r = mpu.get_context_parallel_world_size(), mpu.get_context_parallel_rank()
         tp = mpu.get_tensor_model_parallel_world_size()     # TP > 1: cfg / params / cache hold this rank's heads, groups and ffn slice
         ws = self._decode_workspace(token.device)
-        w8 = self._w8_layers()                                  # FP8 weights (CP = 1, TP = 1): ops.gemv_w8 in place of ops.gemv
+        w8 = self._w8_layers()                                  # FP8 / MXFP4 weights (CP = 1, TP = 1): ops.gemv_w8 / gemv_mx4 in place of ops.gemv
+        gemv_q = ops.gemv_mx4 if self._mx4 else ops.gemv_w8
         h = ops.row_gather(self.p["embed"], token.reshape(1), out=ws["h"], check_bounds=False)   # [1, hidden]
         cos, sin = ops.rope_table(position.reshape(1), self.rotary_pos_emb.inv_freq)
         owner = (ip.decode_steps % cp) == r
@@ -455,7 +463,7 @@ class GPTVLModel:
             def gemv(x, name, *args, **kw):
                 if w8 is None:
                     return ops.gemv(x, lp[name], *args, **kw)
-                return ops.gemv_w8(x, *w8[li][name], *args, **kw)
+                return gemv_q(x, *w8[li][name], *args, **kw)
 
             kv = ip.key_value_memory_dict[li + 1]
             sc = ip.kv_scale_dict.get(li + 1)                   # FP8 cache (CP = 1): codes in kv, scales here
@@ -563,7 +571,7 @@ class GPTVLModel:
         if w8 is not None and extra.get("w8_of") is not w8:       # FP8 weights: where the _w8 entries find codes and scales
             extra["w8"], extra["w8_of"] = [], w8                  # (built again should the copies have been freed and rebuilt)
             for q in w8:
-                s = _L.W8Layer()
+                s = _L.Mx4Layer() if self._mx4 else _L.W8Layer()
                 for name in self.W8_NAMES:
                     codes, scales = q[name]
                     setattr(s, name[:-2] + "_codes", codes.data_ptr())
@@ -583,12 +591,13 @@ class GPTVLModel:
         lib, stream = _L.load(), torch.cuda.current_stream().cuda_stream
         group = mpu.get_context_parallel_group() if cp > 1 else None
         kv8 = extra.get("kv8")
+        sfx = "_mx4" if isinstance(w8[0] if w8 else None, _L.Mx4Layer) else "_w8"      # the format the structs were built for
+        attn_q, mlp_q = getattr(lib, "vita_decode_layer_attn" + sfx), getattr(lib, "vita_decode_layer_mlp" + sfx)
         for li, s in enumerate(structs):
             s.append_row, s.len, s.n_splits = (row if owner else -1), length, n_splits
             if w8 is not None:
-                _L.check(lib.vita_decode_layer_attn_w8(C.byref(s), C.byref(w8[li]), None if kv8 is None else C.byref(kv8[li]), stream),
-                         "vita_decode_layer_attn_w8")
-                _L.check(lib.vita_decode_layer_mlp_w8(C.byref(s), C.byref(w8[li]), stream), "vita_decode_layer_mlp_w8")
+                _L.check(attn_q(C.byref(s), C.byref(w8[li]), None if kv8 is None else C.byref(kv8[li]), stream), "vita_decode_layer_attn" + sfx)
+                _L.check(mlp_q(C.byref(s), C.byref(w8[li]), stream), "vita_decode_layer_mlp" + sfx)
                 continue
             if kv8 is not None:
                 _L.check(lib.vita_decode_layer_attn_kv8(C.byref(s), C.byref(kv8[li]), stream), "vita_decode_layer_attn_kv8")

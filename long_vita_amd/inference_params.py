@@ -32,13 +32,13 @@ def check_kv_cache_dtype(name, allow_none: bool = False):
     return name
 
 
-DECODE_WEIGHT_DTYPES = ("bf16", "fp8_e4m3")
+DECODE_WEIGHT_DTYPES = ("bf16", "fp8_e4m3", "mxfp4")
 
 
 def check_decode_weight_dtype(name, allow_none: bool = False):
     """What the cached token step and the multi-row steps (beam, batched, shared-prefix) read the four linears of a decoder layer
-    from: "bf16" (the default) or "fp8_e4m3" (OCP e4m3fn codes + one fp32 scale per 128 consecutive K elements of a weight row,
-    DESIGN.md 4.5).  Anything else is a ValueError."""
+    from: "bf16" (the default), "fp8_e4m3" (OCP e4m3fn codes + one fp32 scale per 128 consecutive K elements of a weight row) or
+    "mxfp4" (OCP e2m1 codes + one E8M0 scale byte per 32 consecutive K elements).  Anything else is a ValueError."""
     if name is None and allow_none:
         return None
     if name not in DECODE_WEIGHT_DTYPES:

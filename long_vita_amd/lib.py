@@ -157,6 +157,12 @@ class W8Layer(C.Structure):
     ]
 
 
+class Mx4Layer(C.Structure):
+    """Mirror of ``vita_mx4_layer`` (include/vita_hip.h)."""
+
+    _fields_ = list(W8Layer._fields_)
+
+
 _p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); must list EVERY function declared in include/vita_hip.h
@@ -281,6 +287,11 @@ PROTOTYPES = {
     "vita_gemv_rows_w8": (_i, [_p, _l, _i, _p, _l, _p, _p, _l, _l, _l, _i, _p, _p, _l, _p]),
     "vita_decode_layer_attn_w8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(W8Layer), C.POINTER(Kv8Cache), _p]),
     "vita_decode_layer_mlp_w8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(W8Layer), _p]),
+    "vita_mx4_quantize": (_i, [_p, _l, _l, _l, _p, _l, _p, _p]),
+    "vita_gemv_mx4": (_i, [_p, _p, _l, _p, _p, _l, _l, _i, _p, _p, _p, _f, _p]),
+    "vita_gemv_rows_mx4": (_i, [_p, _l, _i, _p, _l, _p, _p, _l, _l, _l, _i, _p, _p, _l, _p]),
+    "vita_decode_layer_attn_mx4": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(Mx4Layer), C.POINTER(Kv8Cache), _p]),
+    "vita_decode_layer_mlp_mx4": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(Mx4Layer), _p]),
 }
 
 _lock = threading.Lock()

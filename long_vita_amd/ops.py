@@ -1330,6 +1330,71 @@ def gemv_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue
 
 
 # ------------------------------------------------------------------------------------------------
+# MXFP4 (e2m1 + E8M0) decoder weights for the cached token step (include/vita_hip.h: vita_mx4_*, vita_gemv_mx4)
+# ------------------------------------------------------------------------------------------------
+MX4_BLOCK = 32                           # consecutive K elements of a weight row that share a scale byte
+
+
+def mx4_layout(N: int, K: int) -> dict:
+    """Pure layout, no allocation: codes [N, K / 2] uint8 (two e2m1 codes per byte, element 2 j in the low nibble of byte j), scales
+    [N, K / 32] uint8 (E8M0), and their bytes next to the bf16 weight's."""
+    if K % MX4_BLOCK:
+        raise ValueError(f"mx4: K = {K} must be a multiple of {MX4_BLOCK}")
+    nbytes = N * (K // 2) + N * (K // MX4_BLOCK)
+    return {"codes": (N, K // 2), "scales": (N, K // MX4_BLOCK), "bytes": nbytes, "bytes_bf16": 2 * N * K, "ratio": nbytes / (2 * N * K)}
+
+
+def _mx4_views(codes: torch.Tensor, scales: torch.Tensor, what: str):
+    if codes.dim() != 2 or codes.dtype != torch.uint8 or codes.stride(1) != 1:
+        raise ValueError(f"{what}: codes [N, K / 2] must be uint8 with unit inner stride")
+    rows, K = codes.shape[0], 2 * codes.shape[1]
+    if K % MX4_BLOCK:
+        raise RuntimeError(f"{what}: K = {K} must be a multiple of {MX4_BLOCK}")
+    if tuple(scales.shape) != (rows, K // MX4_BLOCK) or scales.dtype != torch.uint8 or not scales.is_contiguous():
+        raise ValueError(f"{what}: scales must be dense uint8 [N, K / {MX4_BLOCK}]")
+    return rows, K
+
+
+def mx4_quantize(w: torch.Tensor, codes: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None):
+    """w [N, K] bf16 (unit inner stride) -> (codes [N, K / 2] uint8, scales [N, K / 32] uint8) by the MXFP4 rule of csrc/mx4_rule.h on
+    every run of 32 consecutive K elements of a row.  codes / scales: destinations to fill (codes may be a padded-row view)."""
+    if w.dim() != 2 or w.stride(1) != 1:
+        raise ValueError("mx4_quantize: w [N, K] with unit inner stride")
+    N, K = w.shape
+    lay = mx4_layout(N, K)
+    if codes is None:
+        codes = torch.empty(lay["codes"], dtype=torch.uint8, device=w.device)
+    if scales is None:
+        scales = torch.empty(lay["scales"], dtype=torch.uint8, device=w.device)
+    if _mx4_views(codes, scales, "mx4_quantize") != (N, K):
+        raise ValueError("mx4_quantize: codes and scales do not match w")
+    _L.check(_L.load().vita_mx4_quantize(_dev(w, "w", BF16), w.stride(0), N, K, _dev(codes, "codes"), codes.stride(0),
+                                         _dev(scales, "scales", torch.uint8), _stream()), "vita_mx4_quantize")
+    return codes, scales
+
+
+def gemv_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+             residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, gamma: Optional[torch.Tensor] = None,
+             eps: float = 0.0) -> torch.Tensor:
+    """gemv over MXFP4 weights: y[N] = epilogue(dequant(codes, scales)[N, K] . x[K]); SWIGLU: codes of cat[gate, up], N = rows / 2.
+    gamma: x is RMS-normalised first (gamma [K], eps), as the fused layer entries do."""
+    K = x.numel()
+    n_rows, Kc = _mx4_views(codes, scales, "gemv_mx4")
+    if Kc != K:
+        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, K / 2 = {K // 2} expected")
+    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
+    y = torch.empty(N, dtype=BF16, device=x.device) if out is None else out
+    if y.numel() != N or not y.is_contiguous() or not x.is_contiguous():
+        raise ValueError("gemv_mx4 needs contiguous x and out of N elements")
+    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
+        raise ValueError("gemv_mx4: gamma [K] contiguous")
+    _L.check(_L.load().vita_gemv_mx4(_dev(x, "x", BF16), _dev(codes, "codes"), codes.stride(0), _dev(scales, "scales", torch.uint8),
+                                     _dev(y, "out", BF16), N, K, epilogue, _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
+                                     _opt(gamma, "gamma", BF16), float(eps), _stream()), "vita_gemv_mx4")
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
 # beam search on a shared-prefix KV cache (M/inference/text_generation/generation.py:283-471)
 # ------------------------------------------------------------------------------------------------
 BEAM_MAX = 8
@@ -1383,6 +1448,31 @@ def gemv_rows_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epi
                                          _dev(scales, "scales", torch.float32), _dev(y, "out", BF16), y.stride(0), N, K, epilogue,
                                          _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
                                          residual.stride(0) if residual is not None else 0, _stream()), "vita_gemv_rows_w8")
+    return y
+
+
+def gemv_rows_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemv_rows over MXFP4 weights: y[b] = epilogue(dequant(codes, scales) . x[b]) for the rows of x [rows <= 8, K]; every code row and
+    its scales are read once for all of them, and row b has the bits of gemv_mx4(x[b]) without gamma (normalise the rows with rmsnorm
+    first).  SWIGLU: codes of cat[gate, up], N = code rows / 2.  residual [rows, N], out [rows, N] (unit inner stride; out may alias
+    residual)."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("gemv_rows_mx4: x must be [rows, K] with a unit inner stride")
+    rows, K = x.shape
+    n_rows, Kc = _mx4_views(codes, scales, "gemv_rows_mx4")
+    if Kc != K:
+        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, K / 2 = {K // 2} expected")
+    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
+    y = torch.empty(rows, N, dtype=BF16, device=x.device) if out is None else out
+    if tuple(y.shape) != (rows, N) or y.stride(1) != 1:
+        raise ValueError("gemv_rows_mx4: out must be [rows, N] with a unit inner stride")
+    if residual is not None and (tuple(residual.shape) != (rows, N) or residual.stride(1) != 1):
+        raise ValueError("gemv_rows_mx4: residual must be [rows, N] with a unit inner stride")
+    _L.check(_L.load().vita_gemv_rows_mx4(_dev(x, "x", BF16), x.stride(0), rows, _dev(codes, "codes"), codes.stride(0),
+                                          _dev(scales, "scales", torch.uint8), _dev(y, "out", BF16), y.stride(0), N, K, epilogue,
+                                          _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
+                                          residual.stride(0) if residual is not None else 0, _stream()), "vita_gemv_rows_mx4")
     return y
 
 
