@@ -849,6 +849,12 @@ int vita_decode_layer_mlp(const vita_decode_layer_params* p, void* stream);
  *   kv_group_stride of the parameter struct are not read.  The appended row holds the codes and scales of the rule applied to the
  *   K / V row vita_decode_layer_attn appends; the context is that of vita_kv8_store + vita_decode_attn_partial_kv8 +
  *   vita_decode_attn_merge, bit for bit.  vita_decode_layer_mlp follows unchanged.
+ * vita_kv8_load: the mirror of vita_kv8_store: reads rows [0, rows) of such a cache back as bf16 into k_dst / v_dst (row 0, group 0;
+ *   strides in bf16 elements, multiples of 8, pointers 16-byte aligned): x~_i = bf16_rne(f32(code_i) * s), one fp32 multiply and one
+ *   round-to-nearest-even conversion; non-finite stays non-finite.  Nothing outside those rows is read or written, the padding
+ *   between rows and groups included.  A cached call of q_len > 1 tokens behind an FP8 cache stages the earlier rows this way and
+ *   runs vita_flash_attn_extend_fwd on the staging buffer.  head_dim != 128, misaligned pointers or strides, rows * groups > 2^40:
+ *   VITA_ERR_UNSUPPORTED; a null pointer, rows <= 0 or groups <= 0: VITA_ERR_INVALID_ARG; nothing is launched.
  * Stands behind Megatron's InferenceParams.key_value_memory_dict (Attention._adjust_key_value_for_inference under the decode loop
  * M/inference/text_generation/generation.py:127-131) and the HF cache update of modeling_long_vita.py:150-202. */
 typedef struct {
@@ -862,6 +868,11 @@ int vita_kv8_store(const void* k_src, const void* v_src, int64_t src_row_stride,
                    int groups, int head_dim, void* k_codes, void* v_codes, int64_t code_row_stride, int64_t code_group_stride,
                    void* k_scales, void* v_scales, int64_t scale_row_stride, int64_t scale_group_stride, int64_t row0,
                    const void* row0_dev, int64_t capacity, void* stream);
+/* the HF cache update modeling_long_vita.py:150-202 with q_len > 1 */
+int vita_kv8_load(const void* k_codes, const void* v_codes, int64_t code_row_stride, int64_t code_group_stride,
+                  const void* k_scales, const void* v_scales, int64_t scale_row_stride, int64_t scale_group_stride, int64_t rows,
+                  int groups, int head_dim, void* k_dst, void* v_dst, int64_t dst_row_stride, int64_t dst_group_stride,
+                  void* stream);
 /* InferenceParams.key_value_memory_dict (Megatron); modeling_long_vita.py:150-202 (HF cache) */
 int vita_decode_attn_partial_kv8(const void* q, int64_t q_group_stride, int64_t q_head_stride, const void* k_codes,
                                  const void* v_codes, int64_t code_row_stride, int64_t code_group_stride, const void* k_scales,

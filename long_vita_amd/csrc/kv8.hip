@@ -1,5 +1,6 @@
-// FP8 (OCP e4m3fn) KV cache for the cached decode: the quantising store and the split decode attention
-// over codes + scales.  One rule for every kernel here and for tests/kv8_cases.py, per K or V head row x[0..127] (bf16, K after
+// FP8 (OCP e4m3fn) KV cache for the cached decode: the quantising store, the split decode attention over codes +
+// scales, and the de-quantising load that hands rows back as bf16 (x~_i = bf16_rne(f32(c_i) * s), kv8_rule.h) to the one-pass extend
+// of a follow-up turn, whose attention kernel reads bf16 K / V.  One rule for every kernel here and for tests/kv8_cases.py, per K or V head row x[0..127] (bf16, K after
 // RoPE) of one (cache row, kv group):
 //   amax = max |x_i| (a NaN in the row makes amax NaN) ; s = amax > 0 ? amax / 448 : 1 ; c_i = e4m3fn_rne(x_i / s) ; x^_i = f32(c_i) * s
 // fp32, IEEE division, no clamp: x / s reaches at most 448 (1 + 2^-23), which rounds to 448; a non-finite element leaves non-finite
@@ -40,6 +41,27 @@ __global__ __launch_bounds__(256) void kv8_store_kernel(const bf16_t* __restrict
     const u32x2 c = kv8_encode8(x, s);
     *reinterpret_cast<u32x2*>((kv ? vc : kc) + (row0 + r) * code_row_stride + (int64_t)g * code_group_stride + sub * 8) = c;
     if (sub == 0) (kv ? vs : ks)[(row0 + r) * scale_row_stride + (int64_t)g * scale_group_stride] = s;
+  }
+}
+
+// ---- de-quantising load: the store's mirror, item = (row r, group g, K or V) on 16 lanes x 8 elements ------------------------------
+// one 8-byte code load + one broadcast 4-byte scale load, kv8_readback8, one 16-byte store: 132 B in and 256 B out per item, HBM-bound.
+// Nothing outside rows [0, rows) is read or written, the padding between rows and groups included.
+__global__ __launch_bounds__(256) void kv8_load_kernel(const unsigned char* __restrict__ kc, const unsigned char* __restrict__ vc,
+                                                       int64_t code_row_stride, int64_t code_group_stride,
+                                                       const float* __restrict__ ks, const float* __restrict__ vs,
+                                                       int64_t scale_row_stride, int64_t scale_group_stride, int64_t rows, int groups,
+                                                       bf16_t* __restrict__ k_dst, bf16_t* __restrict__ v_dst, int64_t dst_row_stride,
+                                                       int64_t dst_group_stride) {
+  const int sub = threadIdx.x & 15;
+  const int64_t items = rows * groups * 2;
+  for (int64_t it = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 4; it < items; it += ((int64_t)gridDim.x * blockDim.x) >> 4) {
+    const int kv = (int)(it & 1);
+    const int g = (int)((it >> 1) % groups);
+    const int64_t r = (it >> 1) / groups;
+    const u32x2 c = *reinterpret_cast<const u32x2*>((kv ? vc : kc) + r * code_row_stride + (int64_t)g * code_group_stride + sub * 8);
+    const float s = (kv ? vs : ks)[r * scale_row_stride + (int64_t)g * scale_group_stride];
+    *reinterpret_cast<u32x4*>((kv ? v_dst : k_dst) + r * dst_row_stride + (int64_t)g * dst_group_stride + sub * 8) = kv8_readback8(c, s);
   }
 }
 
@@ -273,6 +295,25 @@ extern "C" int vita_kv8_store(const void* k_src, const void* v_src, int64_t src_
                      src_row_stride, src_group_stride, rows, groups, (unsigned char*)k_codes, (unsigned char*)v_codes,
                      code_row_stride, code_group_stride, (float*)k_scales, (float*)v_scales, scale_row_stride, scale_group_stride,
                      row0, (const int64_t*)row0_dev, capacity);
+  return vita_check_launch();
+}
+
+extern "C" int vita_kv8_load(const void* k_codes, const void* v_codes, int64_t code_row_stride, int64_t code_group_stride,
+                             const void* k_scales, const void* v_scales, int64_t scale_row_stride, int64_t scale_group_stride,
+                             int64_t rows, int groups, int head_dim, void* k_dst, void* v_dst, int64_t dst_row_stride,
+                             int64_t dst_group_stride, void* stream) {
+  if (!k_dst || !v_dst || rows <= 0 || groups <= 0) return VITA_ERR_INVALID_ARG;
+  int rc = VITA_OK;
+  if (!kv8_cache_ok(k_codes, v_codes, code_row_stride, code_group_stride, k_scales, v_scales, &rc)) return rc;
+  if (head_dim != 128 || (dst_row_stride & 7) || (dst_group_stride & 7) || (((uintptr_t)k_dst | (uintptr_t)v_dst) & 15) ||
+      rows > (int64_t(1) << 40) || rows * groups > (int64_t(1) << 40))
+    return VITA_ERR_UNSUPPORTED;
+  const int64_t items = rows * groups * 2;                               // 16 lanes each, 16 per workgroup
+  const unsigned blocks = (unsigned)((items + 15) / 16 < 4096 ? (items + 15) / 16 : 4096);
+  hipLaunchKernelGGL(kv8_load_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const unsigned char*)k_codes,
+                     (const unsigned char*)v_codes, code_row_stride, code_group_stride, (const float*)k_scales, (const float*)v_scales,
+                     scale_row_stride, scale_group_stride, rows, groups, (bf16_t*)k_dst, (bf16_t*)v_dst, dst_row_stride,
+                     dst_group_stride);
   return vita_check_launch();
 }
 

@@ -30,6 +30,20 @@ __device__ __forceinline__ u32x2 kv8_encode8(const u32x4 x, const float s) {
   }
   return c;
 }
+// The rule for reading a cache row back as bf16 (vita_kv8_load; the one-pass extend behind an FP8 cache): x~_i = bf16_rne(f32(c_i) * s),
+// one fp32 multiply rounded to fp32, then one RNE conversion to bf16.  Non-finite stays non-finite: a NaN code or a NaN scale gives NaN,
+// an inf scale inf (or NaN on a zero code).  In torch: (codes.float() * scales[..., None]).to(torch.bfloat16).
+__device__ __forceinline__ u32x4 kv8_readback8(const u32x2 c, const float s) {
+  u32x4 x;
+#pragma unroll
+  for (int w = 0; w < 2; ++w) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[w], false);
+    const auto hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[w], true);
+    x[2 * w] = pack_bf16x2(lo[0] * s, lo[1] * s);
+    x[2 * w + 1] = pack_bf16x2(hi[0] * s, hi[1] * s);
+  }
+  return x;
+}
 // 4 codes of one word -> two packed bf16 pairs (exact)
 __device__ __forceinline__ void kv8_decode4(const unsigned w, unsigned& p0, unsigned& p1) {
   const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w, false);

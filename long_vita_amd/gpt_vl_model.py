@@ -190,9 +190,22 @@ class GPTVLModel:
             if not extend:
                 n_msg = self.kv_split if self.kv_split is not None else ops.cp_kv_split(c.kv_groups, c.heads, s)
                 ws["kv"] = e(n_msg, 2, s, c.kv_groups // n_msg, c.head_dim)
-            self._ws = {k: v for k, v in self._ws.items() if k == "decode" or isinstance(k, tuple) != extend}   # one size of this kind
+            keep = ("decode", "kv8_stage")
+            self._ws = {k: v for k, v in self._ws.items() if k in keep or isinstance(k, tuple) != extend}   # one size of this kind
             self._ws[key] = ws
         return ws
+
+    def _kv8_stage(self, n: int, device, cap: int) -> torch.Tensor:
+        """The bf16 K / V [2, >= n, groups, d] a cached call behind an FP8 cache attends over: one layer's worth of bf16 cache (0.54 GB
+        at 128K rows, 4.3 GB at 1M), one buffer per model shared by all layers.  Grows geometrically (the chunks of a chunked prefill
+        do not each allocate), by no more than the cache's capacity `cap` asks for; a shorter call keeps it."""
+        st = self._ws.get("kv8_stage")
+        if st is None or st.shape[1] < n or st.device != device:
+            rows = n if st is None or st.device != device else max(n, min(2 * st.shape[1], cap))
+            del st
+            self._ws.pop("kv8_stage", None)                       # free the smaller one first
+            st = self._ws["kv8_stage"] = torch.empty(2, rows, self.cfg.kv_groups, self.cfg.head_dim, dtype=torch.bfloat16, device=device)
+        return st
 
     def decoder_layer(self, h: torch.Tensor, lp: dict, cos, sin, ws, kv_dst: Optional[torch.Tensor] = None,
                       cached_rows: Optional[int] = None, keep: Optional[tuple] = None,
@@ -206,7 +219,11 @@ class GPTVLModel:
         layer for the n kept rows only, each with the arithmetic of the full layer; returns those rows [n, hidden] (h is left as the
         layer found it).  A geometry whose attention takes no window runs the full layer and returns h.
         kv_scale [2, cap, groups] fp32: kv_dst is an FP8 cache (CP = 1): the rows are quantised into it (ops.kv8_store); the
-        layer's own attention reads the bf16 K / V of the mixed buffer as ever, so the prefill's logits do not depend on the cache."""
+        layer's own attention reads the bf16 K / V of the mixed buffer as ever, so the prefill's logits do not depend on the cache.
+        With cached_rows = L the attention runs on a bf16 staging buffer (_kv8_stage, one per model, shared by the layers): rows
+        [0, L) are the cache read back (ops.kv8_load: bf16_rne(f32(code) * scale)), rows [L, L + s) the new rows' bf16 K / V.  The
+        new rows see EACH OTHER in bf16, as rows of a prefill do, and every earlier row as the cache reads it back — deliberately
+        not the per-token loop's arithmetic, where a token reads its own quantised K / V."""
         c = self.cfg
         s = h.shape[0]
         cp = mpu.get_context_parallel_world_size()
@@ -217,11 +234,18 @@ class GPTVLModel:
         ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ws["kv"] if use_cp else None, ws["kv"].shape[0] if "kv" in ws else 1)
         m5 = qkv.view(1, s, c.kv_groups, c.qpg + 2, c.head_dim)
         q5 = m5[:, :, :, : c.qpg]                                  # grouped query view, read in place
+        kv_att = kv_dst                                            # what a cached call's attention reads
         if kv_dst is not None:
             if kv_scale is not None:
-                if use_cp or cached_rows is not None:
-                    raise NotImplementedError("an FP8 KV cache is filled by the CP = 1 prefill and the token step only")
+                if cp > 1 or self.force_cp_path:
+                    raise NotImplementedError("an FP8 KV cache is filled and extended at CP = 1 only")
                 ops.kv8_store(m5[0, :, :, c.qpg], m5[0, :, :, c.qpg + 1], kv_dst[0], kv_dst[1], kv_scale[0], kv_scale[1], row0)
+                if cached_rows is not None:
+                    kv_att = self._kv8_stage(row0 + s, h.device, kv_dst.shape[1])
+                    if row0 > 0:
+                        ops.kv8_load(kv_dst[0], kv_dst[1], kv_scale[0], kv_scale[1], row0, kv_att[0], kv_att[1])
+                    kv_att[0, row0: row0 + s].copy_(m5[0, :, :, c.qpg])
+                    kv_att[1, row0: row0 + s].copy_(m5[0, :, :, c.qpg + 1])
             elif use_cp:
                 context_parallel.unpack_kv(ws["kv"], out=kv_dst[:, :s])
             else:
@@ -243,7 +267,7 @@ class GPTVLModel:
                 ev[0].record()
             if cached_rows is not None:
                 # the shard is in sequence order at CP = 1: visibility is by cache row, whatever position ids rotated the rows
-                ops.flash_attn_extend(q5[0], kv_dst[0], kv_dst[1], row0 + s, q_pos0=row0, out=ws["ctx"][0])
+                ops.flash_attn_extend(q5[0], kv_att[0], kv_att[1], row0 + s, q_pos0=row0, out=ws["ctx"][0])
                 ctx = ws["ctx"]
             else:
                 seg = training_utils.get_packed_segments()       # position ids with resets -> packed samples
@@ -665,8 +689,8 @@ class GPTVLModel:
                 raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
             logits = self._decode_graphed(input_ids[0], position_ids[0], ip).view(1, 1, -1).clone()
             return ops.logit_postprocess_(logits, self.cfg.output_multiplier_scale, self.cfg.output_logit_softcapping)
-        # the one-pass extend kernel reads a bf16 cache: an FP8 cache takes the per-token loop below
-        if t >= max(2, self.extend_min_tokens) and tp == 1 and mpu.get_context_parallel_world_size() == 1 and not ip.kv_scale_dict:
+        # the one-pass extend kernel reads bf16 K / V: behind an FP8 cache each layer stages them (decoder_layer, ops.kv8_load)
+        if t >= max(2, self.extend_min_tokens) and tp == 1 and mpu.get_context_parallel_world_size() == 1:
             return self._extend_forward(input_ids, position_ids, ip)
         ip._graph = None                      # eager steps move the python-side counters only
         # tensor parallelism (the released server runs TP 8 x CP 4, server_cp .sh:102-104): the kernel-by-kernel step, whose
@@ -682,7 +706,8 @@ class GPTVLModel:
     def _extend_forward(self, input_ids: torch.Tensor, position_ids: torch.Tensor, ip) -> torch.Tensor:
         """t > 1 new tokens behind the cached context in ONE pass (CP = 1, TP = 1): the prefill's layers on t rows, K / V appended to
         the shard, attention over the whole shard (vita_flash_attn_extend_fwd) — a follow-up turn, or one chunk of a chunked prefill.
-        What modeling_long_vita.py:150-202 does with q_len > 1 behind a DynamicCache.  Returns logits [1, n, vocab] of the rows
+        What modeling_long_vita.py:150-202 does with q_len > 1 behind a DynamicCache.  An FP8 shard (ip.kv_scale_dict) takes the new rows'
+        codes and scales and is read back as bf16 per layer (decoder_layer: ops.kv8_load into the model's staging buffer).  Returns logits [1, n, vocab] of the rows
         ip.logit_mask ([1, t]) keeps, of all t rows without one."""
         c = self.cfg
         t = input_ids.shape[1]
@@ -699,7 +724,8 @@ class GPTVLModel:
         ws = self._workspace(t, h.device, extend=True)
         for li, lp in enumerate(self.p["layers"]):
             with tracing.range(f"extend: layer {li}"):
-                self.decoder_layer(h, lp, cos, sin, ws, ip.key_value_memory_dict[li + 1], cached_rows=row0)
+                self.decoder_layer(h, lp, cos, sin, ws, ip.key_value_memory_dict[li + 1], cached_rows=row0,
+                                   kv_scale=ip.kv_scale_dict.get(li + 1))
         ip.local_len = row0 + t
         ip.decode_steps += t
         ip.consumed_tokens = t

@@ -279,6 +279,7 @@ PROTOTYPES = {
                                          C.c_size_t, _p]),
     # FP8 (e4m3) KV cache for the cached decode
     "vita_kv8_store": (_i, [_p, _p, _l, _l, _l, _i, _i, _p, _p, _l, _l, _p, _p, _l, _l, _l, _p, _l, _p]),
+    "vita_kv8_load": (_i, [_p, _p, _l, _l, _p, _p, _l, _l, _l, _i, _i, _p, _p, _l, _l, _p]),
     "vita_decode_attn_partial_kv8": (_i, [_p, _l, _l, _p, _p, _l, _l, _p, _p, _l, _l, _i, _p, _i, _i, _i, _i, _f, _p, _p, _p, _p]),
     "vita_decode_layer_attn_kv8": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(Kv8Cache), _p]),
     # FP8 (e4m3) decoder weights for the cached token step

@@ -1239,6 +1239,26 @@ def kv8_store(k_src: torch.Tensor, v_src: torch.Tensor, k_codes: torch.Tensor, v
                                       _dev(row0, "row0", torch.int64) if on_dev else None, cap, _stream()), "vita_kv8_store")
 
 
+def kv8_load(k_codes: torch.Tensor, v_codes: torch.Tensor, k_scales: torch.Tensor, v_scales: torch.Tensor, rows: int,
+             k_dst: torch.Tensor, v_dst: torch.Tensor) -> None:
+    """Read rows [0, rows) of the cache views k_codes / v_codes [cap, G, d] and k_scales / v_scales [cap, G] fp32 back as bf16 into
+    rows [0, rows) of k_dst / v_dst [n, G, d] (shared strides, unit inner stride): bf16_rne(f32(code) * scale), in torch
+    (codes.float() * scales[..., None]).to(torch.bfloat16).  Nothing behind row `rows` is read or written."""
+    cap, G, d = _kv8_views(k_codes, v_codes, k_scales, v_scales, "kv8_load")
+    rows = int(rows)
+    if (k_dst.dim() != 3 or tuple(k_dst.shape[1:]) != (G, d) or v_dst.shape != k_dst.shape or v_dst.stride() != k_dst.stride()
+            or k_dst.stride(2) != 1):
+        raise ValueError("kv8_load: destinations [n, G, d] with shared strides and unit inner stride")
+    if rows < 0 or rows > cap or rows > k_dst.shape[0]:
+        raise ValueError("kv8_load: rows do not fit the cache or the destination")
+    if rows == 0:
+        return
+    _L.check(_L.load().vita_kv8_load(_dev(k_codes, "k_codes"), _dev(v_codes, "v_codes"), k_codes.stride(0), k_codes.stride(1),
+                                     _dev(k_scales, "k_scales", torch.float32), _dev(v_scales, "v_scales", torch.float32),
+                                     k_scales.stride(0), k_scales.stride(1), rows, G, d, _dev(k_dst, "k_dst", BF16),
+                                     _dev(v_dst, "v_dst", BF16), k_dst.stride(0), k_dst.stride(1), _stream()), "vita_kv8_load")
+
+
 def decode_attn_partial_kv8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: torch.Tensor, k_scales: torch.Tensor,
                             v_scales: torch.Tensor, length: int, softmax_scale: Optional[float] = None,
                             len_dev: Optional[torch.Tensor] = None):
