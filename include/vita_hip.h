@@ -85,6 +85,34 @@ int vita_select_token(const void* logits /* bf16 [rows, ld] */, int64_t ld, int6
                       int64_t* token_out /* [rows] */, int32_t* kept_out /* [rows], may be NULL */,
                       int mark_chosen, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Prompt-lookup speculative decoding (transformers' generate(prompt_lookup_num_tokens=k) at the same call site).  Additions at ABI 19.
+ * Neither entry synchronises with the host.
+ * vita_ngram_draft: the candidate rule of PromptLookupCandidateGenerator.get_candidates on the device history hist[0, n),
+ * n = clamp(*n_hist, 0, hist_cap):  for g = min(max_ngram, n - 1) down to 1 take the LEFTMOST i in [0, n - g] with
+ * hist[i : i + g] == hist[n - g : n] and i + g < min(n, max_total); the candidate is hist[i + g : min(i + g + num_draft, n, max_total)],
+ * cut in front of its first eos id.  The first g that has such an i ends the search, even when the cut leaves nothing.  No such i, or
+ * max_total == n + 1: zero drafts.  draft_out [num_draft] (unused slots -1), n_draft_out [1].  One pass over the history for all g; an
+ * order-independent 64-bit minimum in two stages through `workspace` (8-byte aligned, vita_ngram_draft_workspace_bytes, never
+ * initialised by the caller): the result is deterministic.  An entry of hist never forms an address.  Null pointers, num_draft < 1,
+ * max_ngram < 1: VITA_ERR_INVALID_ARG; num_draft > 7, n_eos > 8, max_ngram > 2^20, hist_cap >= 2^31: VITA_ERR_UNSUPPORTED.
+ * vita_draft_verify: the greedy acceptance of one verify pass of t = 2 .. 8 rows.  a_i = the choice vita_select_token makes with
+ * do_sample = 0 on row i when the penalised ids are seen U {draft[0 .. i - 1]} (a draft id outside [0, cols) penalises nothing, never
+ * indexes seen and never equals an a_i); n_acc = the leading i < t - 1 with draft[i] == a_i; emitted = a_0 .. a_{n_acc}, cut BEHIND the
+ * first one that is an eos id (stop = 1).  Then hist[n .. n + n_emit) = emitted while they fit hist_cap, *n_hist = min(n + n_emit,
+ * hist_cap), seen[token] = 1 for each emitted token, record [t + 2] = {n_emit, stop, emitted[0 .. t - 1]} with unused slots -1.
+ * A row in which no score exceeds -inf (all -inf or NaN) chooses id 0: the history and the byte map only ever see ids in [0, cols).
+ * cols / ld / alignment as vita_select_token; t outside 2 .. 8: VITA_ERR_UNSUPPORTED. */
+/* tools/inference_long_vita.py:820-826,868 */
+int64_t vita_ngram_draft_workspace_bytes(int64_t hist_cap);
+/* tools/inference_long_vita.py:820-826,868 */
+int vita_ngram_draft(const int64_t* hist, int64_t hist_cap, const int32_t* n_hist, int max_ngram, int num_draft,
+                     int64_t max_total, const int64_t* eos, int n_eos, int64_t* draft_out, int32_t* n_draft_out,
+                     void* workspace, int64_t workspace_bytes, void* stream);
+/* tools/inference_long_vita.py:820-826,868 */
+int vita_draft_verify(const void* logits, int64_t ld, int t, int64_t cols, uint8_t* seen, float repetition_penalty,
+                      const int64_t* draft, const int64_t* eos, int n_eos, int64_t* hist, int64_t hist_cap, int32_t* n_hist,
+                      int64_t* record, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * RoPE.  Replaces M/core/models/common/embeddings/rotary_pos_embedding.py:84-122 (table),
  * :181-204 (apply_rotary_pos_emb_bshd) and apex fused_apply_rotary_pos_emb (:248-252).

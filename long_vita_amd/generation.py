@@ -454,6 +454,137 @@ def _generate_shared_prefix(model, tokens, lengths, shared_prefix_len, return_ou
 
 
 # ------------------------------------------------------------------------------------------------
+# prompt-lookup speculative decoding (transformers' generate(prompt_lookup_num_tokens=k); tools/inference_long_vita.py:820-826,868)
+# ------------------------------------------------------------------------------------------------
+LOOKUP_MIN, LOOKUP_MAX = 1, 7
+
+
+@torch.no_grad()
+def generate_with_lookup(model, forward_step, first_logits, ids, max_new_tokens, *, num_draft, max_ngram=2, eos=(),
+                         repetition_penalty=1.0, draft_source=None, stats=None):
+    """Greedy decoding that verifies up to num_draft = 1 .. 7 drafted tokens per step, behind a batch-1 prefill or extend: forward_step
+    is the ForwardStep whose cache holds all of ids [1, s] (the WHOLE conversation) and first_logits [1, V] (bf16) are the logits of its
+    last token.  Returns [1, s + generated] int64; the cache then holds everything but the last generated token.
+
+    The history (int64 [s + max_new_tokens] and its length) and the byte map of seen ids live on the device.  Every iteration ends
+    with ONE small device-to-host copy: the record of what was emitted and the number of drafts for the next iteration.
+      zero drafts    the ordinary token step (the captured graph included), ops.select_token, greedy;
+      n drafts       a verify pass of t = 1 + min(n, remaining - 1, capacity - L - 1) rows fed [last token, drafts]
+                     (GPTVLModel._verify_forward on inference_params.DraftRows), ops.draft_verify, DraftRows.keep(n_emit);
+    then ops.ngram_draft for the next iteration, queued before the copy.  Stops: an emitted eos id, or max_new_tokens.
+
+    The emitted tokens are the greedy choice on the pass's own logits: a pass's arithmetic is the shared-prefix step's, not the
+    batch-1 step's, so at a near-tie the output can differ from the plain loop's, as transformers' assisted generation can.
+
+    draft_source(history: list of ints) -> list of ints replaces the n-gram rule (a host callable: the tests force acceptance
+    patterns with it; a draft model would plug in here).  stats, a dict, receives iterations / passes / steps and, per
+    iteration, the drafts offered and the tokens emitted.  An iteration is one step or pass of the model behind the prefill: the FIRST
+    token, chosen from first_logits, is not one, so N tokens with always-wrong drafts are N - 1 iterations of one emitted token."""
+    from . import ops
+    from .inference_params import DraftRows
+    k, G = int(num_draft), int(max_ngram)
+    if not LOOKUP_MIN <= k <= LOOKUP_MAX:
+        raise ValueError(f"prompt_lookup_num_tokens must be {LOOKUP_MIN} .. {LOOKUP_MAX}, got {k}")
+    if G < 1:
+        raise ValueError("max_matching_ngram_size must be >= 1")
+    if ids.dim() != 2 or ids.shape[0] != 1:
+        raise ValueError("generate_with_lookup runs batch 1")
+    n_new = int(max_new_tokens)
+    ip = forward_step.inference_params
+    rows = DraftRows(ip, k + 1)                                 # refuses an FP8 cache, beam state, an empty cache: nothing is launched
+    dev, s = ids.device, ids.shape[1]
+    if stats is None:
+        stats = {}
+    stats.update(iterations=0, passes=0, steps=0, offered=[], emitted=[])
+    if n_new < 1:
+        return ids.clone()
+    vocab = first_logits.shape[-1]
+    if bool(((ids < 0) | (ids >= vocab)).any()):                # a draft is a token of the history and is embedded unchecked
+        raise IndexError("generate_with_lookup: token id out of range")
+    cap_hist = s + n_new
+    hist = torch.zeros(cap_hist, dtype=torch.int64, device=dev)
+    hist[:s] = ids[0]
+    n_hist = torch.full((1,), s, dtype=torch.int32, device=dev)
+    seen = None
+    if repetition_penalty != 1.0:
+        seen = torch.zeros(1, vocab, dtype=torch.uint8, device=dev)
+        ops.token_seen_mark_(seen, ids)
+    eos_list = sorted(int(e) for e in eos)
+    eos_dev = torch.tensor(eos_list, dtype=torch.int64, device=dev) if eos_list else None
+    # what the host reads per iteration, in one copy: record [10] = {n_emit, stop, emitted[8]}, then the next draft count (int32)
+    back = torch.zeros(12, dtype=torch.int64, device=dev)
+    record, n_draft = back[:10], back[10:11].view(torch.int32)[:1]
+    draft = torch.full((LOOKUP_MAX,), -1, dtype=torch.int64, device=dev)
+    host_hist = ids[0].tolist() if draft_source is not None else None
+
+    def next_draft():
+        """Queue the drafts of the next iteration behind what was just appended."""
+        if draft_source is None:
+            ops.ngram_draft(hist, n_hist, G, k, cap_hist, eos_dev, draft_out=draft[:k], n_draft_out=n_draft)
+
+    def read_back():
+        got = back.cpu()                                        # the iteration's one copy to the host
+        rec = got[:10].tolist()
+        nd = int(got[10:11].view(torch.int32)[0])
+        emitted = rec[2: 2 + rec[0]]
+        if draft_source is not None:
+            host_hist.extend(emitted)
+            d = [int(v) for v in draft_source(list(host_hist))][:k]
+            if any(not 0 <= v < vocab for v in d):
+                raise IndexError("draft_source: token id out of range")
+            nd = len(d)
+            if nd:
+                draft[:nd] = torch.tensor(d, dtype=torch.int64)
+        return emitted, bool(rec[1]), nd
+
+    def plain(logits):
+        """The token of one row of logits [1, V], chosen, appended and recorded as a pass of one emitted token."""
+        tok = ops.select_token(logits, seen=seen, repetition_penalty=repetition_penalty, mark_chosen=seen is not None)
+        record[2:3].copy_(tok)
+        n = s + generated
+        hist[n: n + 1].copy_(tok)
+        n_hist.fill_(n + 1)
+        next_draft()
+        emitted, _, nd = read_back()
+        return emitted, emitted[0] in eos_list, nd
+
+    generated = 0
+    record.fill_(-1)
+    record[0], record[1] = 1, 0
+    logits = first_logits if first_logits.dtype == torch.bfloat16 else first_logits.to(torch.bfloat16)
+    emitted, stop, nd = plain(logits.reshape(1, vocab).contiguous())
+    generated += 1
+    while not stop and generated < n_new:
+        stats["iterations"] += 1
+        n = s + generated                                       # the history's length; its last token is not in the cache yet
+        L = ip.local_len
+        t = 1 + min(nd, n_new - generated - 1, rows.capacity - L - 1)
+        stats["offered"].append(max(t - 1, 0))
+        if t < 2:
+            stats["steps"] += 1
+            record.fill_(-1)
+            record[0], record[1] = 1, 0
+            pos = torch.full((1, 1), ip.sequence_len_offset, dtype=torch.long, device=dev)
+            logits = forward_step(hist[n - 1: n][None], pos, None)[:, -1, :]
+            emitted, stop, nd = plain(logits)
+            generated += 1
+            stats["emitted"].append(1)
+            continue
+        stats["passes"] += 1
+        rows.prepare(t)
+        tokens_in = torch.cat([hist[n - 1: n], draft[: t - 1]])[None]
+        pos = torch.arange(ip.sequence_len_offset, ip.sequence_len_offset + t, dtype=torch.long, device=dev)[None]
+        logits = model(tokens_in, pos, None, inference_params=rows)                       # [1, t, V]
+        ops.draft_verify(logits[0], draft, hist, n_hist, seen=seen, repetition_penalty=repetition_penalty, eos=eos_dev, record=record)
+        next_draft()
+        emitted, stop, nd = read_back()
+        rows.keep(len(emitted))
+        generated += len(emitted)
+        stats["emitted"].append(len(emitted))
+    return hist[: s + generated][None].clone()
+
+
+# ------------------------------------------------------------------------------------------------
 # beam search on a shared-prefix KV cache (:283-471)
 # ------------------------------------------------------------------------------------------------
 BEAM_MIN, BEAM_MAX = 2, 8

@@ -20,7 +20,7 @@ import torch
 
 from . import context_parallel, ops, parallel_state as mpu, tracing, training_utils
 from .dot_product_attention import DotProductAttention
-from .inference_params import DecodeBatch, SharedPrefixBatch, check_decode_weight_dtype, check_kv_cache_dtype
+from .inference_params import DecodeBatch, DraftRows, SharedPrefixBatch, check_decode_weight_dtype, check_kv_cache_dtype
 from .language_model_embedding import LanguageModelEmbedding
 from .layers import ColumnParallelLinear
 from .rotary_pos_embedding import RotaryEmbedding
@@ -322,6 +322,8 @@ class GPTVLModel:
         ip = inference_params
         if isinstance(ip, DecodeBatch):
             return self._batch_forward(input_ids, position_ids, ip)
+        if isinstance(ip, DraftRows):
+            return self._verify_forward(input_ids, position_ids, ip)
         if isinstance(ip, SharedPrefixBatch):
             if ip.pass_segments is not None:             # extend_rows prepared a ragged pass
                 return self._prefix_extend_forward(input_ids, position_ids, ip)
@@ -644,6 +646,8 @@ class GPTVLModel:
         if g is None:
             ip._graph_weights = self._w8_layers()               # the copies the capture reads, quantised outside it
             dev = token.device
+            # "row" / "len" are the capture's record of the cache length: inference_params.set_graph_length moves them when rows
+            # are committed or rolled back outside the capture (DraftRows.keep); keep their names and dtypes in step with it
             st = {"tok": torch.zeros(1, dtype=torch.int64, device=dev),
                   "pos": torch.zeros(1, dtype=torch.int64, device=dev),
                   "row": torch.full((1,), ip.local_len, dtype=torch.int64, device=dev),
@@ -893,6 +897,46 @@ class GPTVLModel:
                                   batch.lens, batch.tail_cap, out=out)
 
         return self._rows_token(tokens, position, append, attend, batch.advance)
+
+    def _verify_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], rows: DraftRows) -> torch.Tensor:
+        """The verify pass of speculative decoding (inference_params.DraftRows): tokens [1, t], t = 2 .. 8 CONSECUTIVE tokens of one
+        request — its last chosen token and t - 1 drafts — in ONE multi-row step.  _rows_token with row i's K / V appended to the
+        cache's own row L + i (ops.rope_append_rows through the static table) and ops.prefix_batch_attn over the cache rows [0, L),
+        read once for all rows, and a tail that starts at row L of the cache itself, row i seeing i + 1 rows of it.  The head runs on
+        all t rows.  Returns logits [1, t, vocab]; nothing is committed: DraftRows.keep(n) does that once the caller knows how many
+        rows stay, and a captured token step is left alone.  The decoder weights are whatever decode_weight_dtype says.  CP = 1
+        and TP = 1."""
+        c = self.cfg
+        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.force_cp_path:
+            raise NotImplementedError("the verify pass is built for CP = 1 and TP = 1")
+        if input_ids.dim() != 2 or input_ids.shape[0] != 1:
+            raise ValueError("the verify pass takes tokens [1, t]")
+        t = input_ids.shape[1]
+        if rows.t is None:
+            rows.prepare(t)                                      # raises before any launch when t is out of range or the cache is full
+        if rows.t != t:
+            raise ValueError(f"the prepared pass takes tokens [1, {rows.t}]")
+        L, ip = rows.prefix_len, rows.ip
+        if position_ids is None:
+            position = torch.arange(ip.sequence_len_offset, ip.sequence_len_offset + t, dtype=torch.long, device=input_ids.device)
+        elif tuple(position_ids.shape) != (1, t):
+            raise ValueError(f"the verify pass takes positions [1, {t}]")
+        else:
+            position = position_ids[0].contiguous()
+        rows.consumed_tokens = t
+        ptrs, tails = rows.kv_ptrs.unbind(0), rows.tail_ptrs.unbind(0)
+        append_rows, tail_lens, caps = rows.append_rows[:t], rows.tail_lens[:t], rows.caps[:t]
+
+        def append(li, qkv, cos, sin):
+            ops.rope_append_rows(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ptrs[li][:t], rows.kv_row_stride, rows.kv_group_stride,
+                                 append_rows, caps)
+
+        def attend(li, q, out):
+            kv = ip.key_value_memory_dict[li + 1]
+            ops.prefix_batch_attn(q, kv[0], kv[1], L, tails[li][:t], rows.kv_row_stride, rows.kv_group_stride, tail_lens, t, out=out)
+
+        h = self._rows_token(input_ids[0].contiguous(), position, append, attend, lambda: None)
+        return self._head(h).transpose(0, 1).contiguous()                                   # [1, t, vocab]
 
     def _prefix_extend_forward(self, input_ids: torch.Tensor, position_ids: Optional[torch.Tensor], batch: SharedPrefixBatch) -> torch.Tensor:
         """The rows' own prompt tokens behind the shared prefix in ONE pass (what the reference's loop teacher-forces one token per

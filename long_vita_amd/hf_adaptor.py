@@ -346,7 +346,12 @@ class LongVITAForCausalLM:
         behind cache.get_seq_length() are fed, in one extend step, then one cached step per token.  return_dict_in_generate: an object
         with `sequences` and `past_key_values` (the cache holds everything but the last generated token, as transformers' does).
         kv_cache_dtype: "bf16" or "fp8_e4m3" for the cache this call allocates (None: self.kv_cache_dtype); a cache handed in keeps
-        its own format.  There is no beam search on an FP8 cache: num_beams > 1 raises NotImplementedError there."""
+        its own format.  There is no beam search on an FP8 cache: num_beams > 1 raises NotImplementedError there.
+        prompt_lookup_num_tokens=k (1 .. 7; a keyword or a generation_config attribute, with max_matching_ngram_size, default 2):
+        transformers' prompt-lookup decoding — up to k tokens that followed an earlier occurrence of the last n-gram are verified
+        together with the next token in one step of the model (_generate_lookup, generation.generate_with_lookup; greedy, bf16
+        cache, CP = 1, TP = 1).  Absent or None: nothing changes.  draft_source=callable(history) -> drafts replaces the n-gram rule.  With
+        return_dict_in_generate the object also carries `lookup_stats` (generation.generate_with_lookup's stats of this call)."""
         cache_dtype = check_kv_cache_dtype(kv_cache_dtype, allow_none=True) or self.kv_cache_dtype
         if cache_dtype != "bf16" and int(kwargs.get("num_beams") or 1) > 1:
             raise NotImplementedError("beam search on an FP8 KV cache is not built")
@@ -355,11 +360,15 @@ class LongVITAForCausalLM:
             raise ValueError("generate(inputs=[1, S] token ids) — the Long-VITA path runs batch 1")
         gc = generation_config or self.generation_config
         n_new = max_new_tokens if max_new_tokens is not None else (_get(gc, "max_new_tokens") or 20)
+        lookup = self._lookup_params(gc, kwargs)                # None: the keyword is absent and nothing below changes
         penalty, do_sample, temperature, top_k, top_p = selection_params(gc, do_sample)
         eos = eos_token_id if eos_token_id is not None else _get(gc, "eos_token_id")
         eos = set() if eos is None else set(eos) if isinstance(eos, (list, tuple, set)) else {int(eos)}
         ids = ids.to(self.device)
         s = ids.shape[1]
+        if lookup is not None:
+            return self._generate_lookup(ids, images, image_indices, past_key_values, n_new, eos, penalty, do_sample, lookup,
+                                         return_dict_in_generate, kv_cache_dtype, kwargs.get("draft_source"))
         select = None
         if penalty != 1.0 or do_sample:
             if self.device_select and os.environ.get("VITA_DEVICE_SELECT", "1") != "0":
@@ -384,6 +393,61 @@ class LongVITAForCausalLM:
             if int(out[0, -1]) in eos:
                 break
         return out.clone()
+
+    @staticmethod
+    def _lookup_params(gc, kwargs):
+        """(prompt_lookup_num_tokens, max_matching_ngram_size) of transformers' prompt-lookup decoding, a keyword of generate() or an
+        attribute of the generation config (the keyword wins); None when prompt_lookup_num_tokens is absent or None.  Pure host code."""
+        k = kwargs["prompt_lookup_num_tokens"] if kwargs.get("prompt_lookup_num_tokens") is not None else _get(gc, "prompt_lookup_num_tokens")
+        if k is None:
+            return None
+        if isinstance(k, bool) or int(k) != k or not generation.LOOKUP_MIN <= int(k) <= generation.LOOKUP_MAX:
+            raise ValueError(f"prompt_lookup_num_tokens must be an integer in {generation.LOOKUP_MIN} .. {generation.LOOKUP_MAX} "
+                             f"(a verify pass holds at most 8 rows), got {k!r}")
+        g = kwargs["max_matching_ngram_size"] if kwargs.get("max_matching_ngram_size") is not None else _get(gc, "max_matching_ngram_size")
+        g = 2 if g is None else g                              # transformers' default
+        if isinstance(g, bool) or int(g) != g or int(g) < 1:
+            raise ValueError(f"max_matching_ngram_size must be an integer >= 1, got {g!r}")
+        beams = kwargs["num_beams"] if kwargs.get("num_beams") is not None else _get(gc, "num_beams")
+        if int(beams or 1) > 1:
+            raise ValueError("prompt_lookup_num_tokens is greedy decoding at batch 1: num_beams > 1 cannot be combined with it")
+        return int(k), int(g)
+
+    def _generate_lookup(self, ids, images, image_indices, cache, n_new, eos, penalty, do_sample, lookup, return_dict, kv_cache_dtype,
+                         draft_source=None):
+        """generate(prompt_lookup_num_tokens=k): the uncached part of `ids` in one call, as _generate_cached feeds it, then
+        generation.generate_with_lookup on that cache.  Every refusal is raised before anything is launched."""
+        from . import parallel_state as mpu
+        if do_sample:
+            raise NotImplementedError("prompt_lookup_num_tokens with do_sample=True (speculative sampling) is not built")
+        if penalty != 1.0 and not (self.device_select and os.environ.get("VITA_DEVICE_SELECT", "1") != "0"):
+            raise NotImplementedError("repetition_penalty needs the device selection (model.device_select / VITA_DEVICE_SELECT)")
+        if mpu.get_context_parallel_world_size() != 1 or mpu.get_tensor_model_parallel_world_size() != 1 or self.model.force_cp_path:
+            raise NotImplementedError("prompt_lookup_num_tokens is built for CP = 1 and TP = 1")
+        if cache is not None and not isinstance(cache, HipCache):
+            raise TypeError("past_key_values must come from this model's own forward(use_cache=True) / generate(return_dict_in_generate=True)")
+        cached = cache is not None and len(cache) > 0
+        fp8 = cache.step.inference_params.kv_cache_is_fp8 if cached else \
+            (check_kv_cache_dtype(kv_cache_dtype, allow_none=True) or self.kv_cache_dtype) != "bf16"
+        if fp8:
+            raise NotImplementedError("prompt_lookup_num_tokens on an FP8 KV cache is not built (the verify pass reads a bf16 cache)")
+        s = ids.shape[1]
+        if cached:
+            seen = cache.get_seq_length()
+            if s <= seen:
+                raise ValueError(f"generate(past_key_values=): inputs hold {s} tokens, the cache already {seen} — pass the whole conversation "
+                                 "with at least one token the cache has not seen (its logits start the answer)")
+            out = self.forward(input_ids=ids[:, seen:], past_key_values=cache, num_logits_to_keep=1)
+        else:
+            out = self.forward(input_ids=ids, images=images, image_indices=image_indices, use_cache=True, num_logits_to_keep=1,
+                               kv_cache_dtype=kv_cache_dtype)
+        cache = out.past_key_values
+        self._grow_cache(cache.step.inference_params, n_new)    # the pass's tables hold the cache's addresses: grow first
+        stats = {}                                              # iterations / passes / steps, drafts offered and tokens emitted per iteration
+        seq = generation.generate_with_lookup(self.model, cache.step, out.logits[:, -1, :], ids, n_new, num_draft=lookup[0],
+                                              max_ngram=lookup[1], eos=eos, repetition_penalty=penalty, draft_source=draft_source,
+                                              stats=stats)
+        return types.SimpleNamespace(sequences=seq, past_key_values=cache, lookup_stats=stats) if return_dict else seq
 
     def _device_selector(self, ids, n_new, penalty, do_sample, temperature, top_k, top_p):
         """The per-token choice on the device.  The byte map of tokens already in the row starts from the WHOLE `ids` (the prompt with its

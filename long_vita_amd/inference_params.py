@@ -336,6 +336,124 @@ class SharedPrefixBatch(_RowSteps):
         super().advance()
 
 
+def set_graph_length(ip) -> None:
+    """Move the captured token step of `ip` (GPTVLModel._decode_graphed: ip._graph = (graph, st)) to ip.local_len without dropping
+    the capture: st["row"] (int64 [1], the row the next token is appended to) and st["len"] (int32 [1], the rows it then attends
+    to) are the capture's only record of the cache length.  No capture: nothing to do."""
+    g = getattr(ip, "_graph", None)
+    if g is not None:
+        st = g[1]
+        st["row"].fill_(ip.local_len)
+        st["len"].fill_(ip.local_len + 1)
+
+
+DRAFT_ROWS_MIN, DRAFT_ROWS_MAX = 2, BATCH_MAX            # rows of one verify pass: the last token and 1 .. 7 drafts
+
+
+class DraftRows:
+    """The verify pass of speculative decoding on ONE prefilled batch-1 request (GPTVLModel._verify_forward; CP = 1, TP = 1, bf16
+    cache): t = 2 .. max_rows consecutive tokens of the SAME request — the last chosen token and t - 1 drafts — go through the model
+    in one multi-row step.  Row i is appended to the cache's own row L + i and attends to the rows [0, L), read once for all rows,
+    and to the rows [L, L + i]: tail lengths 1 .. t over one shared tail are a causal chain.  No K / V is copied and no second cache
+    exists.
+
+    kv_ptrs [layers, max_rows, 2] (int64 on the device, built once: every row names the cache's own K / V base) and caps [max_rows]
+    (the capacity) are the table ops.rope_append_rows takes.  prepare(t) sets, for L = ip.local_len, append_rows[i] = L + i,
+    tail_lens[i] = i + 1 and tail_ptrs[layer, i] = base + L * row_stride (16-byte aligned: the strides are multiples of 8
+    elements) in ONE host-to-device upload; it raises the cache-full error before any launch.  keep(n) commits the first n >= 1
+    rows of the pass: local_len = L + n, sequence_len_offset / decode_steps move by n; the rows behind are stale and the next pass or
+    step overwrites them.  keep does NOT drop a captured token step: it sets the capture's two device counters to the new length."""
+
+    def __init__(self, ip, max_rows: int = DRAFT_ROWS_MAX):
+        if not isinstance(ip, InferenceParams):
+            raise ValueError("DraftRows: the request is the InferenceParams of a prefilled batch-1 request")
+        if ip.kv_cache_is_fp8:
+            raise NotImplementedError("a verify pass on an FP8 KV cache is not built (the prefix attention reads a bf16 cache)")
+        if ip.beams is not None:
+            raise ValueError("DraftRows: the request holds beam state")
+        if not ip.key_value_memory_dict or ip.local_len < 1:
+            raise ValueError("DraftRows: the request is the InferenceParams of a prefilled batch-1 request (its cache is empty)")
+        max_rows = int(max_rows)
+        if not DRAFT_ROWS_MIN <= max_rows <= DRAFT_ROWS_MAX:
+            raise ValueError(f"DraftRows takes max_rows = {DRAFT_ROWS_MIN} .. {DRAFT_ROWS_MAX}, got {max_rows}")
+        self.layer_numbers = list(ip.key_value_memory_dict)
+        kv0 = ip.key_value_memory_dict[self.layer_numbers[0]]
+        for kv in ip.key_value_memory_dict.values():
+            if kv.dtype != torch.bfloat16:
+                raise ValueError("DraftRows: the cache must be bf16")
+            if kv.dim() != 4 or kv.shape[0] != 2 or kv.shape != kv0.shape or kv.stride(3) != 1 or kv.stride() != kv0.stride() \
+                    or kv.device != kv0.device or kv.stride(1) % 8 or kv.stride(2) % 8:
+                raise ValueError("DraftRows: the layers' caches must be [2, capacity, kv groups, head_dim] with the same strides, "
+                                 "multiples of 8 elements")
+        if ip.local_len > kv0.shape[1]:
+            raise ValueError("DraftRows: the request holds more tokens than its cache has rows")
+        self.ip, self.max_rows = ip, max_rows
+        self.device = kv0.device
+        self.capacity = kv0.shape[1]
+        self.kv_row_stride, self.kv_group_stride = kv0.stride(1), kv0.stride(2)
+        layers = len(self.layer_numbers)
+        self._bases = [[ip.key_value_memory_dict[ln][0].data_ptr(), ip.key_value_memory_dict[ln][1].data_ptr()] for ln in self.layer_numbers]
+        table = [[base] * max_rows for base in self._bases]
+        self.kv_ptrs = torch.tensor(table, dtype=torch.int64).to(self.device)             # [layers, max_rows, 2]
+        self.caps = torch.full((max_rows,), self.capacity, dtype=torch.int32).to(self.device)
+        # one upload per pass: the tail table [layers, max_rows, 2] int64, then append_rows and tail_lens as int32 [2, max_rows]
+        self._n_tail = layers * max_rows * 2
+        self._pass = torch.zeros(self._n_tail + max_rows, dtype=torch.int64, device=self.device)
+        # the host image of that upload, built once: prepare() is one add and two selects on it, no Python per layer or row
+        self._host = torch.zeros(self._n_tail + max_rows, dtype=torch.int64)
+        self._host_bases = torch.tensor(table, dtype=torch.int64).view(-1)
+        self._host_rows = self._host[self._n_tail:].view(torch.int32).view(2, max_rows)
+        self._iota = torch.arange(max_rows, dtype=torch.int32)
+        self.tail_ptrs = self._pass[: self._n_tail].view(layers, max_rows, 2)
+        rows32 = self._pass[self._n_tail:].view(torch.int32).view(2, max_rows)
+        self.append_rows, self.tail_lens = rows32[0], rows32[1]
+        self.t = None                        # the rows of the prepared pass; None: no pass is prepared
+        self.prefix_len = 0                  # L of the prepared pass
+        self.consumed_tokens = None
+        self.use_kv_cache = True
+
+    @property
+    def sequence_len_offset(self):
+        return self.ip.sequence_len_offset
+
+    def prepare(self, t: int) -> int:
+        """Prepare a pass of t rows behind the L = ip.local_len rows stored; returns L."""
+        t = int(t)
+        if not DRAFT_ROWS_MIN <= t <= self.max_rows:
+            raise ValueError(f"a verify pass takes {DRAFT_ROWS_MIN} .. {self.max_rows} rows, got {t}")
+        L = int(self.ip.local_len)
+        if L < 1:
+            raise ValueError("DraftRows: the cache is empty")
+        if L + t > self.capacity:
+            raise RuntimeError("KV cache shard is full (max_sequence_length reached)")
+        torch.add(self._host_bases, L * self.kv_row_stride * 2, out=self._host[: self._n_tail])     # bytes: bf16 rows
+        live = self._iota < t
+        self._host_rows[0] = torch.where(live, self._iota + L, -1)
+        self._host_rows[1] = torch.where(live, self._iota + 1, 0)
+        host = self._host
+        self._upload(host)
+        self.t, self.prefix_len = t, L
+        return L
+
+    def _upload(self, host):
+        self._pass.copy_(host)                                  # host -> device; nothing is read back
+
+    def keep(self, n: int) -> int:
+        """Commit the first n rows of the pass that ran; returns the new length."""
+        n = int(n)
+        if self.t is None:
+            raise ValueError("keep: no pass is prepared")
+        if not 1 <= n <= self.t:
+            raise ValueError(f"keep: 1 .. {self.t} rows of the pass can stay, got {n}")
+        ip = self.ip
+        ip.local_len = self.prefix_len + n
+        ip.sequence_len_offset += n
+        ip.decode_steps += n
+        set_graph_length(ip)                                    # a captured token step is kept: its device counters follow
+        self.t = None
+        return ip.local_len
+
+
 class ForwardStep:
     """M/inference/text_generation/forward_step.py (ForwardStep.__init__ wrapper :27-39 and
     _no_pipelining_forward_step :42-57): owns the InferenceParams, calls the model, advances

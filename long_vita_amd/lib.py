@@ -176,6 +176,10 @@ PROTOTYPES = {
     "vita_token_seen_mark": (_i, [_p, _l, _p, _l, _p, _p]),
     "vita_select_token_workspace_bytes": (_l, [_l, _l]),
     "vita_select_token": (_i, [_p, _l, _l, _l, _p, _f, _i, _f, _i, _f, _p, _p, _p, _i, _p, _l, _p]),
+    # prompt-lookup speculative decoding (tools/inference_long_vita.py:820-826,868)
+    "vita_ngram_draft_workspace_bytes": (_l, [_l]),
+    "vita_ngram_draft": (_i, [_p, _l, _p, _i, _i, _l, _p, _i, _p, _p, _p, _l, _p]),
+    "vita_draft_verify": (_i, [_p, _l, _i, _l, _p, _f, _p, _p, _i, _p, _l, _p, _p, _p]),
     "vita_rope_table": (_i, [_p, _p, _p, _p, _l, _i, _p]),
     "vita_rope_cos_sin": (_i, [_p, _l, _p, _p, _l, _i, _p]),
     "vita_rope_apply": (_i, [_p, _l, _i, _i, _l, _l, _p, _p, _i, _p]),

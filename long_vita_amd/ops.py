@@ -1752,6 +1752,73 @@ def select_token(logits: torch.Tensor, *, seen: Optional[torch.Tensor] = None, r
     return (token, kept) if return_kept else token
 
 
+# ------------------------------------------------------------------------------------------------
+# prompt-lookup speculative decoding (include/vita_hip.h: vita_ngram_draft, vita_draft_verify)
+# ------------------------------------------------------------------------------------------------
+DRAFT_MAX = 7                            # drafts of one verify pass: 1 + DRAFT_MAX rows = BEAM_MAX
+
+
+def _lookup_common(hist: torch.Tensor, n_hist: torch.Tensor, eos: Optional[torch.Tensor], what: str):
+    if hist.dtype != torch.int64 or hist.dim() != 1 or not hist.is_contiguous():
+        raise ValueError(f"{what}: hist must be contiguous int64 [hist_cap]")
+    if n_hist.dtype != torch.int32 or n_hist.numel() != 1:
+        raise ValueError(f"{what}: n_hist must be one int32 on the device")
+    if eos is not None and (eos.dtype != torch.int64 or eos.dim() != 1 or not eos.is_contiguous()):
+        raise ValueError(f"{what}: eos must be contiguous int64 [n_eos]")
+    n_eos = 0 if eos is None else eos.numel()
+    return n_eos, (_dev(eos, "eos") if n_eos else None)
+
+
+def ngram_draft(hist: torch.Tensor, n_hist: torch.Tensor, max_ngram: int, num_draft: int, max_total: int,
+                eos: Optional[torch.Tensor] = None, draft_out: Optional[torch.Tensor] = None, n_draft_out: Optional[torch.Tensor] = None):
+    """The prompt-lookup candidate of the device history hist[0, *n_hist) (int64 [hist_cap]; n_hist one int32 on the device): the up to
+    num_draft <= 7 tokens that followed the leftmost earlier occurrence of the longest trailing n-gram of at most max_ngram tokens, as
+    transformers' PromptLookupCandidateGenerator.get_candidates picks them (include/vita_hip.h: vita_ngram_draft).  Returns
+    (draft_out int64 [num_draft], unused slots -1; n_draft_out int32 [1]).  Nothing here synchronises with the host."""
+    n_eos, eos_ptr = _lookup_common(hist, n_hist, eos, "ngram_draft")
+    k = int(num_draft)
+    if draft_out is None:
+        draft_out = torch.empty(max(k, 0), dtype=torch.int64, device=hist.device)
+    if n_draft_out is None:
+        n_draft_out = torch.empty(1, dtype=torch.int32, device=hist.device)
+    if draft_out.dtype != torch.int64 or draft_out.numel() != max(k, 0) or not draft_out.is_contiguous():
+        raise ValueError("ngram_draft: draft_out must be contiguous int64 [num_draft]")
+    if n_draft_out.dtype != torch.int32 or n_draft_out.numel() != 1:
+        raise ValueError("ngram_draft: n_draft_out must be one int32")
+    h = _L.load()
+    nbytes = h.vita_ngram_draft_workspace_bytes(hist.numel())
+    ws = _workspace(nbytes, hist.device)
+    _L.check(h.vita_ngram_draft(_dev(hist, "hist"), hist.numel(), _dev(n_hist, "n_hist"), int(max_ngram), k, int(max_total), eos_ptr, n_eos,
+                                _dev(draft_out, "draft_out"), _dev(n_draft_out, "n_draft_out"), _dev(ws, "workspace"), nbytes, _stream()),
+             "vita_ngram_draft")
+    return draft_out, n_draft_out
+
+
+def draft_verify(logits: torch.Tensor, draft: torch.Tensor, hist: torch.Tensor, n_hist: torch.Tensor, *, seen: Optional[torch.Tensor] = None,
+                 repetition_penalty: float = 1.0, eos: Optional[torch.Tensor] = None, record: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The greedy acceptance of one verify pass (include/vita_hip.h: vita_draft_verify): bf16 logits [t, V] of the rows fed
+    [last token, draft[0 .. t - 2]], t = 2 .. 8; `seen` one row of the byte map select_token reads ([V] or [1, V] uint8) or None.  Row i's
+    token is select_token's greedy choice with seen U draft[:i] penalised; the tokens up to and including the first row that disagrees
+    with its draft are emitted (cut behind an eos id), appended to hist / n_hist and marked in `seen`.  Returns record int64 [t + 2] =
+    {n_emit, stop, emitted tokens, -1 ...} on the device.  Nothing here synchronises with the host."""
+    if logits.dim() != 2 or logits.stride(1) != 1:
+        raise ValueError("logits must be [t, V] with unit column stride")
+    t, cols = logits.shape
+    n_eos, eos_ptr = _lookup_common(hist, n_hist, eos, "draft_verify")
+    if draft.dtype != torch.int64 or draft.dim() != 1 or draft.numel() < t - 1 or not draft.is_contiguous():
+        raise ValueError("draft_verify: draft must be contiguous int64 with at least t - 1 ids")
+    if seen is not None and (seen.dtype != torch.uint8 or not seen.is_contiguous() or seen.numel() != cols):
+        raise ValueError("seen must be one contiguous row of uint8 [V]")
+    if record is None:
+        record = torch.empty(t + 2, dtype=torch.int64, device=logits.device)
+    if record.dtype != torch.int64 or record.numel() < t + 2 or not record.is_contiguous():
+        raise ValueError("draft_verify: record must be contiguous int64 with at least t + 2 slots")
+    _L.check(_L.load().vita_draft_verify(_dev(logits, "logits", BF16), logits.stride(0), t, cols, _opt(seen, "seen"), float(repetition_penalty),
+                                         _dev(draft, "draft"), eos_ptr, n_eos, _dev(hist, "hist"), hist.numel(), _dev(n_hist, "n_hist"),
+                                         _dev(record, "record"), _stream()), "vita_draft_verify")
+    return record
+
+
 def add(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out = bf16(a + b) (out may alias a): one pass, no copy of either operand."""
     if a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous():
