@@ -345,7 +345,8 @@ int vita_flash_attn_fwd_window(const vita_attn_params* p, const int32_t* q_tiles
  *   q: t rows read in place from the mixed QKV activation: head j of kv group g of row i at q + i * q_row_stride + g * q_group_stride
  *      + j * q_head_stride.  k_cache / v_cache: rows [0, n_keys) of a cache shard [rows][n_kv_heads][128] (row / group strides in
  *      elements, shared by K and V); rows behind n_keys are never read.  out [t][n_q_heads][128] through its strides; lse (optional)
- *      fp32 [n_q_heads][t], natural log.  head_dim 128 only; every stride a multiple of 8 elements (else VITA_ERR_UNSUPPORTED).
+ *      fp32 [n_q_heads][t], natural log.  head_dim 128 only; q / k_cache / v_cache / out 16-byte aligned, every stride a multiple of
+ *      8 elements, lse 4-byte aligned (else VITA_ERR_UNSUPPORTED).
  *   Visibility by position: query row i sits at q_pos0 + i.  Keys [0, n_full) are visible to every row; key k >= n_full sits at
  *      key_pos0 + (k - n_full) * key_pos_step and is visible iff that position <= the row's.  One device, one cache: n_full = the
  *      cached length L, key_pos0 = q_pos0 = L, step 1; step > 1 describes a round-robin shard of the appended rows.  A row that sees no

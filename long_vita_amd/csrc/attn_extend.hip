@@ -512,6 +512,7 @@ extern "C" int vita_flash_attn_extend_fwd(const vita_attn_extend_params* p, void
   if (p->kv_row_stride * KVT > 0x7fffffffLL) return VITA_ERR_UNSUPPORTED;   // 32-bit lane offsets inside a tile
   const uintptr_t bases = (uintptr_t)p->q | (uintptr_t)p->k_cache | (uintptr_t)p->v_cache | (uintptr_t)p->out;
   if (bases & 15) return VITA_ERR_UNSUPPORTED;         // 16-byte vector loads / LDS-DMA pieces start at the bases
+  if ((uintptr_t)p->lse & 3) return VITA_ERR_UNSUPPORTED;   // word stores
 
   ExtArgs a;
   a.q = (const bf16_t*)p->q; a.q_rs = p->q_row_stride; a.q_gs = p->q_group_stride; a.q_hs = p->q_head_stride;

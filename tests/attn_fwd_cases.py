@@ -458,32 +458,39 @@ def ulp_distance(a, b):
     return torch.where(torch.isnan(a.float()) | torch.isnan(b.float()), torch.full_like(d, 1 << 20), d)
 
 
-def check_outputs(case, ref, o, lse, rows=None):
-    """None, or what is wrong with o bf16 [B, Sq, Hq, D] and lse fp32 [B, Hq, Sq] on `rows` (bool [Sq]; default all):
-    up / down rows bit-equal; every other row within one bf16 step, bit-equal where the weight sum is a power of two, at most
-    DIFF_CAP of the case's elements off at all; lse within LSE_TOL max(1, |lse|)."""
-    Sq = n_q_rows(case)
-    rows = torch.ones(Sq, dtype=torch.bool) if rows is None else rows
+def check_rows(ref, o, lse, rows, kind_of):
+    """The checking rule itself, for any entry whose answers come as o bf16 [B, Sq, Hq, D] and lse fp32 [B, Hq, Sq] (tests/attn_extend_cases.py
+    shares it): None, or what is wrong on `rows` (bool [Sq]); kind_of(row, head) names the row's kind in the message.  A row that sees no key
+    (ref.lse == -inf) must be a zero row bit for bit (+0 for -0 passes) with lse exactly -inf."""
     dist = ulp_distance(o, ref.o)                                                     # [B, Sq, Hq, D]
     bits_differ = dist > 0        # (+0 for -0 passes: the losers' 2^-256 of an up / down row round to -0 in fp64 and are +0 in fp32)
     live = rows[None, :, None, None]
-    strict = (ref.exact.T[None, :, :, None] | ref.pow2.permute(0, 2, 1)[..., None]) & live
+    blind = torch.isinf(ref.lse) & (ref.lse < 0)                                      # [B, Hq, Sq]
+    strict = (ref.exact.T[None, :, :, None] | (ref.pow2 | blind).permute(0, 2, 1)[..., None]) & live
     bad = (bits_differ & strict) | ((dist > 1) & live)
     if bool(bad.any()):
         b, r, h, d = (int(i) for i in bad.nonzero()[0])
-        return (f"{int(bad.sum())} elements wrong; first at (batch={b}, row={r}, head={h} [{row_kinds(case, h)[r]}], col={d}): got "
+        return (f"{int(bad.sum())} elements wrong; first at (batch={b}, row={r}, head={h} [{kind_of(r, h)}], col={d}): got "
                 f"{float(o[b, r, h, d])!r}, expected {float(ref.o[b, r, h, d])!r} ({float(ref.o64[b, r, h, d])!r})")
     n_off = int(((dist > 0) & live).sum())
     if n_off > DIFF_CAP * o.numel():
         return f"{n_off} of {o.numel()} elements are one bf16 step off: more than {DIFF_CAP:.1%}"
     err = (lse.double() - ref.lse).abs()
     lim = LSE_TOL * ref.lse.abs().clamp_min(1.0)
-    bad = (~(err <= lim)) & rows[None, None, :]
+    bad = torch.where(blind, lse.double() != ref.lse, ~(err <= lim)) & rows[None, None, :]
     if bool(bad.any()):
         b, h, r = (int(i) for i in bad.nonzero()[0])
-        return (f"lse: {int(bad.sum())} rows wrong; first at (batch={b}, head={h} [{row_kinds(case, h)[r]}], row={r}): got "
+        return (f"lse: {int(bad.sum())} rows wrong; first at (batch={b}, head={h} [{kind_of(r, h)}], row={r}): got "
                 f"{float(lse[b, h, r])!r}, expected {float(ref.lse[b, h, r])!r}")
     return None
+
+
+def check_outputs(case, ref, o, lse, rows=None):
+    """None, or what is wrong with o bf16 [B, Sq, Hq, D] and lse fp32 [B, Hq, Sq] on `rows` (bool [Sq]; default all):
+    up / down rows bit-equal; every other row within one bf16 step, bit-equal where the weight sum is a power of two, at most
+    DIFF_CAP of the case's elements off at all; lse within LSE_TOL max(1, |lse|)."""
+    rows = torch.ones(n_q_rows(case), dtype=torch.bool) if rows is None else rows
+    return check_rows(ref, o, lse, rows, lambda r, h: row_kinds(case, h)[r])
 
 
 # ------------------------------------------------------------------------------------------------

@@ -65,6 +65,11 @@ def test_abi_version_unchanged(h):
     (dict(softmax_scale=0.0), lib.VITA_ERR_INVALID_ARG), (dict(softmax_scale=-0.1), lib.VITA_ERR_INVALID_ARG),
     (dict(softmax_scale=float("inf")), lib.VITA_ERR_INVALID_ARG), (dict(softmax_scale=float("nan")), lib.VITA_ERR_INVALID_ARG),
     (dict(kv_row_stride=0), lib.VITA_ERR_INVALID_ARG),
+    (dict(q_pos0=-1), lib.VITA_ERR_INVALID_ARG), (dict(key_pos0=-1), lib.VITA_ERR_INVALID_ARG),
+    (dict(q_pos0=2 ** 40 - 15), lib.VITA_ERR_UNSUPPORTED),                # q_pos0 + t = 2^40 + 1
+    (dict(t=2 ** 26), lib.VITA_ERR_UNSUPPORTED),                          # t x n_q_heads = 40 x 2^26 > 2^31 - 256
+    (dict(out_head_stride=132), lib.VITA_ERR_UNSUPPORTED),
+    (dict(lse=FAKE + 2), lib.VITA_ERR_UNSUPPORTED), (dict(lse=FAKE + 1), lib.VITA_ERR_UNSUPPORTED),      # word stores: 4-byte aligned
 ])
 def test_bad_arguments_are_refused_before_any_launch(h, over, code):
     assert h.vita_flash_attn_extend_fwd(C.byref(_params(**over)), None) == code
@@ -78,6 +83,8 @@ def test_split_launch_needs_its_workspace(h):
     assert need > 0
     assert h.vita_flash_attn_extend_fwd(C.byref(p), None) == lib.VITA_ERR_INVALID_ARG
     p.workspace, p.workspace_bytes = FAKE, need - 4
+    assert h.vita_flash_attn_extend_fwd(C.byref(p), None) == lib.VITA_ERR_INVALID_ARG
+    p.workspace, p.workspace_bytes = FAKE + 8, need                       # large enough, not 16-byte aligned
     assert h.vita_flash_attn_extend_fwd(C.byref(p), None) == lib.VITA_ERR_INVALID_ARG
     with pytest.raises(ValueError):
         lib.check(lib.VITA_ERR_INVALID_ARG, "vita_flash_attn_extend_fwd")
