@@ -619,7 +619,6 @@ bool decode_layer_args_ok(const vita_decode_layer_params* p) {
 namespace {
 // what the attention entries check of an FP8 cache, and everything they do behind the QKV GEMV: RoPE + K / V append, the split
 // attention and the merge.  c != NULL: the cache is the FP8 cache it describes (kv8.hip).
-bool w8_misaligned(const void* codes, const void* scales) { return ((uintptr_t)codes & 15) || ((uintptr_t)scales & 3); }
 bool kv8_cache_null(const vita_kv8_cache* c) { return !c || !c->k_codes || !c->v_codes || !c->k_scales || !c->v_scales; }
 bool kv8_cache_misaligned(const vita_kv8_cache* c) {
   return (c->code_row_stride & 7) || (c->code_group_stride & 7) || (((uintptr_t)c->k_codes | (uintptr_t)c->v_codes) & 7) ||
@@ -693,24 +692,6 @@ extern "C" int vita_decode_layer_attn_kv8(const vita_decode_layer_params* p, con
   return decode_layer_attn_tail(p, c, st);
 }
 
-// the same layer with FP8 weights (w8.hip): the four GEMVs read codes + scales, everything between them is unchanged
-extern "C" int vita_decode_layer_attn_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, const vita_kv8_cache* c,
-                                         void* stream) {
-  if (!decode_layer_args_ok(p) || !w || !w->qkv_codes || !w->qkv_scales || !p->ln1 || !p->qkv_b || !p->cos || !p->sin ||
-      !p->part_m || !p->part_l || !p->part_o || (c ? kv8_cache_null(c) : (!p->k_cache || !p->v_cache)))
-    return VITA_ERR_INVALID_ARG;
-  if (p->head_dim != 128 || p->heads / p->kv_groups > 8 || (p->hidden & 127) || p->len < 0 || p->len > p->capacity ||
-      p->append_row >= p->capacity || p->n_splits <= 0 || (c && kv8_cache_misaligned(c)) ||
-      w8_misaligned(w->qkv_codes, w->qkv_scales) || (((uintptr_t)p->h | (uintptr_t)p->ln1) & 15))
-    return VITA_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t qkv_out = (int64_t)(p->heads + 2 * p->kv_groups) * p->head_dim;
-  const int rc = vita_gemv_w8(p->h, w->qkv_codes, p->hidden, w->qkv_scales, p->qkv, qkv_out, p->hidden, VITA_EPI_BIAS, p->qkv_b,
-                              nullptr, p->ln1, p->eps, st);
-  if (rc != VITA_OK) return rc;
-  return decode_layer_attn_tail(p, c, st);
-}
-
 extern "C" int vita_decode_layer_mlp(const vita_decode_layer_params* p, void* stream) {
   if (!decode_layer_args_ok(p) || !p->o_w || !p->ln2 || !p->fc1_w || !p->fc2_w) return VITA_ERR_INVALID_ARG;
   if (p->head_dim != 128 || (p->hidden & 7) || (p->ffn & 7)) return VITA_ERR_UNSUPPORTED;
@@ -724,62 +705,71 @@ extern "C" int vita_decode_layer_mlp(const vita_decode_layer_params* p, void* st
   return vita_check_launch();
 }
 
-extern "C" int vita_decode_layer_mlp_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, void* stream) {
-  if (!decode_layer_args_ok(p) || !w || !w->o_codes || !w->o_scales || !w->fc1_codes || !w->fc1_scales || !w->fc2_codes ||
-      !w->fc2_scales || !p->ln2)
-    return VITA_ERR_INVALID_ARG;
-  if (p->head_dim != 128 || (p->hidden & 127) || (p->ffn & 127) || w8_misaligned(w->o_codes, w->o_scales) ||
-      w8_misaligned(w->fc1_codes, w->fc1_scales) || w8_misaligned(w->fc2_codes, w->fc2_scales) ||
-      (((uintptr_t)p->h | (uintptr_t)p->ctx | (uintptr_t)p->act | (uintptr_t)p->ln2) & 15))
-    return VITA_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-  int rc = decode_layer_merge_ranks(p, st);
-  if (rc != VITA_OK) return rc;
-  const int64_t hd = (int64_t)p->heads * p->head_dim;
-  rc = vita_gemv_w8(p->ctx, w->o_codes, hd, w->o_scales, p->h, p->hidden, hd, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr, 0.f, st);
-  if (rc != VITA_OK) return rc;
-  rc = vita_gemv_w8(p->h, w->fc1_codes, p->hidden, w->fc1_scales, p->act, p->ffn, p->hidden, VITA_EPI_SWIGLU, nullptr, nullptr,
-                    p->ln2, p->eps, st);
-  if (rc != VITA_OK) return rc;
-  return vita_gemv_w8(p->act, w->fc2_codes, p->ffn, w->fc2_scales, p->h, p->hidden, p->ffn, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr,
-                      0.f, st);
-}
+// the same layer with quantised weights (w8.hip, mx4.hip): the four GEMVs read codes + scales, everything between them is unchanged.
+// What the two entries of a format need to know of it; L = vita_w8_layer or vita_mx4_layer, which have the same fields.
+namespace {
+struct qweight_format {
+  int (*gemv)(const void* x, const void* codes, int64_t ldc_bytes, const void* scales, void* y, int64_t N, int64_t K, int epilogue,
+              const void* bias, const void* R, const void* gamma, float eps, void* stream);
+  int k_mask;                 // hidden and ffn are multiples of the K elements per scale: block - 1
+  int codes_per_byte;         // a code row of K elements is K / codes_per_byte bytes
+  uintptr_t scale_align;      // the scale pointers' alignment mask: 3 for fp32 scales, 0 for bytes, where there is none to check
+  bool misaligned(const void* codes, const void* scales) const { return ((uintptr_t)codes & 15) || ((uintptr_t)scales & scale_align); }
+};
+constexpr qweight_format kW8Weights = {vita_gemv_w8, 127, 1, 3}, kMx4Weights = {vita_gemv_mx4, 31, 2, 0};
 
-// the same layer with MXFP4 weights (mx4.hip): the _w8 entries with the four GEMVs swapped
-extern "C" int vita_decode_layer_attn_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, const vita_kv8_cache* c,
-                                          void* stream) {
+template <class L>
+int decode_layer_attn_q(const qweight_format& f, const vita_decode_layer_params* p, const L* w, const vita_kv8_cache* c, void* stream) {
   if (!decode_layer_args_ok(p) || !w || !w->qkv_codes || !w->qkv_scales || !p->ln1 || !p->qkv_b || !p->cos || !p->sin ||
       !p->part_m || !p->part_l || !p->part_o || (c ? kv8_cache_null(c) : (!p->k_cache || !p->v_cache)))
     return VITA_ERR_INVALID_ARG;
-  if (p->head_dim != 128 || p->heads / p->kv_groups > 8 || (p->hidden & 31) || p->len < 0 || p->len > p->capacity ||
-      p->append_row >= p->capacity || p->n_splits <= 0 || (c && kv8_cache_misaligned(c)) || ((uintptr_t)w->qkv_codes & 15) ||
-      (((uintptr_t)p->h | (uintptr_t)p->ln1) & 15))
+  if (p->head_dim != 128 || p->heads / p->kv_groups > 8 || (p->hidden & f.k_mask) || p->len < 0 || p->len > p->capacity ||
+      p->append_row >= p->capacity || p->n_splits <= 0 || (c && kv8_cache_misaligned(c)) ||
+      f.misaligned(w->qkv_codes, w->qkv_scales) || (((uintptr_t)p->h | (uintptr_t)p->ln1) & 15))
     return VITA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   const int64_t qkv_out = (int64_t)(p->heads + 2 * p->kv_groups) * p->head_dim;
-  const int rc = vita_gemv_mx4(p->h, w->qkv_codes, p->hidden / 2, w->qkv_scales, p->qkv, qkv_out, p->hidden, VITA_EPI_BIAS, p->qkv_b,
-                               nullptr, p->ln1, p->eps, st);
+  const int rc = f.gemv(p->h, w->qkv_codes, p->hidden / f.codes_per_byte, w->qkv_scales, p->qkv, qkv_out, p->hidden, VITA_EPI_BIAS,
+                        p->qkv_b, nullptr, p->ln1, p->eps, st);
   if (rc != VITA_OK) return rc;
   return decode_layer_attn_tail(p, c, st);
 }
 
-extern "C" int vita_decode_layer_mlp_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, void* stream) {
+template <class L>
+int decode_layer_mlp_q(const qweight_format& f, const vita_decode_layer_params* p, const L* w, void* stream) {
   if (!decode_layer_args_ok(p) || !w || !w->o_codes || !w->o_scales || !w->fc1_codes || !w->fc1_scales || !w->fc2_codes ||
       !w->fc2_scales || !p->ln2)
     return VITA_ERR_INVALID_ARG;
-  if (p->head_dim != 128 || (p->hidden & 31) || (p->ffn & 31) ||
-      (((uintptr_t)w->o_codes | (uintptr_t)w->fc1_codes | (uintptr_t)w->fc2_codes) & 15) ||
+  if (p->head_dim != 128 || (p->hidden & f.k_mask) || (p->ffn & f.k_mask) || f.misaligned(w->o_codes, w->o_scales) ||
+      f.misaligned(w->fc1_codes, w->fc1_scales) || f.misaligned(w->fc2_codes, w->fc2_scales) ||
       (((uintptr_t)p->h | (uintptr_t)p->ctx | (uintptr_t)p->act | (uintptr_t)p->ln2) & 15))
     return VITA_ERR_UNSUPPORTED;
   hipStream_t st = (hipStream_t)stream;
   int rc = decode_layer_merge_ranks(p, st);
   if (rc != VITA_OK) return rc;
   const int64_t hd = (int64_t)p->heads * p->head_dim;
-  rc = vita_gemv_mx4(p->ctx, w->o_codes, hd / 2, w->o_scales, p->h, p->hidden, hd, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr, 0.f, st);
+  const int cpb = f.codes_per_byte;
+  rc = f.gemv(p->ctx, w->o_codes, hd / cpb, w->o_scales, p->h, p->hidden, hd, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr, 0.f, st);
   if (rc != VITA_OK) return rc;
-  rc = vita_gemv_mx4(p->h, w->fc1_codes, p->hidden / 2, w->fc1_scales, p->act, p->ffn, p->hidden, VITA_EPI_SWIGLU, nullptr, nullptr,
-                     p->ln2, p->eps, st);
+  rc = f.gemv(p->h, w->fc1_codes, p->hidden / cpb, w->fc1_scales, p->act, p->ffn, p->hidden, VITA_EPI_SWIGLU, nullptr, nullptr, p->ln2,
+              p->eps, st);
   if (rc != VITA_OK) return rc;
-  return vita_gemv_mx4(p->act, w->fc2_codes, p->ffn / 2, w->fc2_scales, p->h, p->hidden, p->ffn, VITA_EPI_RESIDUAL, nullptr, p->h,
-                       nullptr, 0.f, st);
+  return f.gemv(p->act, w->fc2_codes, p->ffn / cpb, w->fc2_scales, p->h, p->hidden, p->ffn, VITA_EPI_RESIDUAL, nullptr, p->h, nullptr,
+                0.f, st);
+}
+}  // namespace
+
+extern "C" int vita_decode_layer_attn_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, const vita_kv8_cache* c,
+                                         void* stream) {
+  return decode_layer_attn_q(kW8Weights, p, w, c, stream);
+}
+extern "C" int vita_decode_layer_mlp_w8(const vita_decode_layer_params* p, const vita_w8_layer* w, void* stream) {
+  return decode_layer_mlp_q(kW8Weights, p, w, stream);
+}
+extern "C" int vita_decode_layer_attn_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, const vita_kv8_cache* c,
+                                          void* stream) {
+  return decode_layer_attn_q(kMx4Weights, p, w, c, stream);
+}
+extern "C" int vita_decode_layer_mlp_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, void* stream) {
+  return decode_layer_mlp_q(kMx4Weights, p, w, stream);
 }

@@ -1,11 +1,13 @@
 // FP8 (OCP e4m3fn) decoder weights for the cached token step: the quantiser that runs once per weight, the
-// single-token GEMV over codes + scales and its form for the 2 .. 8 rows of the multi-row steps.  The rule is the KV cache's
+// single-token GEMV over codes + scales and its form for the 2 .. 8 rows of the multi-row steps (the body MXFP4 shares: qgemv.h,
+// with the format's facts in W8Format below).  The rule is the KV cache's
 // (kv8_rule.h, tests/kv8_cases.py), applied to every run of 128 consecutive K elements of one weight row W[n, 128 b .. 128 b + 127]:
 // codes [N, K] (1 byte, row stride in bytes), scales [N, K / 128] fp32 dense, 0.516 of the bf16 bytes.  Every e4m3 value is a bf16
 // value, so the dot product is decode.hip's v_dot2_f32_bf16 on the codes; a block's scale multiplies the lane's finished 16-element
 // partial, and nothing is rounded to bf16 in front of the epilogue.
 #include "vita_common.h"
 #include "kv8_rule.h"
+#include "qgemv.h"
 
 #include <math.h>
 
@@ -40,24 +42,16 @@ __global__ __launch_bounds__(256) void w8_quantize_kernel(const bf16_t* __restri
 // scale = 26 VALU instructions, against 16 bytes every ~34 lane-cycles that HBM delivers per CU: the kernel stays HBM-bound.
 // NORM: gemv_kernel's rstd (gemv_rstd) and gemv_norm_x, so the normalised x has the bits it has on the bf16 path.
 // Rows behind N (an odd N's second row recomputes row N - 1 and stores nothing) and columns behind K are never read.
-// w8_dot16 = w8_decode16 (16 codes -> 8 packed bf16 pairs) + w8_dot16p (the eight chained dot2 from 0): gemv_rows_w8_kernel decodes a
+// w8_dot16 = w8_decode16 (16 codes -> 8 packed bf16 pairs) + qgemv_dot16p (the eight chained dot2 from 0): qgemv.h's body decodes a
 // vector once and runs the chain once per input row.
 __device__ __forceinline__ void w8_decode16(const u32x4 c, unsigned (&p)[8]) {
 #pragma unroll
   for (int j = 0; j < 4; ++j) kv8_decode4(c[j], p[2 * j], p[2 * j + 1]);
 }
-__device__ __forceinline__ float w8_dot16p(const unsigned (&p)[8], const u32x4 xa, const u32x4 xb) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s = dot2_bf16(xa[j], p[j], s);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) s = dot2_bf16(xb[j], p[4 + j], s);
-  return s;
-}
 __device__ __forceinline__ float w8_dot16(const u32x4 c, const u32x4 xa, const u32x4 xb) {
   unsigned p[8];
   w8_decode16(c, p);
-  return w8_dot16p(p, xa, xb);
+  return qgemv_dot16p(p, xa, xb);
 }
 
 template <int EPI, bool NORM>
@@ -116,116 +110,35 @@ void launch_gemv_w8(const void* x, const void* codes, int64_t ldc, const void* s
 }
 
 // ---- y[b][N] = epilogue(dequant(codes, scales)[N,K] . x[b][K]) for b < rows <= 8: the multi-row decode steps on FP8 weights --------
-// gemv_rows_kernel's promise on gemv_w8_kernel's arithmetic: a wave reads each of its code rows and their scales ONCE for all input
-// rows, decodes a 16-code vector to packed bf16 once, and every (input row, code row) pair keeps an fp32 accumulator of its own that
-// walks K exactly as gemv_w8_kernel does (lane stride 64 over the vectors, w8_dot16p from 0, acc += partial * scale, wave_reduce_sum,
-// gemv_epilogue), so row b has the bits of vita_gemv_w8 on row b.  No folded RMSNorm: a wave would redo every row's ~40 VALU
-// instructions per 8 elements for the few code rows it owns; the steps normalise once with vita_rmsnorm_fwd.
-// A wave owns CR code rows: 2 at R = 2 as gemv_w8_kernel, 4 at R = 4 and 8, which halves the x bytes (R x 32 per lane and vector,
-// from L1 / L2) that go with a byte of codes.  SWIGLU: the gate and up rows of CR / 2 outputs.  R = rows rounded up to 2, 4 or 8:
-// the surplus rows recompute row rows - 1 and are not stored; outputs behind N recompute output N - 1 and are not stored.  Code
-// rows behind N (2 N), columns behind K and input rows behind rows - 1 are never read.
+// gemv_rows_kernel's promise on gemv_w8_kernel's arithmetic, by qgemv.h's body: it walks K exactly as gemv_w8_kernel does (lane stride
+// 64 over the vectors, the chain from 0, acc += partial * scale, wave_reduce_sum, gemv_epilogue), so row b has the bits of
+// vita_gemv_w8 on row b.  No folded RMSNorm: a wave would redo every row's ~40 VALU instructions per 8 elements for the few code
+// rows it owns; the steps normalise once with vita_rmsnorm_fwd.  A wave owns 2 code rows at R = 2 as gemv_w8_kernel,
+// 4 at R = 4 and 8, which halves the x bytes (R x 32 per lane and vector, from L1 / L2) that go with a byte of codes.
+struct W8Format {
+  using codes_t = u32x4;
+  using scale_t = float;
+  using held_t = float;
+  static constexpr int kScaleShift = 7, kVecShift = 3;
+  static constexpr int code_rows(int R) { return R == 2 ? 2 : 4; }
+  static __device__ __forceinline__ void decode16(const u32x4 c, unsigned (&p)[8]) { w8_decode16(c, p); }
+  static __device__ __forceinline__ float scale_f32(const float s) { return s; }
+  static __device__ __forceinline__ float accumulate(const float acc, const float dot, const float scale) { return acc + dot * scale; }
+  // K a multiple of the block, code rows of K bytes at a 16-byte stride from a 16-byte aligned base
+  static bool codes_unsupported(const void* codes, int64_t ldc_bytes, int64_t K) {
+    return (K & (kW8Block - 1)) || K >= (int64_t(1) << 31) || (ldc_bytes & 15) || ldc_bytes < K || ((uintptr_t)codes & 15);
+  }
+  static constexpr uintptr_t kScaleAlign = 3;                          // fp32 scales
+  static constexpr int kRowsBelowOne = VITA_ERR_INVALID_ARG;
+};
+
 template <int EPI, int R>
 __global__ __launch_bounds__(256) void gemv_rows_w8_kernel(const bf16_t* __restrict__ x, int64_t ldx, int rows,
                                                            const unsigned char* __restrict__ codes, int64_t ldc,
                                                            const float* __restrict__ scales, bf16_t* __restrict__ y, int64_t ldy,
                                                            int64_t N, int64_t K, const bf16_t* __restrict__ bias,
                                                            const bf16_t* __restrict__ Res, int64_t ldr) {
-  constexpr bool SW = EPI == VITA_EPI_SWIGLU;
-  constexpr int CR = R == 2 ? 2 : 4, NSUB = SW ? 2 : 1, NOUT = CR / NSUB;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t n0 = ((int64_t)blockIdx.x * 4 + wave) * NOUT;          // first output of this wave
-  if (n0 >= N) return;
-  const int nvec = (int)(K >> 4), nblk = (int)(K >> 7);
-  const u32x4* xr[R];
-#pragma unroll
-  for (int b = 0; b < R; ++b) xr[b] = reinterpret_cast<const u32x4*>(x + (int64_t)(b < rows ? b : rows - 1) * ldx);
-  const u32x4* cp[NOUT][NSUB];
-  const float* sp[NOUT][NSUB];
-  float acc[NOUT][NSUB][R];
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-    const int64_t n = (n0 + o < N) ? n0 + o : N - 1;                   // clamp: tail outputs recompute output N - 1
-#pragma unroll
-    for (int s = 0; s < NSUB; ++s) {
-      const int64_t r = n + s * N;                                     // SWIGLU: s = 1 is the "up" row
-      cp[o][s] = reinterpret_cast<const u32x4*>(codes + r * ldc);
-      sp[o][s] = scales + r * nblk;
-#pragma unroll
-      for (int b = 0; b < R; ++b) acc[o][s][b] = 0.f;
-    }
-  }
-  // The loads are placed by hand (sched_barrier: nothing is scheduled across it), because left alone hipcc sinks every load to its
-  // first use to save registers and waits for each in turn.  Loads come back in issue order, so per vector: the x vectors of all
-  // rows (L1 / L2) are issued and fly under the decode of the codes, which were issued one vector earlier; then the codes and
-  // scales of the NEXT vector (HBM) are issued last and fly under all the dot products of this one.  Behind the last vector the
-  // same codes are loaded again: never a column behind K.  The order of the arithmetic is not touched.
-  u32x4 cv[NOUT][NSUB];
-  float sc[NOUT][NSUB];
-  const auto load_codes = [&](const int v) {
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-#pragma unroll
-      for (int s = 0; s < NSUB; ++s) {
-        cv[o][s] = cp[o][s][v];
-        sc[o][s] = sp[o][s][v >> 3];
-      }
-    }
-  };
-  if (lane < nvec) load_codes(lane);
-  for (int v = lane; v < nvec; v += 64) {
-    u32x4 xa[R], xb[R];
-#pragma unroll
-    for (int b = 0; b < R; ++b) xa[b] = xr[b][2 * v], xb[b] = xr[b][2 * v + 1];
-    __builtin_amdgcn_sched_barrier(0);
-    unsigned p[NOUT][NSUB][8];
-    float scv[NOUT][NSUB];
-#pragma unroll
-    for (int o = 0; o < NOUT; ++o) {
-#pragma unroll
-      for (int s = 0; s < NSUB; ++s) {
-        w8_decode16(cv[o][s], p[o][s]);
-        scv[o][s] = sc[o][s];
-      }
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    load_codes(v + 64 < nvec ? v + 64 : v);
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int b = 0; b < R; ++b) {
-#pragma unroll
-      for (int o = 0; o < NOUT; ++o) {
-#pragma unroll
-        for (int s = 0; s < NSUB; ++s) acc[o][s][b] += w8_dot16p(p[o][s], xa[b], xb[b]) * scv[o][s];
-      }
-    }
-  }
-#pragma unroll
-  for (int o = 0; o < NOUT; ++o) {
-#pragma unroll
-    for (int b = 0; b < R; ++b) {
-      const float t0 = wave_reduce_sum(acc[o][0][b]);
-      const float t1 = SW ? wave_reduce_sum(acc[o][NSUB - 1][b]) : 0.f;
-      const int64_t n = n0 + o;
-      if (lane != 0 || n >= N || b >= rows) continue;
-      y[(int64_t)b * ldy + n] = gemv_epilogue<EPI>(t0, t1, GEMV_ELEM(VITA_EPI_BIAS, bias, n), GEMV_ELEM(VITA_EPI_RESIDUAL, Res, (int64_t)b * ldr + n));
-    }
-  }
-}
-
-template <int EPI>
-void launch_gemv_rows_w8(const void* x, int64_t ldx, int rows, const void* codes, int64_t ldc, const void* scales, void* y, int64_t ldy,
-                         int64_t N, int64_t K, const void* bias, const void* R, int64_t ldr, hipStream_t st) {
-#define VITA_GRW8(RR)                                                                                                              \
-  {                                                                                                                                \
-    constexpr int NOUT = (RR == 2 ? 2 : 4) / (EPI == VITA_EPI_SWIGLU ? 2 : 1);                                                     \
-    const int64_t waves = (N + NOUT - 1) / NOUT;                                                                                   \
-    hipLaunchKernelGGL((gemv_rows_w8_kernel<EPI, RR>), dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, (const bf16_t*)x, ldx, \
-                       rows, (const unsigned char*)codes, ldc, (const float*)scales, (bf16_t*)y, ldy, N, K, (const bf16_t*)bias,   \
-                       (const bf16_t*)R, ldr);                                                                                     \
-  }
-  if (rows <= 2) VITA_GRW8(2) else if (rows <= 4) VITA_GRW8(4) else VITA_GRW8(8)
-#undef VITA_GRW8
+  qgemv_body<W8Format, EPI, R, false>(x, ldx, rows, codes, ldc, scales, y, ldy, N, K, bias, Res, ldr, nullptr, 0.f);
 }
 
 }  // namespace
@@ -233,6 +146,7 @@ void launch_gemv_rows_w8(const void* x, int64_t ldx, int rows, const void* codes
 extern "C" int vita_w8_quantize(const void* W, int64_t ldw, int64_t N, int64_t K, void* codes, int64_t ldc_bytes, void* scales,
                                 void* stream) {
   if (!W || !codes || !scales || N <= 0 || K <= 0) return VITA_ERR_INVALID_ARG;
+  // not W8Format::codes_unsupported: the quantiser has no 32-bit K (N K <= 2^40 is its bound)
   if ((K & (kW8Block - 1)) || (ldw & 7) || ldw < K || (ldc_bytes & 15) || ldc_bytes < K ||
       (((uintptr_t)W | (uintptr_t)codes) & 15) || ((uintptr_t)scales & 3) || N > (int64_t(1) << 40) / K)
     return VITA_ERR_UNSUPPORTED;
@@ -245,41 +159,23 @@ extern "C" int vita_w8_quantize(const void* W, int64_t ldw, int64_t N, int64_t K
 
 extern "C" int vita_gemv_w8(const void* x, const void* codes, int64_t ldc_bytes, const void* scales, void* y, int64_t N, int64_t K,
                             int epilogue, const void* bias, const void* R, const void* gamma, float eps, void* stream) {
-  if (!x || !codes || !scales || !y || N <= 0 || K <= 0) return VITA_ERR_INVALID_ARG;
-  if ((epilogue == VITA_EPI_BIAS && !bias) || (epilogue == VITA_EPI_RESIDUAL && !R)) return VITA_ERR_INVALID_ARG;
-  if (gamma && !(eps >= 0.f)) return VITA_ERR_INVALID_ARG;
-  if ((K & (kW8Block - 1)) || K >= (int64_t(1) << 31) || (ldc_bytes & 15) || ldc_bytes < K ||
-      (((uintptr_t)x | (uintptr_t)codes | (uintptr_t)gamma) & 15) || ((uintptr_t)scales & 3))   // 16-byte vectors, 4-byte scales
-    return VITA_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-#define VITA_GW8(E)                                                                                       \
-  case E:                                                                                                 \
-    if (gamma) launch_gemv_w8<E, true>(x, codes, ldc_bytes, scales, y, N, K, bias, R, gamma, eps, st);    \
-    else launch_gemv_w8<E, false>(x, codes, ldc_bytes, scales, y, N, K, bias, R, nullptr, 0.f, st);       \
-    break;
-  switch (epilogue) {
-    VITA_GW8(VITA_EPI_NONE) VITA_GW8(VITA_EPI_BIAS) VITA_GW8(VITA_EPI_RESIDUAL) VITA_GW8(VITA_EPI_SWIGLU)
-    default: return VITA_ERR_UNSUPPORTED;
-  }
-#undef VITA_GW8
-  return vita_check_launch();
+  const int rc = qgemv_refusal<W8Format>(x, codes, ldc_bytes, scales, y, N, K, epilogue, bias, R, gamma, eps);
+  if (rc != VITA_OK) return rc;
+  return qgemv_dispatch_norm(epilogue, gamma != nullptr, [&](auto e, auto norm) {
+    launch_gemv_w8<decltype(e)::value, decltype(norm)::value>(x, codes, ldc_bytes, scales, y, N, K, bias, R, gamma, norm ? eps : 0.f,
+                                                              (hipStream_t)stream);
+  });
 }
 
 extern "C" int vita_gemv_rows_w8(const void* x, int64_t ldx, int rows, const void* codes, int64_t ldc_bytes, const void* scales, void* y,
                                  int64_t ldy, int64_t N, int64_t K, int epilogue, const void* bias, const void* R, int64_t ldr,
                                  void* stream) {
-  if (!x || !codes || !scales || !y || N <= 0 || K <= 0 || rows <= 0) return VITA_ERR_INVALID_ARG;
-  if ((epilogue == VITA_EPI_BIAS && !bias) || (epilogue == VITA_EPI_RESIDUAL && (!R || ldr < N))) return VITA_ERR_INVALID_ARG;
-  if (rows > 8 || (K & (kW8Block - 1)) || K >= (int64_t(1) << 31) || (ldc_bytes & 15) || ldc_bytes < K || (ldx & 7) || ldx < K ||
-      ldy < N || (((uintptr_t)x | (uintptr_t)codes) & 15) || ((uintptr_t)scales & 3))              // 16-byte vectors, 4-byte scales
-    return VITA_ERR_UNSUPPORTED;
-  hipStream_t st = (hipStream_t)stream;
-#define VITA_GRW8E(E) \
-  case E: launch_gemv_rows_w8<E>(x, ldx, rows, codes, ldc_bytes, scales, y, ldy, N, K, bias, R, ldr, st); break;
-  switch (epilogue) {
-    VITA_GRW8E(VITA_EPI_NONE) VITA_GRW8E(VITA_EPI_BIAS) VITA_GRW8E(VITA_EPI_RESIDUAL) VITA_GRW8E(VITA_EPI_SWIGLU)
-    default: return VITA_ERR_UNSUPPORTED;
-  }
-#undef VITA_GRW8E
-  return vita_check_launch();
+  const int rc = qgemv_rows_refusal<W8Format>(x, ldx, rows, codes, ldc_bytes, scales, y, ldy, N, K, epilogue, bias, R, ldr);
+  if (rc != VITA_OK) return rc;
+  return qgemv_dispatch_rows(epilogue, rows, [&](auto e, auto r) {
+    constexpr int E = decltype(e)::value, RR = decltype(r)::value;
+    hipLaunchKernelGGL((gemv_rows_w8_kernel<E, RR>), dim3(qgemv_blocks<W8Format, E, RR>(N)), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)x, ldx, rows, (const unsigned char*)codes, ldc_bytes, (const float*)scales, (bf16_t*)y, ldy, N, K,
+                       (const bf16_t*)bias, (const bf16_t*)R, ldr);
+  });
 }

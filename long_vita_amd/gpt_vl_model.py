@@ -23,6 +23,7 @@ from .dot_product_attention import DotProductAttention
 from .inference_params import DecodeBatch, DraftRows, SharedPrefixBatch, check_decode_weight_dtype, check_kv_cache_dtype
 from .language_model_embedding import LanguageModelEmbedding
 from .layers import ColumnParallelLinear
+from .ops import WEIGHT_FORMATS          # the table itself: `ops` below may be replaced by a stand-in, its names are looked up per call
 from .rotary_pos_embedding import RotaryEmbedding
 
 
@@ -107,19 +108,30 @@ class GPTVLModel:
     W8_NAMES = ("qkv_w", "o_w", "fc1_w", "fc2_w")
 
     @property
+    def _wfmt(self):
+        """ops' record of the format the copies in self._w8 are (to be) of; None with the switch at "bf16"."""
+        return WEIGHT_FORMATS.get(getattr(self, "_decode_weight_dtype", "bf16"))
+
+    @property
     def _mx4(self) -> bool:
         """The copies in self._w8 are (to be) MXFP4 codes + scale bytes, not FP8 codes + fp32 scales."""
-        return getattr(self, "_decode_weight_dtype", "bf16") == "mxfp4"
+        return self._wfmt is WEIGHT_FORMATS["mxfp4"]
+
+    def _quantised_op(self, kind: str):
+        """What a decode step that has copies (self._w8_layers()) runs in place of ops.<kind>, kind = "gemv" or "gemv_rows": the
+        format's ops.<kind>_<tag> on codes and scales."""
+        return getattr(ops, WEIGHT_FORMATS[self._decode_weight_dtype].ops[kind])
 
     def _w8_layers(self, refresh: bool = False):
         """The quantised copies of every layer's four weights, [{name: (codes, scales)}], or None with the switch at "bf16".  Built
         on the device when first asked for (the first cached token or multi-row step); refresh (the start of a request) re-quantises,
         in place, every copy whose source has another data_ptr() or _version than the one it was made from."""
-        if getattr(self, "_decode_weight_dtype", "bf16") == "bf16":
+        fmt = self._wfmt
+        if fmt is None:
             return None
         if mpu.get_context_parallel_world_size() > 1 or mpu.get_tensor_model_parallel_world_size() > 1 or self.force_cp_path:
             raise NotImplementedError("the FP8 and MXFP4 decoder weights are built for CP = 1 and TP = 1")
-        quantize, layout = (ops.mx4_quantize, ops.mx4_layout) if self._mx4 else (ops.w8_quantize, ops.w8_layout)
+        quantize, layout = getattr(ops, fmt.ops["quantize"]), getattr(ops, fmt.ops["layout"])
         if getattr(self, "_w8", None) is None:
             self._w8 = [{} for _ in self.p["layers"]]
             self._w8_src = [{} for _ in self.p["layers"]]
@@ -146,7 +158,7 @@ class GPTVLModel:
             return ops.gemv_rows(x, self.p["layers"][li][name], epilogue, bias, **kw)
         if gamma is not None:
             x = ops.rmsnorm(x, gamma, self.cfg.eps, out=xn)
-        return (ops.gemv_rows_mx4 if self._mx4 else ops.gemv_rows_w8)(x, *w8[li][name], epilogue, bias, **kw)
+        return self._quantised_op("gemv_rows")(x, *w8[li][name], epilogue, bias, **kw)
 
     # ---------------------------------------------------------------------------------------------
     @classmethod
@@ -478,7 +490,7 @@ class GPTVLModel:
         tp = mpu.get_tensor_model_parallel_world_size()     # TP > 1: cfg / params / cache hold this rank's heads, groups and ffn slice
         ws = self._decode_workspace(token.device)
         w8 = self._w8_layers()                                  # FP8 / MXFP4 weights (CP = 1, TP = 1): ops.gemv_w8 / gemv_mx4 in place of ops.gemv
-        gemv_q = ops.gemv_mx4 if self._mx4 else ops.gemv_w8
+        gemv_op = ops.gemv if w8 is None else self._quantised_op("gemv")
         h = ops.row_gather(self.p["embed"], token.reshape(1), out=ws["h"], check_bounds=False)   # [1, hidden]
         cos, sin = ops.rope_table(position.reshape(1), self.rotary_pos_emb.inv_freq)
         owner = (ip.decode_steps % cp) == r
@@ -487,9 +499,7 @@ class GPTVLModel:
         for li, lp in enumerate(self.p["layers"]):
 
             def gemv(x, name, *args, **kw):
-                if w8 is None:
-                    return ops.gemv(x, lp[name], *args, **kw)
-                return gemv_q(x, *w8[li][name], *args, **kw)
+                return gemv_op(x, *((lp[name],) if w8 is None else w8[li][name]), *args, **kw)
 
             kv = ip.key_value_memory_dict[li + 1]
             sc = ip.kv_scale_dict.get(li + 1)                   # FP8 cache (CP = 1): codes in kv, scales here
@@ -593,11 +603,11 @@ class GPTVLModel:
                     extra["kv8"].append(k8)
             st = ip._layer_structs = (structs, extra)
         structs, extra = st
-        w8 = self._w8_layers()
-        if w8 is not None and extra.get("w8_of") is not w8:       # FP8 weights: where the _w8 entries find codes and scales
+        w8, fmt = self._w8_layers(), self._wfmt
+        if w8 is not None and extra.get("w8_of") is not w8:       # quantised weights: where the format's entries find codes and scales
             extra["w8"], extra["w8_of"] = [], w8                  # (built again should the copies have been freed and rebuilt)
             for q in w8:
-                s = _L.Mx4Layer() if self._mx4 else _L.W8Layer()
+                s = getattr(_L, fmt.layer)()
                 for name in self.W8_NAMES:
                     codes, scales = q[name]
                     setattr(s, name[:-2] + "_codes", codes.data_ptr())
@@ -617,13 +627,13 @@ class GPTVLModel:
         lib, stream = _L.load(), torch.cuda.current_stream().cuda_stream
         group = mpu.get_context_parallel_group() if cp > 1 else None
         kv8 = extra.get("kv8")
-        sfx = "_mx4" if isinstance(w8[0] if w8 else None, _L.Mx4Layer) else "_w8"      # the format the structs were built for
-        attn_q, mlp_q = getattr(lib, "vita_decode_layer_attn" + sfx), getattr(lib, "vita_decode_layer_mlp" + sfx)
+        if w8 is not None:
+            attn_q, mlp_q = fmt.entries["layer_attn"], fmt.entries["layer_mlp"]
         for li, s in enumerate(structs):
             s.append_row, s.len, s.n_splits = (row if owner else -1), length, n_splits
             if w8 is not None:
-                _L.check(attn_q(C.byref(s), C.byref(w8[li]), None if kv8 is None else C.byref(kv8[li]), stream), "vita_decode_layer_attn" + sfx)
-                _L.check(mlp_q(C.byref(s), C.byref(w8[li]), stream), "vita_decode_layer_mlp" + sfx)
+                _L.check(getattr(lib, attn_q)(C.byref(s), C.byref(w8[li]), None if kv8 is None else C.byref(kv8[li]), stream), attn_q)
+                _L.check(getattr(lib, mlp_q)(C.byref(s), C.byref(w8[li]), stream), mlp_q)
                 continue
             if kv8 is not None:
                 _L.check(lib.vita_decode_layer_attn_kv8(C.byref(s), C.byref(kv8[li]), stream), "vita_decode_layer_attn_kv8")

@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import torch
 
+from .ops import WEIGHT_FORMATS
 
 KV_CACHE_DTYPES = ("bf16", "fp8_e4m3")
 
@@ -32,7 +33,7 @@ def check_kv_cache_dtype(name, allow_none: bool = False):
     return name
 
 
-DECODE_WEIGHT_DTYPES = ("bf16", "fp8_e4m3", "mxfp4")
+DECODE_WEIGHT_DTYPES = ("bf16",) + tuple(WEIGHT_FORMATS)     # "fp8_e4m3", "mxfp4": the formats ops keeps a record of
 
 
 def check_decode_weight_dtype(name, allow_none: bool = False):

@@ -10,7 +10,7 @@ import contextlib
 import ctypes as C
 import math
 import os
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
@@ -1286,46 +1286,151 @@ def decode_attn_partial_kv8(q: torch.Tensor, k_codes: torch.Tensor, v_codes: tor
 
 
 # ------------------------------------------------------------------------------------------------
-# FP8 (e4m3) decoder weights for the cached token step (include/vita_hip.h: vita_w8_*, vita_gemv_w8)
+# quantised decoder weights for the cached token step and the multi-row steps: FP8 (e4m3 + fp32 scales) and MXFP4 (e2m1 + E8M0 bytes)
+# (include/vita_hip.h: vita_w8_*, vita_gemv_w8, vita_gemv_rows_w8 and their _mx4 twins)
 # ------------------------------------------------------------------------------------------------
-W8_BLOCK = 128                           # consecutive K elements of a weight row that share a scale
+W8_BLOCK = 128                           # FP8: consecutive K elements of a weight row that share a scale
+MX4_BLOCK = 32                           # MXFP4: consecutive K elements of a weight row that share a scale byte
 
 
+class WeightFormat(NamedTuple):
+    """What tells one quantised weight format from another on the host side.  Everything below, GPTVLModel's switch and
+    inference_params.DECODE_WEIGHT_DTYPES read WEIGHT_FORMATS; the device side's twin is the traits struct in csrc/<tag>.hip."""
+    dtype: str                           # the name decode_weight_dtype takes
+    tag: str                             # in this module's names and the library's
+    block: int                           # K elements per scale
+    per_byte: int                        # codes per byte
+    code_dtypes: tuple                   # what a codes tensor may be; the first is what quantize allocates
+    scale_dtype: torch.dtype
+    code_words: str                      # the two, as the messages say them
+    scale_word: str
+    layer: str                           # lib's mirror of the fused layer entries' struct of code and scale pointers
+    ops: dict                            # OP_NAMES' kind -> this module's name: callers look it up on the module when they call
+    entries: dict                        # ENTRY_NAMES' kind -> the library's entry
+
+    def codes_shape(self, K="K"):
+        """How a row of K codes reads in a message: "K" / "K / 2"; with a number: "K = 256" / "K / 2 = 128"."""
+        words = "K" if self.per_byte == 1 else f"K / {self.per_byte}"
+        return words if K == "K" else f"{words} = {K // self.per_byte}"
+
+
+OP_NAMES = {"layout": "{}_layout", "quantize": "{}_quantize", "gemv": "gemv_{}", "gemv_rows": "gemv_rows_{}"}
+ENTRY_NAMES = {"quantize": "vita_{}_quantize", "gemv": "vita_gemv_{}", "gemv_rows": "vita_gemv_rows_{}",
+               "layer_attn": "vita_decode_layer_attn_{}", "layer_mlp": "vita_decode_layer_mlp_{}"}
+
+
+def _weight_format(dtype, tag, *facts):
+    return WeightFormat(dtype, tag, *facts, ops={k: v.format(tag) for k, v in OP_NAMES.items()},
+                        entries={k: v.format(tag) for k, v in ENTRY_NAMES.items()})
+
+
+WEIGHT_FORMATS = {f.dtype: f for f in (
+    _weight_format("fp8_e4m3", "w8", W8_BLOCK, 1, (KV8_DTYPE, torch.uint8), torch.float32, f"{KV8_DTYPE} (or their bytes as uint8)", "fp32",
+                   "W8Layer"),
+    _weight_format("mxfp4", "mx4", MX4_BLOCK, 2, (torch.uint8,), torch.uint8, "uint8", "uint8", "Mx4Layer"))}
+_W8, _MX4 = WEIGHT_FORMATS["fp8_e4m3"], WEIGHT_FORMATS["mxfp4"]
+
+
+def _q_layout(f: WeightFormat, N: int, K: int) -> dict:
+    if K % f.block:
+        raise ValueError(f"{f.tag}: K = {K} must be a multiple of {f.block}")
+    nbytes = N * (K // f.per_byte) + f.scale_dtype.itemsize * N * (K // f.block)
+    return {"codes": (N, K // f.per_byte), "scales": (N, K // f.block), "bytes": nbytes, "bytes_bf16": 2 * N * K, "ratio": nbytes / (2 * N * K)}
+
+
+def _q_views(f: WeightFormat, codes: torch.Tensor, scales: torch.Tensor, what: str):
+    """(code rows, K) of a codes / scales pair of format f, or what is wrong with it."""
+    if codes.dim() != 2 or codes.dtype not in f.code_dtypes or codes.stride(1) != 1:
+        raise ValueError(f"{what}: codes [N, {f.codes_shape()}] must be {f.code_words} with unit inner stride")
+    rows, K = codes.shape[0], f.per_byte * codes.shape[1]
+    if K % f.block:
+        raise RuntimeError(f"{what}: K = {K} must be a multiple of {f.block}")
+    if tuple(scales.shape) != (rows, K // f.block) or scales.dtype != f.scale_dtype or not scales.is_contiguous():
+        raise ValueError(f"{what}: scales must be dense {f.scale_word} [N, K / {f.block}]")
+    return rows, K
+
+
+def _q_quantize(f: WeightFormat, w: torch.Tensor, codes: Optional[torch.Tensor], scales: Optional[torch.Tensor]):
+    what = f.ops["quantize"]
+    if w.dim() != 2 or w.stride(1) != 1:
+        raise ValueError(f"{what}: w [N, K] with unit inner stride")
+    N, K = w.shape
+    lay = _q_layout(f, N, K)
+    if codes is None:
+        codes = torch.empty(lay["codes"], dtype=f.code_dtypes[0], device=w.device)
+    if scales is None:
+        scales = torch.empty(lay["scales"], dtype=f.scale_dtype, device=w.device)
+    if _q_views(f, codes, scales, what) != (N, K):
+        raise ValueError(f"{what}: codes and scales do not match w")
+    entry = f.entries["quantize"]
+    _L.check(getattr(_L.load(), entry)(_dev(w, "w", BF16), w.stride(0), N, K, _dev(codes, "codes"), codes.stride(0),
+                                       _dev(scales, "scales", f.scale_dtype), _stream()), entry)
+    return codes, scales
+
+
+def _q_gemv(f: WeightFormat, x, codes, scales, epilogue, bias, residual, out, gamma, eps) -> torch.Tensor:
+    what = f.ops["gemv"]
+    K = x.numel()
+    n_rows, Kc = _q_views(f, codes, scales, what)
+    if Kc != K:
+        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, {f.codes_shape(K)} expected")
+    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
+    y = torch.empty(N, dtype=BF16, device=x.device) if out is None else out
+    if y.numel() != N or not y.is_contiguous() or not x.is_contiguous():
+        raise ValueError(f"{what} needs contiguous x and out of N elements")
+    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
+        raise ValueError(f"{what}: gamma [K] contiguous")
+    entry = f.entries["gemv"]
+    _L.check(getattr(_L.load(), entry)(_dev(x, "x", BF16), _dev(codes, "codes"), codes.stride(0), _dev(scales, "scales", f.scale_dtype),
+                                       _dev(y, "out", BF16), N, K, epilogue, _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
+                                       _opt(gamma, "gamma", BF16), float(eps), _stream()), entry)
+    return y
+
+
+def _q_gemv_rows(f: WeightFormat, x, codes, scales, epilogue, bias, residual, out) -> torch.Tensor:
+    what = f.ops["gemv_rows"]
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError(f"{what}: x must be [rows, K] with a unit inner stride")
+    rows, K = x.shape
+    n_rows, Kc = _q_views(f, codes, scales, what)
+    if Kc != K:
+        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, {f.codes_shape(K)} expected")
+    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
+    y = torch.empty(rows, N, dtype=BF16, device=x.device) if out is None else out
+    if tuple(y.shape) != (rows, N) or y.stride(1) != 1:
+        raise ValueError(f"{what}: out must be [rows, N] with a unit inner stride")
+    if residual is not None and (tuple(residual.shape) != (rows, N) or residual.stride(1) != 1):
+        raise ValueError(f"{what}: residual must be [rows, N] with a unit inner stride")
+    entry = f.entries["gemv_rows"]
+    _L.check(getattr(_L.load(), entry)(_dev(x, "x", BF16), x.stride(0), rows, _dev(codes, "codes"), codes.stride(0),
+                                       _dev(scales, "scales", f.scale_dtype), _dev(y, "out", BF16), y.stride(0), N, K, epilogue,
+                                       _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
+                                       residual.stride(0) if residual is not None else 0, _stream()), entry)
+    return y
+
+
+# the public names: each binds its format's record to the one implementation above
 def w8_layout(N: int, K: int) -> dict:
     """Pure layout, no allocation: codes [N, K] e4m3 (1 byte), scales [N, K / 128] fp32, and their bytes next to the bf16 weight's."""
-    if K % W8_BLOCK:
-        raise ValueError(f"w8: K = {K} must be a multiple of {W8_BLOCK}")
-    nbytes = N * K + 4 * N * (K // W8_BLOCK)
-    return {"codes": (N, K), "scales": (N, K // W8_BLOCK), "bytes": nbytes, "bytes_bf16": 2 * N * K, "ratio": nbytes / (2 * N * K)}
+    return _q_layout(_W8, N, K)
 
 
-def _w8_views(codes: torch.Tensor, scales: torch.Tensor, what: str):
-    if codes.dim() != 2 or codes.dtype not in (KV8_DTYPE, torch.uint8) or codes.stride(1) != 1:
-        raise ValueError(f"{what}: codes [N, K] must be {KV8_DTYPE} (or their bytes as uint8) with unit inner stride")
-    rows, K = codes.shape
-    if K % W8_BLOCK:
-        raise RuntimeError(f"{what}: K = {K} must be a multiple of {W8_BLOCK}")
-    if tuple(scales.shape) != (rows, K // W8_BLOCK) or not scales.is_contiguous():
-        raise ValueError(f"{what}: scales must be dense fp32 [N, K / {W8_BLOCK}]")
-    return rows, K
+def mx4_layout(N: int, K: int) -> dict:
+    """Pure layout, no allocation: codes [N, K / 2] uint8 (two e2m1 codes per byte, element 2 j in the low nibble of byte j), scales
+    [N, K / 32] uint8 (E8M0), and their bytes next to the bf16 weight's."""
+    return _q_layout(_MX4, N, K)
 
 
 def w8_quantize(w: torch.Tensor, codes: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None):
     """w [N, K] bf16 (unit inner stride) -> (codes [N, K] e4m3, scales [N, K / 128] fp32) by the KV cache's rule on every run of
     128 consecutive K elements of a row.  codes / scales: destinations to fill (codes may be a padded-row view)."""
-    if w.dim() != 2 or w.stride(1) != 1:
-        raise ValueError("w8_quantize: w [N, K] with unit inner stride")
-    N, K = w.shape
-    lay = w8_layout(N, K)
-    if codes is None:
-        codes = torch.empty(lay["codes"], dtype=KV8_DTYPE, device=w.device)
-    if scales is None:
-        scales = torch.empty(lay["scales"], dtype=torch.float32, device=w.device)
-    if _w8_views(codes, scales, "w8_quantize") != (N, K):
-        raise ValueError("w8_quantize: codes and scales do not match w")
-    _L.check(_L.load().vita_w8_quantize(_dev(w, "w", BF16), w.stride(0), N, K, _dev(codes, "codes"), codes.stride(0),
-                                        _dev(scales, "scales", torch.float32), _stream()), "vita_w8_quantize")
-    return codes, scales
+    return _q_quantize(_W8, w, codes, scales)
+
+
+def mx4_quantize(w: torch.Tensor, codes: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None):
+    """w [N, K] bf16 (unit inner stride) -> (codes [N, K / 2] uint8, scales [N, K / 32] uint8) by the MXFP4 rule of csrc/mx4_rule.h on
+    every run of 32 consecutive K elements of a row.  codes / scales: destinations to fill (codes may be a padded-row view)."""
+    return _q_quantize(_MX4, w, codes, scales)
 
 
 def gemv_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
@@ -1333,64 +1438,7 @@ def gemv_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue
             eps: float = 0.0) -> torch.Tensor:
     """gemv over FP8 weights: y[N] = epilogue(dequant(codes, scales)[N, K] . x[K]); SWIGLU: codes of cat[gate, up], N = rows / 2.
     gamma: x is RMS-normalised first (gamma [K], eps), as the fused layer entries do."""
-    K = x.numel()
-    n_rows, Kc = _w8_views(codes, scales, "gemv_w8")
-    if Kc != K:
-        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, K = {K} expected")
-    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
-    y = torch.empty(N, dtype=BF16, device=x.device) if out is None else out
-    if y.numel() != N or not y.is_contiguous() or not x.is_contiguous():
-        raise ValueError("gemv_w8 needs contiguous x and out of N elements")
-    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
-        raise ValueError("gemv_w8: gamma [K] contiguous")
-    _L.check(_L.load().vita_gemv_w8(_dev(x, "x", BF16), _dev(codes, "codes"), codes.stride(0), _dev(scales, "scales", torch.float32),
-                                    _dev(y, "out", BF16), N, K, epilogue, _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
-                                    _opt(gamma, "gamma", BF16), float(eps), _stream()), "vita_gemv_w8")
-    return y
-
-
-# ------------------------------------------------------------------------------------------------
-# MXFP4 (e2m1 + E8M0) decoder weights for the cached token step (include/vita_hip.h: vita_mx4_*, vita_gemv_mx4; DESIGN.md 4.5)
-# ------------------------------------------------------------------------------------------------
-MX4_BLOCK = 32                           # consecutive K elements of a weight row that share a scale byte
-
-
-def mx4_layout(N: int, K: int) -> dict:
-    """Pure layout, no allocation: codes [N, K / 2] uint8 (two e2m1 codes per byte, element 2 j in the low nibble of byte j), scales
-    [N, K / 32] uint8 (E8M0), and their bytes next to the bf16 weight's."""
-    if K % MX4_BLOCK:
-        raise ValueError(f"mx4: K = {K} must be a multiple of {MX4_BLOCK}")
-    nbytes = N * (K // 2) + N * (K // MX4_BLOCK)
-    return {"codes": (N, K // 2), "scales": (N, K // MX4_BLOCK), "bytes": nbytes, "bytes_bf16": 2 * N * K, "ratio": nbytes / (2 * N * K)}
-
-
-def _mx4_views(codes: torch.Tensor, scales: torch.Tensor, what: str):
-    if codes.dim() != 2 or codes.dtype != torch.uint8 or codes.stride(1) != 1:
-        raise ValueError(f"{what}: codes [N, K / 2] must be uint8 with unit inner stride")
-    rows, K = codes.shape[0], 2 * codes.shape[1]
-    if K % MX4_BLOCK:
-        raise RuntimeError(f"{what}: K = {K} must be a multiple of {MX4_BLOCK}")
-    if tuple(scales.shape) != (rows, K // MX4_BLOCK) or scales.dtype != torch.uint8 or not scales.is_contiguous():
-        raise ValueError(f"{what}: scales must be dense uint8 [N, K / {MX4_BLOCK}]")
-    return rows, K
-
-
-def mx4_quantize(w: torch.Tensor, codes: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None):
-    """w [N, K] bf16 (unit inner stride) -> (codes [N, K / 2] uint8, scales [N, K / 32] uint8) by the MXFP4 rule of csrc/mx4_rule.h on
-    every run of 32 consecutive K elements of a row.  codes / scales: destinations to fill (codes may be a padded-row view)."""
-    if w.dim() != 2 or w.stride(1) != 1:
-        raise ValueError("mx4_quantize: w [N, K] with unit inner stride")
-    N, K = w.shape
-    lay = mx4_layout(N, K)
-    if codes is None:
-        codes = torch.empty(lay["codes"], dtype=torch.uint8, device=w.device)
-    if scales is None:
-        scales = torch.empty(lay["scales"], dtype=torch.uint8, device=w.device)
-    if _mx4_views(codes, scales, "mx4_quantize") != (N, K):
-        raise ValueError("mx4_quantize: codes and scales do not match w")
-    _L.check(_L.load().vita_mx4_quantize(_dev(w, "w", BF16), w.stride(0), N, K, _dev(codes, "codes"), codes.stride(0),
-                                         _dev(scales, "scales", torch.uint8), _stream()), "vita_mx4_quantize")
-    return codes, scales
+    return _q_gemv(_W8, x, codes, scales, epilogue, bias, residual, out, gamma, eps)
 
 
 def gemv_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
@@ -1398,20 +1446,25 @@ def gemv_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogu
              eps: float = 0.0) -> torch.Tensor:
     """gemv over MXFP4 weights: y[N] = epilogue(dequant(codes, scales)[N, K] . x[K]); SWIGLU: codes of cat[gate, up], N = rows / 2.
     gamma: x is RMS-normalised first (gamma [K], eps), as the fused layer entries do."""
-    K = x.numel()
-    n_rows, Kc = _mx4_views(codes, scales, "gemv_mx4")
-    if Kc != K:
-        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, K / 2 = {K // 2} expected")
-    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
-    y = torch.empty(N, dtype=BF16, device=x.device) if out is None else out
-    if y.numel() != N or not y.is_contiguous() or not x.is_contiguous():
-        raise ValueError("gemv_mx4 needs contiguous x and out of N elements")
-    if gamma is not None and (gamma.numel() != K or not gamma.is_contiguous()):
-        raise ValueError("gemv_mx4: gamma [K] contiguous")
-    _L.check(_L.load().vita_gemv_mx4(_dev(x, "x", BF16), _dev(codes, "codes"), codes.stride(0), _dev(scales, "scales", torch.uint8),
-                                     _dev(y, "out", BF16), N, K, epilogue, _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
-                                     _opt(gamma, "gamma", BF16), float(eps), _stream()), "vita_gemv_mx4")
-    return y
+    return _q_gemv(_MX4, x, codes, scales, epilogue, bias, residual, out, gamma, eps)
+
+
+def gemv_rows_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+                 residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemv_rows over FP8 weights: y[b] = epilogue(dequant(codes, scales) . x[b]) for the rows of x [rows <= 8, K]; every code row and
+    its scales are read once for all of them, and row b has the bits of gemv_w8(x[b]) without gamma (normalise the rows with rmsnorm
+    first).  SWIGLU: codes of cat[gate, up], N = code rows / 2.  residual [rows, N], out [rows, N] (unit inner stride; out may alias
+    residual)."""
+    return _q_gemv_rows(_W8, x, codes, scales, epilogue, bias, residual, out)
+
+
+def gemv_rows_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """gemv_rows over MXFP4 weights: y[b] = epilogue(dequant(codes, scales) . x[b]) for the rows of x [rows <= 8, K]; every code row and
+    its scales are read once for all of them, and row b has the bits of gemv_mx4(x[b]) without gamma (normalise the rows with rmsnorm
+    first).  SWIGLU: codes of cat[gate, up], N = code rows / 2.  residual [rows, N], out [rows, N] (unit inner stride; out may alias
+    residual)."""
+    return _q_gemv_rows(_MX4, x, codes, scales, epilogue, bias, residual, out)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1443,56 +1496,6 @@ def gemv_rows(x: torch.Tensor, w: torch.Tensor, epilogue: int = EPI_NONE, bias: 
                                            y.stride(0), N, K, epilogue, _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
                                            residual.stride(0) if residual is not None else 0, _opt(gamma, "gamma", BF16), float(eps),
                                            _stream()), "vita_gemv_rows_bf16")
-    return y
-
-
-def gemv_rows_w8(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
-                 residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """gemv_rows over FP8 weights: y[b] = epilogue(dequant(codes, scales) . x[b]) for the rows of x [rows <= 8, K]; every code row and
-    its scales are read once for all of them, and row b has the bits of gemv_w8(x[b]) without gamma (normalise the rows with rmsnorm
-    first).  SWIGLU: codes of cat[gate, up], N = code rows / 2.  residual [rows, N], out [rows, N] (unit inner stride; out may alias
-    residual)."""
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError("gemv_rows_w8: x must be [rows, K] with a unit inner stride")
-    rows, K = x.shape
-    n_rows, Kc = _w8_views(codes, scales, "gemv_rows_w8")
-    if Kc != K:
-        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, K = {K} expected")
-    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
-    y = torch.empty(rows, N, dtype=BF16, device=x.device) if out is None else out
-    if tuple(y.shape) != (rows, N) or y.stride(1) != 1:
-        raise ValueError("gemv_rows_w8: out must be [rows, N] with a unit inner stride")
-    if residual is not None and (tuple(residual.shape) != (rows, N) or residual.stride(1) != 1):
-        raise ValueError("gemv_rows_w8: residual must be [rows, N] with a unit inner stride")
-    _L.check(_L.load().vita_gemv_rows_w8(_dev(x, "x", BF16), x.stride(0), rows, _dev(codes, "codes"), codes.stride(0),
-                                         _dev(scales, "scales", torch.float32), _dev(y, "out", BF16), y.stride(0), N, K, epilogue,
-                                         _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
-                                         residual.stride(0) if residual is not None else 0, _stream()), "vita_gemv_rows_w8")
-    return y
-
-
-def gemv_rows_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
-                  residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """gemv_rows over MXFP4 weights: y[b] = epilogue(dequant(codes, scales) . x[b]) for the rows of x [rows <= 8, K]; every code row and
-    its scales are read once for all of them, and row b has the bits of gemv_mx4(x[b]) without gamma (normalise the rows with rmsnorm
-    first).  SWIGLU: codes of cat[gate, up], N = code rows / 2.  residual [rows, N], out [rows, N] (unit inner stride; out may alias
-    residual)."""
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise ValueError("gemv_rows_mx4: x must be [rows, K] with a unit inner stride")
-    rows, K = x.shape
-    n_rows, Kc = _mx4_views(codes, scales, "gemv_rows_mx4")
-    if Kc != K:
-        raise RuntimeError(f"supplied weight's shape is {tuple(codes.shape)}, K / 2 = {K // 2} expected")
-    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
-    y = torch.empty(rows, N, dtype=BF16, device=x.device) if out is None else out
-    if tuple(y.shape) != (rows, N) or y.stride(1) != 1:
-        raise ValueError("gemv_rows_mx4: out must be [rows, N] with a unit inner stride")
-    if residual is not None and (tuple(residual.shape) != (rows, N) or residual.stride(1) != 1):
-        raise ValueError("gemv_rows_mx4: residual must be [rows, N] with a unit inner stride")
-    _L.check(_L.load().vita_gemv_rows_mx4(_dev(x, "x", BF16), x.stride(0), rows, _dev(codes, "codes"), codes.stride(0),
-                                          _dev(scales, "scales", torch.uint8), _dev(y, "out", BF16), y.stride(0), N, K, epilogue,
-                                          _opt(bias, "bias", BF16), _opt(residual, "residual", BF16),
-                                          residual.stride(0) if residual is not None else 0, _stream()), "vita_gemv_rows_mx4")
     return y
 
 
