@@ -14,8 +14,20 @@
 //   * phase 1: 32 MFMAs  S(t+1) = K(t+1) Q^T  ||  exp2 / row sum / bf16 pack of the last 8 - NF2 P fragments of tile t
 //     phase 2: 32 MFMAs  O += V(t)^T P(t)^T   ||  the first NF2 P fragments of tile t+1
 //     NF2 = 4: one exp half-unit behind every MFMA, two fma + two exp2 behind the even ones, two adds + one pack behind the odd
-//     ones; sched_barrier(0) in front of and behind every MFMA keeps the order (left alone, the scheduler hoists a slot's filler
-//     in front of its MFMA and two MFMAs issue back to back)
+//     ones (phase 1 ends two slots early: make_deal1); sched_barrier(0) in front of and behind every MFMA keeps the order (left
+//     alone, the scheduler hoists a slot's filler in front of its MFMA and two MFMAs issue back to back)
+//   * the SEAMS between the phases hold a branch and nothing else (r26; before, stamped: 223 and 265 cycles per tile beyond the MFMA
+//     slot, of about 2900, profiles/r26_attn_seams.txt): whatever a phase needs before its first MFMA is done inside the phase
+//     before it.  The S phase reads the P V phase's first three V^T fragments in front of its MFMAs 29 and 31 and makes the
+//     acceptance compare (and the mask flag of the tile being multiplied) in front of MFMA 31, into ONE scalar, so that one s_cmp
+//     and one branch separate the last S MFMA from the first P V MFMA; the fragments stay live across the out-of-line path.  The
+//     P V phase moves the tile walk on and builds the next trip's DMA descriptors in two of its sum-and-pack gaps, holds the tile's
+//     barrier in front of its MFMA 29 and reads the next S phase's first three K fragments behind it: the loop's back edge is the
+//     other seam.  The prologue and the peeled last trip keep the plain order.  Bit-identical to the kernel before (the arithmetic,
+//     its order inside every half-unit and the order of the row-sum adds are untouched; tests/test_attn64_seams_gpu.py holds the
+//     digests).  Same-box A / B, 7 rounds: 128K 134.50 -> 131.00 ms (- 2.6 %, parent's spread 0.12 ms), 32K 8.585 -> 8.320, 16K 2.173
+//     -> 2.134 (profiles/r26_attn_seams_ab.txt; what each step gave alone, and that the barrier and the walk pay only next to the
+//     closed S -> P V seam: HISTORY §4.1)
 //   * OPTIMISTIC running maximum (r12) on top of the LAZY one (r02: the maximum, and with it O and l, only moves when some row of
 //     the wave exceeds it by more than 2^THR, THR = 8, so P <= 2^8 instead of <= 1 — bf16 / fp32 have the range, the relative
 //     rounding of P is unchanged — and the 400-instruction accumulator rescale leaves the steady state).  Tile 0 gets its true row
@@ -27,7 +39,7 @@
 //     are bit-identical to that kernel's.  Same-box A / B against it: 128K 145.7 -> 135.0 ms, 32K 9.24 -> 8.71, 16K 2.40 -> 2.25
 //     (profiles/r12_attn_optimistic_ab.txt)
 //   * K / V tiles HBM/L2 -> LDS by LDS-DMA (buffer_load ... lds: SGPR descriptor re-based per tile + the lane's 32-bit offset,
-//     no address VALU), separate K and V rings of two 16 KiB slots, one barrier per tile; attn_tile.h's frag / tr layouts
+//     no address VALU), separate K and V rings of two 16 KiB slots, one barrier per tile (inside the P V phase); attn_tile.h's frag / tr layouts
 //     (conflict-free ds_read_b128 / ds_read_b64_tr_b16), the swizzle applied to the DMA's per-lane SOURCE address
 //   * masks: a tile of the diagonal chunk that reaches past the workgroup's first row is masked element-wise for every wave
 //     (tiles wholly past a wave's rows come out as exp2(-inf) = 0: no per-wave control flow in the pipeline)
@@ -44,11 +56,12 @@ constexpr int NF2 = 4;                                                          
 constexpr int THR = 8;                                                               // lazy running maximum, log2 units
 constexpr float ACCEPT_MAX = (float)(1 << THR);                                      // a lane's row sum <= 2^THR: none of its p exceeds 2^THR
 
-// ---- filler schedule: the 64 exp half-units of a tile dealt to the 2 x 32 MFMA slots by cumulative issue cost -------------------
+// ---- filler schedule: the 64 exp half-units of a tile dealt to the 2 x 32 MFMA slots -------------------------------------------------
 // half 0: two fma + two exp2 (1 + 1 + 2 + 2), half 1: two row-sum adds + one bf16 pack (3).  Phase 2 (P V of tile t) carries half-units
-// 0 .. 8 NF2 - 1 of tile t+1, phase 1 (S of tile t+1) half-units 8 NF2 .. 63 of tile t.  A unit goes to the slot its weight's midpoint
-// falls in; with NF2 = 4 that is ONE half-unit per slot, half 0 behind the even MFMAs and half 1 behind the odd ones: no gap
-// holds more than 24 cycles of VALU issue, and the gaps in front of the even MFMAs (LDS reads, DMA pieces) hold 12.
+// 0 .. 8 NF2 - 1 of tile t+1, dealt by cumulative issue cost (make_map: a unit goes to the slot its weight's midpoint falls in; with
+// NF2 = 4 that is ONE half-unit per slot, half 0 behind the even MFMAs and half 1 behind the odd ones: no gap holds more than 24 cycles
+// of VALU issue, and the gaps in front of the even MFMAs, with their LDS reads, hold 12).  Phase 1 (S of tile t+1) carries half-units
+// 8 NF2 .. 63 of tile t and ENDS TWO SLOTS EARLY (make_deal1).
 struct SlotMap { int first[33]; };
 constexpr int half_w(int h) { return (h & 1) ? 3 : 6; }
 constexpr SlotMap make_map(int h0, int n) {
@@ -62,6 +75,26 @@ constexpr SlotMap make_map(int h0, int n) {
   }
   m.first[32] = n;
   return m;
+}
+// Phase 1: half-units 32 .. 63, up to two per slot; w picks the pair of exp2 temporaries.  Slots 0 .. 21 and 28, 29 hold one, in order.
+// Half-units 54 .. 57 and 58 .. 61 are dealt over three slots each as (exp2 pair A | exp2 pair B | sums and packs of A and B): 8 + 24,
+// 8 + 24 and 8 + 2 x 12.5 cycles of issue, the doubled slots being 24 and 27, whose gaps carry neither a DMA piece nor a K read.  The
+// tile's last row-sum add is behind MFMA 29, slots 30 and 31 are free: the acceptance compare is issued in front of MFMA 31.  The adds
+// into l_tile keep the order of the half-units, so the sums are the ones a one-per-slot deal gives.
+struct Deal { int n[32]; int h[32][2]; int w[32][2]; };
+constexpr Deal make_deal1() {
+  Deal d{};
+  for (int s = 0; s < 22; ++s) { d.n[s] = 1; d.h[s][0] = 32 + s; }
+  const int at[2] = {22, 25};
+  for (int k = 0; k < 2; ++k) {
+    const int s = at[k], u = 32 + s + k;                      // u even: the exp2 half of pair A
+    d.n[s] = 1; d.h[s][0] = u;
+    d.n[s + 1] = 1; d.h[s + 1][0] = u + 2; d.w[s + 1][0] = 1;
+    d.n[s + 2] = 2; d.h[s + 2][0] = u + 1; d.h[s + 2][1] = u + 3; d.w[s + 2][1] = 1;
+  }
+  d.n[28] = 1; d.h[28][0] = 62;
+  d.n[29] = 1; d.h[29][0] = 63;
+  return d;
 }
 
 // One barrier per tile (rings of two slots).  (Rings of four slots, TWO tiles between barriers and the DMAs of tiles t+2 .. t+4 issued
@@ -200,21 +233,23 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   // maximum, l_run ~ 5e4 -> ulp 4e-3), the small ones are rounded away and O / l comes out too large — 1.5e-2 at 13 M keys
   // (tools/bench_maxseq.py: one CP = 8 rank at S = 16.8 M); a tile's partial sum is 32 x larger than its terms
   float l_tile[2] = {0.f, 0.f};
-  float ea = 0.f, eb = 0.f;
+  float ea[2] = {0.f, 0.f}, eb[2] = {0.f, 0.f};                      // two pairs of exp2 results (Deal)
 
-  constexpr SlotMap MAP1 = make_map(8 * NF2, 64 - 8 * NF2), MAP2 = make_map(0, 8 * NF2);
+  constexpr SlotMap MAP2 = make_map(0, 8 * NF2);
+  constexpr Deal DEAL1 = make_deal1();
+  static_assert(NF2 == 4, "make_deal1 deals half-units 32 .. 63");
 
   // exp half-units (64 per tile): h -> fragment g = h >> 3 (need order of P V: g = 2 f + qb), element pair pr = (h >> 1) & 3;
   // half 0: the two fma + exp2 of the pair, half 1: row sum, bf16 pack (an exp2 result is never consumed by the next instruction)
-  auto exp_half = [&](int par, int h) __attribute__((always_inline)) {
+  auto exp_half = [&](int par, int h, int w = 0) __attribute__((always_inline)) {
     const int g = h >> 3, pr = (h >> 1) & 3, qb = g & 1, f = g >> 1, kb = f >> 1, r = 8 * (f & 1) + 2 * pr;
     if ((h & 1) == 0) {
-      ea = __builtin_amdgcn_exp2f(fmaf(sb[par][qb][kb][r], scale_log2e, m_neg[qb]));
-      eb = __builtin_amdgcn_exp2f(fmaf(sb[par][qb][kb][r + 1], scale_log2e, m_neg[qb]));
+      ea[w] = __builtin_amdgcn_exp2f(fmaf(sb[par][qb][kb][r], scale_log2e, m_neg[qb]));
+      eb[w] = __builtin_amdgcn_exp2f(fmaf(sb[par][qb][kb][r + 1], scale_log2e, m_neg[qb]));
     } else {
-      l_tile[qb] += ea;
-      l_tile[qb] += eb;
-      pk[par][qb][f][pr] = pack_bf16x2(ea, eb);
+      l_tile[qb] += ea[w];
+      l_tile[qb] += eb[w];
+      pk[par][qb][f][pr] = pack_bf16x2(ea[w], eb[w]);
       asm volatile("" :: "v"(pk[par][qb][f][pr]), "v"(l_tile[qb]));                            // computed HERE (no sinking past the phase)
     }
   };
@@ -249,14 +284,25 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
     const s16x8 ac = __builtin_shufflevector(a, c, 0, 1, 2, 3, 4, 5, 6, 7);
     return __builtin_bit_cast(bf16x8, ac);
   };
-  // S(buffer `dst`) = K(kslot) Q^T: slot = 4 ds + 2 kb + qb; K fragment (kb, ds) read two fragments ahead (ring of four);
-  // FILL: the exp half-units 8 NF2 .. 63 of tile `par` go behind the MFMAs
+  // S(buffer `dst`) = K(kslot) Q^T: slot = 4 ds + 2 kb + qb; K fragment (kb, ds) read two fragments ahead (ring of four).
+  // FILL (every S phase but the prologue's): the exp half-units 8 NF2 .. 63 of tile `par` go behind the MFMAs; the first three K
+  // fragments are in kr_pre already; in front of MFMAs 29 and 31 the first three V^T fragments of tile `par` (in its V ring slot since the
+  // barrier before) are read for the P V phase, and in front of MFMA 31 the phase decides what follows it (`slow`)
   vita_rsrc_t rk_next = vita_make_rsrc_uniform(kbase), rv_next = rk_next;     // descriptors of the tiles being fetched (spread issue)
   bool spread_k = false, spread_v = false;
   int spread_k_slot = 0, spread_v_slot = 0;
+  bf16x8 kr_pre[3], vr_pre[3];                       // the next phase's first three fragments, read before the seam in front of it
+  auto needs_mask = [&](const TileIt& t) __attribute__((always_inline)) { return t.diag && t.j * KVT + KVT - 1 > q_off_wg; };
+  auto seg_masked = [&](const TileIt& t) __attribute__((always_inline)) { return PACKED && t.j * KVT < seg_lo_max; };
+  int nx1_masked = 0;                                // tile nx1 takes a mask (wave-uniform; kept with nx1)
+  unsigned long long slow = 0;                       // tile t fails the acceptance, or tile t+1 needs a mask (wave-uniform)
+  TileIt nx1, nx2;
+  auto next_masked = [&]() __attribute__((always_inline)) { return needs_mask(nx1) || seg_masked(nx1); };
   auto qk_phase = [&](int dst, unsigned kslot, bool fill, int par) __attribute__((always_inline)) {
+    const unsigned vslot = lds0 + LDS_V + par * TILEB;
     bf16x8 kr[4];
-    kr[0] = k_frag(kslot, 0); kr[1] = k_frag(kslot, 1);
+    if (fill) { kr[0] = kr_pre[0]; kr[1] = kr_pre[1]; kr[2] = kr_pre[2]; }
+    else { kr[0] = k_frag(kslot, 0); kr[1] = k_frag(kslot, 1); }
 #pragma unroll
     for (int s = 0; s < 32; ++s) {
       const int i = s >> 1, qb = s & 1, ds = i >> 1, kb = i & 1;
@@ -265,7 +311,17 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
         if (q < 4) { if (spread_k) dma_piece(rk_next, dk_off, lds_kw, spread_k_slot, q); }
         else if (spread_v) dma_piece(rv_next, dv_off, lds_vw, spread_v_slot, q - 4);
       }
-      if (qb == 0 && i + 2 < 16) kr[(i + 2) & 3] = k_frag(kslot, i + 2);
+      if (qb == 0 && i + 2 < 16 && !(fill && i == 0)) kr[(i + 2) & 3] = k_frag(kslot, i + 2);
+      if (fill && s == 29) vr_pre[0] = v_frag(vslot, 0);
+      if (fill && s == 31) {
+        vr_pre[1] = v_frag(vslot, 1); vr_pre[2] = v_frag(vslot, 2);
+        // the acceptance of tile `par` (its last row-sum add is behind MFMA 29) and the mask flag of the tile being multiplied, in one
+        // scalar: two v_cmp into lane masks and two s_or HERE, one s_cmp and one branch behind the last MFMA (the two ballots are
+        // separate on purpose: a ballot of `a || b` goes through a v_cndmask and a second v_cmp)
+        slow = __builtin_amdgcn_ballot_w64(!(l_tile[0] <= ACCEPT_MAX)) | __builtin_amdgcn_ballot_w64(!(l_tile[1] <= ACCEPT_MAX)) |
+               (unsigned long long)(unsigned)nx1_masked;
+        asm volatile("" : "+s"(slow));
+      }
       if (fill) __builtin_amdgcn_sched_barrier(0);   // DMA piece and K reads in FRONT of the slot's MFMA: they share the gap of the slot before
       if (ds == 0) {
         f32x16 z;
@@ -278,7 +334,7 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
       if (fill) {
         __builtin_amdgcn_sched_barrier(0);           // the slot's filler goes BEHIND its MFMA
 #pragma unroll
-        for (int u = MAP1.first[s]; u < MAP1.first[s + 1]; ++u) exp_half(par, 8 * NF2 + u);
+        for (int u = 0; u < DEAL1.n[s]; ++u) exp_half(par, DEAL1.h[s][u], DEAL1.w[s][u]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
@@ -288,14 +344,34 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
 #pragma unroll
     for (int u = 8 * NF2; u < 64; ++u) exp_half(par, u);
   };
-  // O += V(vslot)^T P(par)^T  ||  (has_next) the first NF2 fragments of tile par ^ 1
-  auto pv_phase = [&](int par, unsigned vslot, bool has_next) __attribute__((always_inline)) {
+  // O += V(vslot)^T P(par)^T  ||  (has_next) the first NF2 fragments of tile par ^ 1; the first three V^T fragments are in vr_pre.
+  // EARLY (a loop trip: another S phase follows and its K tile was fetched in this trip): the phase holds the tile's barrier and
+  // everything the next S phase needs before its first MFMA, so that the seam between the two holds the loop's branch and nothing else:
+  //   behind MFMAs 5 and 9 (sum-and-pack gaps)  the tile walk moves on (at a chunk end through the chunk tables, where it stands)
+  //                                             and the two DMA descriptors and the mask flag of the next trip are made, in SGPRs
+  //   in front of MFMA 29                       s_waitcnt vmcnt(0) lgkmcnt(0) + s_barrier.  What the barrier waits for is over by
+  //                                             then: every wave's reads of V(t) (the last one is issued in front of MFMA 26; the
+  //                                             lgkmcnt(0) sees it back) and of K(t+1) (the S phase), and this wave's pieces of K(t+2) /
+  //                                             V(t+1) (issued in the S phase).  The DMAs that refill the two slots are issued in the
+  //                                             NEXT S phase, behind the barrier, as before.
+  //   behind the barrier, in front of 29 and 30 the first three K fragments of K(t+2), from the ring slot this trip filled
+  auto pv_phase = [&](int par, unsigned vslot, bool has_next, bool early) __attribute__((always_inline)) {
+    const unsigned kslot_next = lds0 + LDS_K + par * TILEB;
     bf16x8 vr[4];
-    vr[0] = v_frag(vslot, 0); vr[1] = v_frag(vslot, 1);
+    if (has_next) { vr[0] = vr_pre[0]; vr[1] = vr_pre[1]; vr[2] = vr_pre[2]; }
+    else { vr[0] = v_frag(vslot, 0); vr[1] = v_frag(vslot, 1); }
 #pragma unroll
     for (int s = 0; s < 32; ++s) {
       const int i = s >> 1, qb = s & 1, t = i >> 2, db = i & 3;
-      if (qb == 0 && i + 2 < 16) vr[(i + 2) & 3] = v_frag(vslot, i + 2);
+      if (qb == 0 && i + 2 < 16 && !(has_next && i == 0)) vr[(i + 2) & 3] = v_frag(vslot, i + 2);
+      if (early && s == 29) {
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_sched_barrier(0);
+        kr_pre[0] = k_frag(kslot_next, 0);
+      }
+      if (early && s == 30) { kr_pre[1] = k_frag(kslot_next, 1); kr_pre[2] = k_frag(kslot_next, 2); }
       const u32x4 pw = {pk[par][qb][t][0], pk[par][qb][t][1], pk[par][qb][t][2], pk[par][qb][t][3]};
       const bf16x8 pf = __builtin_bit_cast(bf16x8, pw);
       asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+a"(o[qb][db]) : "v"(vr[i & 3]), "v"(pf));
@@ -303,6 +379,13 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
       if (has_next) {
 #pragma unroll
         for (int u = MAP2.first[s]; u < MAP2.first[s + 1]; ++u) exp_half(par ^ 1, u);
+      }
+      if (early && s == 5) { nx1 = nx2; walk.advance(nx2); }      // (behind the last tile the walk ends: no table is read past its end)
+      if (early && s == 9) {
+        rk_next = vita_make_rsrc_uniform(nx2.kp); rv_next = vita_make_rsrc_uniform(nx1.vp);
+        asm volatile("" : "+s"(rk_next), "+s"(rv_next));          // made HERE, not where the first piece goes out
+        nx1_masked = __builtin_amdgcn_readfirstlane((int)next_masked());
+        asm volatile("" : "+s"(nx1_masked));
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -347,7 +430,9 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   // itself.  If no row exceeds its maximum by 2^THR (a sum of many p, none of them large) the tile stands as computed.  Otherwise
   // the RARE path: the maxima move, l and O *= alpha (every P V MFMA of the tile before has been issued), all 64 half-units again.
   // The maxima therefore move on exactly the tiles, and to exactly the values, of the lazy rule: results are bit for bit its results.
-  auto accept = [&](int par) __attribute__((always_inline)) {
+  // In a loop trip the test itself is made inside the S phase (`slow`, qk_phase) and accept_slow is entered out of line with the P V
+  // phase's first three V^T fragments in registers; it repeats the test, since `slow` also stands for a tile that only needs a mask.
+  auto accept_slow = [&](int par) __attribute__((always_inline)) {
     if (__builtin_expect(__any(!(l_tile[0] <= ACCEPT_MAX) || !(l_tile[1] <= ACCEPT_MAX)), 0)) {
       float mx[2];
       row_max(par, mx);
@@ -372,24 +457,26 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
         for (int h = 0; h < 64; ++h) exp_half(par, h);
       }
     }
+  };
+  auto fold_tile = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int qb = 0; qb < 2; ++qb) {
       l_run[qb] += l_tile[qb];
       l_tile[qb] = 0.f;
     }
   };
-  auto needs_mask = [&](const TileIt& t) __attribute__((always_inline)) { return t.diag && t.j * KVT + KVT - 1 > q_off_wg; };
+  auto accept = [&](int par) __attribute__((always_inline)) { accept_slow(par); fold_tile(); };
   auto masks = [&](const TileIt& t, int par) __attribute__((always_inline)) {          // wave-uniform conditions
     if (needs_mask(t)) mask_tile(par, t.j * KVT);
     if constexpr (PACKED) {
-      if (t.j * KVT < seg_lo_max) seg_mask_tile(par, t.j * KVT);
+      if (seg_masked(t)) seg_mask_tile(par, t.j * KVT);
     }
   };
 
   // ---- prologue: K(0), V(0), K(1) -> LDS; S(0); the start of its softmax -----------------------------------------------------
   TileIt cur;
   walk.begin(cur);
-  TileIt nx1 = cur;
+  nx1 = cur;
   walk.advance(nx1);
   dma_k(cur, 0); dma_v(cur, 0);
   dma_k(nx1, 1);                                     // n_tiles >= 4
@@ -407,21 +494,31 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   for (int u = 0; u < 8 * NF2; ++u) exp_half(0, u);
 
   // ---- main loop: two tiles per trip (the S / P buffer parity is a compile-time constant); n_tiles is a multiple of 4 ----------
-  // full(par): `cur` sits in buffer par; K(t+2) -> K ring slot par, V(t+1) -> V ring slot par ^ 1; S(t+1) -> buffer par ^ 1
+  // full(par): tile t sits in buffer par; K(t+2) -> K ring slot par, V(t+1) -> V ring slot par ^ 1; S(t+1) -> buffer par ^ 1.  On entry
+  // nx1 / nx2 are tiles t+1 / t+2, rk_next / rv_next the descriptors of K(t+2) / V(t+1), nx1_masked the mask flag of tile t+1 and
+  // kr_pre the first three fragments of K(t+1): a loop trip (more_k) leaves all of that behind for the next one from inside its P V
+  // phase, barrier included; the peeled trip has no S phase to prepare and keeps its barrier behind the phase.
+  // The two seams of a trip: S(t+1) -> P V(t) is ONE scalar compare and branch (`slow`, fragments in vr_pre); P V(t) -> S(t+2) is the
+  // loop's own branch (fragments in kr_pre).
   auto full = [&](int par, bool more_k) __attribute__((always_inline)) {
-    TileIt nx2 = nx1;
     // K(t+2) and V(t+1) go out one piece at a time inside the S phase (K(t) in that slot was last read before the previous barrier)
-    spread_k = more_k;
-    if (more_k) { walk.advance(nx2); rk_next = vita_make_rsrc_uniform(nx2.kp); spread_k_slot = par; }
-    rv_next = vita_make_rsrc_uniform(nx1.vp); spread_v = true; spread_v_slot = par ^ 1;
+    spread_k = more_k; spread_k_slot = par;
+    spread_v = true; spread_v_slot = par ^ 1;
     qk_phase(par ^ 1, lds0 + LDS_K + (par ^ 1) * TILEB, true, par);
-    accept(par);
-    masks(nx1, par ^ 1);
-    pv_phase(par, lds0 + LDS_V + par * TILEB, true);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    nx1 = nx2;
+    if (__builtin_expect(slow != 0, 0)) { accept_slow(par); masks(nx1, par ^ 1); }
+    fold_tile();
+    pv_phase(par, lds0 + LDS_V + par * TILEB, true, more_k);
+    if (!more_k) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+    }
   };
+  // what the first trip finds ready (K(1) is in ring slot 1 since the prologue's first barrier)
+  kr_pre[0] = k_frag(lds0 + LDS_K + TILEB, 0); kr_pre[1] = k_frag(lds0 + LDS_K + TILEB, 1); kr_pre[2] = k_frag(lds0 + LDS_K + TILEB, 2);
+  nx2 = nx1;
+  walk.advance(nx2);                                 // n_tiles >= 4
+  rk_next = vita_make_rsrc_uniform(nx2.kp); rv_next = vita_make_rsrc_uniform(nx1.vp);
+  nx1_masked = __builtin_amdgcn_readfirstlane((int)next_masked());
   for (int t = 0; t + 2 < n_tiles; t += 2) {
     full(0, true);
     full(1, true);
@@ -429,7 +526,7 @@ __global__ __launch_bounds__(256, 1) void flash_fwd64_kernel(AttnArgs p) {
   full(0, false);
   finish_sm(1);                                      // last tile: the rest of its softmax, then P V
   accept(1);
-  pv_phase(1, lds0 + LDS_V + TILEB, false);
+  pv_phase(1, lds0 + LDS_V + TILEB, false, false);
 
   // ---- epilogue: O[row][head][d] = O^T / l, lse ------------------------------------------------------------------------------
   asm volatile("s_nop 15\n\ts_nop 15" : "+a"(o[0][0]), "+a"(o[0][1]), "+a"(o[0][2]), "+a"(o[0][3]), "+a"(o[1][0]), "+a"(o[1][1]), "+a"(o[1][2]), "+a"(o[1][3]));
