@@ -1002,6 +1002,37 @@ int vita_decode_layer_attn_mx4(const vita_decode_layer_params* p, const vita_mx4
 int vita_decode_layer_mlp_mx4(const vita_decode_layer_params* p, const vita_mx4_layer* w, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * MXFP8 for the prefill GEMMs (opt-in, CP = 1 and TP = 1): the four linears of a decoder layer on the block-scaled
+ * matrix instruction v_mfma_scale_f32_16x16x128_f8f6f4, which runs e4m3 operands at twice the bf16 rate and applies one E8M0 scale
+ * per 32 K elements in hardware.  Both operands are quantised: the weights once (kept beside the bf16 weights, 0.516 of their bytes),
+ * the activation rows of every linear in a pass of their own.  A matrix [rows][K] is kept as OCP e4m3fn codes [rows][K], one byte
+ * each (row stride in BYTES, a multiple of 16, pointer 16-byte aligned), plus one E8M0 scale byte per run of 32 consecutive K
+ * elements of a row, scales [rows][K / 32] dense.  The rule (csrc/mx8_rule.h), per run x[0..31]: amax = max |x_i|; amax == 0:
+ * e = 0, else e = the smallest integer with amax <= 448 * 2^e, clamped to [-126, 127]; scale byte = e + 127;
+ * code_i = e4m3fn_rne(x_i / 2^e), the sign kept also on a zero; nothing is clamped.  A run with a non-finite element gets scale byte
+ * 0xFF and codes 0x7F (NaN): either alone makes the instruction's result NaN, so every output that reads the run is NaN.  The GEMM
+ * computes with f32(code_i) * 2^e.
+ *
+ * vita_mx8_quantize: X [rows][K] bf16 (row stride ldx in elements, a multiple of 8, pointer 16-byte aligned) -> codes and scales.
+ *   K a multiple of 32 (else VITA_ERR_UNSUPPORTED, as for a misaligned base or stride, ldx < K or ldc_bytes < K).  Bytes of a code
+ *   row behind K are not written, rows behind `rows` are not touched.  A null pointer, rows <= 0 or K <= 0: VITA_ERR_INVALID_ARG.
+ * vita_gemm_mx8: C[M][N] bf16 = epilogue(sum_k dequant(A)[m][k] * dequant(W)[n][k]), fp32 accumulators (inside one instruction the
+ *   128 products are summed by the hardware; between instructions in fp32, ascending k).  Epilogues VITA_EPI_NONE, _BIAS, _RESIDUAL
+ *   (bias may be NULL) and _SWIGLU (W holds [gate(N) ; up(N)] = 2 N rows) with exactly vita_gemm_bf16's rounding order; any other
+ *   value, a missing bias (_BIAS) or R (_RESIDUAL), a null pointer, M, N or K <= 0: VITA_ERR_INVALID_ARG.  C may alias R.  Any
+ *   M >= 1: rows behind M are neither read nor written.  K and N multiples of 128, else VITA_ERR_UNSUPPORTED, as are: code bases not
+ *   16-byte aligned or code strides not multiples of 16 or < K; scale bases not 4-byte aligned; C / R / bias not 8-byte aligned, ldc
+ *   or ldr not a multiple of 4 or < N; M or K >= 2^31, N >= 2^30.  Nothing is launched on a refusal.  A row's bits do not depend on
+ *   M or on the tile the row falls in: every output element is one chain of K / 128 instructions in ascending k.
+ * Stand behind the linears of M/core/tensor_parallel/layers.py:825 in the prefill (M/core/models/multimodal/gpt_vl_model.py:339-347). */
+/* the input rows of the linears of M/core/tensor_parallel/layers.py:825 and their weights, quantised for vita_gemm_mx8 */
+int vita_mx8_quantize(const void* X, int64_t ldx, int64_t rows, int64_t K, void* codes, int64_t ldc_bytes, void* scales, void* stream);
+/* the linears of M/core/tensor_parallel/layers.py:825 at sq > 1 (prefill, M/core/models/multimodal/gpt_vl_model.py:339-347) */
+int vita_gemm_mx8(const void* A_codes, int64_t lda_bytes, const void* A_scales, const void* W_codes, int64_t ldw_bytes,
+                  const void* W_scales, void* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int epilogue, const void* bias,
+                  const void* R, int64_t ldr, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Frame / image preprocessing — ImageProcessor.process_images and dynamic_preprocess,
  * H/data/processor/image_processor.py:180-223,404-448, then the bf16 cast of
  * M/tasks/inference/module.py:693.  frames [n][height][width][3] uint8 RGB (frame_stride bytes apart)

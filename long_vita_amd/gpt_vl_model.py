@@ -20,7 +20,8 @@ import torch
 
 from . import context_parallel, ops, parallel_state as mpu, tracing, training_utils
 from .dot_product_attention import DotProductAttention
-from .inference_params import DecodeBatch, DraftRows, SharedPrefixBatch, check_decode_weight_dtype, check_kv_cache_dtype
+from .inference_params import (DecodeBatch, DraftRows, SharedPrefixBatch, check_decode_weight_dtype, check_kv_cache_dtype,
+                               check_prefill_weight_dtype)
 from .language_model_embedding import LanguageModelEmbedding
 from .layers import ColumnParallelLinear
 from .ops import WEIGHT_FORMATS          # the table itself: `ops` below may be replaced by a stand-in, its names are looked up per call
@@ -86,6 +87,12 @@ class GPTVLModel:
         # and the head go on reading
         self._w8 = None
         self.decode_weight_dtype = os.environ.get("VITA_DECODE_WEIGHT_DTYPE", "bf16")
+        # what the multi-row passes (prefill, extend, prefix-extend, the FP8-cache extend; CP = 1, TP = 1) run the four linears of every
+        # layer on: "bf16", or "mxfp8" = both operands as e4m3 codes + one E8M0 scale byte per 32 K elements on the block-scaled matrix
+        # instruction (ops.gemm_mx8).  The weight copies (0.516 of the bf16 bytes) are built at the first such pass and
+        # kept in self._mx8 next to the bf16 weights; the token steps (decode_weight_dtype) and the head do not read them
+        self._mx8 = None
+        self.prefill_weight_dtype = os.environ.get("VITA_PREFILL_WEIGHT_DTYPE", "bf16")
 
     @property
     def kv_cache_dtype(self) -> str:
@@ -105,7 +112,53 @@ class GPTVLModel:
             self._w8 = None                  # frees the quantised copies: they are of the format the switch leaves
         self._decode_weight_dtype = name
 
+    @property
+    def prefill_weight_dtype(self) -> str:
+        return self._prefill_weight_dtype
+
+    @prefill_weight_dtype.setter
+    def prefill_weight_dtype(self, name: str):
+        if check_prefill_weight_dtype(name) == "bf16":
+            self._mx8 = None                 # frees the quantised copies
+        self._prefill_weight_dtype = name
+
     W8_NAMES = ("qkv_w", "o_w", "fc1_w", "fc2_w")
+
+    def _mx8_layers(self, refresh: bool = False):
+        """The MXFP8 copies of every layer's four weights, {id(layer's parameter dict): {name: (codes, scales)}}, or None with
+        prefill_weight_dtype at "bf16": _w8_layers' life cycle.  Built on the device when first asked for (the first multi-row pass);
+        refresh (the start of a request) re-quantises, in place, every copy whose source has another data_ptr() or _version."""
+        if getattr(self, "_prefill_weight_dtype", "bf16") == "bf16":
+            return None
+        if mpu.get_context_parallel_world_size() > 1 or mpu.get_tensor_model_parallel_world_size() > 1 or self.force_cp_path:
+            raise NotImplementedError("the MXFP8 prefill is built for CP = 1 and TP = 1")
+        if getattr(self, "_mx8", None) is None:
+            self._mx8 = {id(lp): {} for lp in self.p["layers"]}
+            self._mx8_src = {id(lp): {} for lp in self.p["layers"]}
+        elif not refresh:
+            return self._mx8
+        for lp in self.p["layers"]:
+            q, src = self._mx8[id(lp)], self._mx8_src[id(lp)]
+            for name in self.W8_NAMES:
+                w = lp[name]
+                tag = (w.data_ptr(), w._version)
+                if src.get(name) != tag:
+                    have = q.get(name)
+                    reuse = have if have is not None and tuple(have[0].shape) == tuple(w.shape) else (None, None)
+                    q[name] = ops.mx8_quantize(w, *reuse)
+                    src[name] = tag
+        return self._mx8
+
+    def _linear(self, lp: dict, name: str, x: torch.Tensor, epilogue: int, bias=None, select_rows=None, **kw) -> torch.Tensor:
+        """Linear `name` of the layer whose parameters are lp on the rows x [s, K] of a multi-row pass: the one owner of the
+        prefill_weight_dtype choice.  "bf16": ops.gemm with the arguments it is given, select_rows included.  "mxfp8": ops.gemm_mx8 on
+        the quantised rows and the weight's copy; select_rows is dropped, a row's bits there do not depend on the row count."""
+        mx8 = self._mx8_layers()
+        if mx8 is None:
+            if select_rows is not None:
+                kw["select_rows"] = select_rows
+            return ops.gemm(x, lp[name], epilogue, bias, **kw)
+        return ops.gemm_mx8(x, *mx8[id(lp)][name], epilogue, bias, **kw)
 
     @property
     def _wfmt(self):
@@ -242,7 +295,7 @@ class GPTVLModel:
         row0 = cached_rows or 0
         use_cp = (cp > 1 or self.force_cp_path) and cached_rows is None   # force: exercise pack + all-gather + chunk tables at CP = 1
         x = ops.rmsnorm(h, lp["ln1"], c.eps, out=ws["x"])
-        qkv = ops.gemm(x, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"])
+        qkv = self._linear(lp, "qkv_w", x, ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"])
         ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, ws["kv"] if use_cp else None, ws["kv"].shape[0] if "kv" in ws else 1)
         m5 = qkv.view(1, s, c.kv_groups, c.qpg + 2, c.head_dim)
         q5 = m5[:, :, :, : c.qpg]                                  # grouped query view, read in place
@@ -291,13 +344,13 @@ class GPTVLModel:
             self.attn_events.append(ev)
         tp = mpu.get_tensor_model_parallel_world_size()
         if tp == 1:
-            ops.gemm(ctx.view(s, c.heads * c.head_dim), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+            self._linear(lp, "o_w", ctx.view(s, c.heads * c.head_dim), ops.EPI_RESIDUAL, residual=h, out=h)
         else:       # row-parallel: partial sums over the rank's heads -> bf16 all-reduce -> residual add
             self._row_parallel(ctx.view(s, c.heads * c.head_dim), lp["o_w"], h, ws["x"])
         x = ops.rmsnorm(h, lp["ln2"], c.eps, out=ws["x"])
-        act = ops.gemm(x, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"])
+        act = self._linear(lp, "fc1_w", x, ops.EPI_SWIGLU, out=ws["act"])
         if tp == 1:
-            ops.gemm(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+            self._linear(lp, "fc2_w", act, ops.EPI_RESIDUAL, residual=h, out=h)
         else:
             self._row_parallel(act, lp["fc2_w"], h, ws["x"])
         return h
@@ -309,10 +362,10 @@ class GPTVLModel:
         s = h.shape[0]
         ctx = ops.row_gather(ws["ctx"].view(s, c.heads * c.head_dim), idx, check_bounds=False)      # idx comes from a mask over the s rows
         rows = ops.row_gather(h, idx, check_bounds=False)
-        ops.gemm(ctx, lp["o_w"], ops.EPI_RESIDUAL, residual=rows, out=rows, select_rows=s)
+        self._linear(lp, "o_w", ctx, ops.EPI_RESIDUAL, residual=rows, out=rows, select_rows=s)
         x = ops.rmsnorm(rows, lp["ln2"], c.eps)
-        act = ops.gemm(x, lp["fc1_w"], ops.EPI_SWIGLU, select_rows=s)
-        return ops.gemm(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=rows, out=rows, select_rows=s)
+        act = self._linear(lp, "fc1_w", x, ops.EPI_SWIGLU, select_rows=s)
+        return self._linear(lp, "fc2_w", act, ops.EPI_RESIDUAL, residual=rows, out=rows, select_rows=s)
 
     @staticmethod
     def _row_parallel(x: torch.Tensor, w: torch.Tensor, h: torch.Tensor, scratch: torch.Tensor) -> torch.Tensor:
@@ -436,6 +489,8 @@ class GPTVLModel:
         ip.kv_scale_dict = {}
         if getattr(self, "_w8", None) is not None:
             self._w8_layers(refresh=True)    # a request starts: re-quantise the copies whose source weights changed
+        if getattr(self, "_mx8", None) is not None:
+            self._mx8_layers(refresh=True)
         if dtype == "fp8_e4m3":
             if cp > 1 or mpu.get_tensor_model_parallel_world_size() > 1 or self.force_cp_path:
                 raise NotImplementedError("the FP8 KV cache is built for CP = 1 and TP = 1")
@@ -986,7 +1041,7 @@ class GPTVLModel:
             with tracing.range(f"prefix extend: layer {li}"):
                 kv, tails = batch.prefix.key_value_memory_dict[li + 1], batch.tails[li]
                 x = ops.rmsnorm(h, lp["ln1"], c.eps, out=ws["x"])
-                qkv = ops.gemm(x, lp["qkv_w"], ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"])
+                qkv = self._linear(lp, "qkv_w", x, ops.EPI_BIAS, lp["qkv_b"], out=ws["qkv"])
                 ops.rope_qkv_(qkv, c.kv_groups, c.qpg, c.head_dim, cos, sin, None, 1)
                 m4 = qkv.view(n, c.kv_groups, c.qpg + 2, c.head_dim)
                 for b, (first, count, tail0) in enumerate(segs):
@@ -995,10 +1050,10 @@ class GPTVLModel:
                         tails[1, b, tail0: tail0 + count].copy_(m4[first: first + count, :, c.qpg + 1])
                 ctx = ops.prefix_extend_attn(m4[:, :, : c.qpg], kv[0], kv[1], batch.prefix_len, batch.tail_ptrs[li], batch.tail_row_stride,
                                              batch.tail_group_stride, batch.tail_cap, segs, out=ws["ctx"], table=batch.segments)
-                ops.gemm(ctx.view(n, c.heads * c.head_dim), lp["o_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+                self._linear(lp, "o_w", ctx.view(n, c.heads * c.head_dim), ops.EPI_RESIDUAL, residual=h, out=h)
                 x = ops.rmsnorm(h, lp["ln2"], c.eps, out=ws["x"])
-                act = ops.gemm(x, lp["fc1_w"], ops.EPI_SWIGLU, out=ws["act"])
-                ops.gemm(act, lp["fc2_w"], ops.EPI_RESIDUAL, residual=h, out=h)
+                act = self._linear(lp, "fc1_w", x, ops.EPI_SWIGLU, out=ws["act"])
+                self._linear(lp, "fc2_w", act, ops.EPI_RESIDUAL, residual=h, out=h)
         batch.advance()
         rows = ops.rmsnorm(ops.row_gather(h, last), self.p["final_ln"], c.eps)
         return self._head(rows, check_nan=True).contiguous()                              # [B, 1, vocab]

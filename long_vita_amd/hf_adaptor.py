@@ -32,7 +32,7 @@ from typing import Optional
 import torch
 
 from . import checkpoint, generation, gpt_vl_model, lib, ops, vision
-from .inference_params import ForwardStep, check_decode_weight_dtype, check_kv_cache_dtype
+from .inference_params import ForwardStep, check_decode_weight_dtype, check_kv_cache_dtype, check_prefill_weight_dtype
 
 
 def _get(cfg, name, default=None):
@@ -172,14 +172,26 @@ class LongVITAForCausalLM:
     def decode_weight_dtype(self, name: str):
         self.model.decode_weight_dtype = name
 
+    @property
+    def prefill_weight_dtype(self) -> str:
+        """What the multi-row passes (prefill, extend, prefix-extend) run the decoder layers' linears on: "bf16" (default) or "mxfp8"
+        (both operands as e4m3 codes + an E8M0 scale per 32 K elements on the block-scaled matrix instruction, the weight copies kept
+        next to the bf16 weights).  Lives on the model (GPTVLModel.prefill_weight_dtype)."""
+        return self.model.prefill_weight_dtype
+
+    @prefill_weight_dtype.setter
+    def prefill_weight_dtype(self, name: str):
+        self.model.prefill_weight_dtype = name
+
     # -- construction ---------------------------------------------------------------------------------
     @classmethod
     def from_state_dict(cls, config, state_dict, device="cuda", generation_config=None, kv_cache_dtype=None,
-                        decode_weight_dtype=None):
+                        decode_weight_dtype=None, prefill_weight_dtype=None):
         """state_dict: `LongVITAForCausalLM.state_dict()` names — `model.embed_tokens / layers.N.* / norm`, `lm_head`,
         `model.vision_model.*`, `model.vision_projection.*` (modeling_long_vita.py:67-68)."""
         check_kv_cache_dtype(kv_cache_dtype, allow_none=True)       # before the weights are read
         check_decode_weight_dtype(decode_weight_dtype, allow_none=True)
+        check_prefill_weight_dtype(prefill_weight_dtype, allow_none=True)
         lib.load(allow_build=False)                      # the HIP path or nothing
         gcfg, vcfg = configs_from_hf(config)
         vis = None
@@ -193,14 +205,18 @@ class LongVITAForCausalLM:
             self.kv_cache_dtype = kv_cache_dtype
         if decode_weight_dtype is not None:
             self.decode_weight_dtype = decode_weight_dtype
+        if prefill_weight_dtype is not None:
+            self.prefill_weight_dtype = prefill_weight_dtype
         return self
 
     @classmethod
     def from_pretrained(cls, model_path, *model_args, torch_dtype=None, device_map=None, attn_implementation=None,
-                        trust_remote_code=None, device=None, kv_cache_dtype=None, decode_weight_dtype=None, **kwargs):
+                        trust_remote_code=None, device=None, kv_cache_dtype=None, decode_weight_dtype=None, prefill_weight_dtype=None,
+                        **kwargs):
         """`AutoModelForCausalLM.from_pretrained(model_path, trust_remote_code=True, device_map=..., torch_dtype=torch.bfloat16,
         attn_implementation="flash_attention_2")` of inference_long_vita.py:811-817: config.json + *.safetensors of a `*_HF` directory."""
         check_decode_weight_dtype(decode_weight_dtype, allow_none=True)   # before anything is read
+        check_prefill_weight_dtype(prefill_weight_dtype, allow_none=True)
         if torch_dtype not in (None, torch.bfloat16, "bfloat16", "auto"):
             raise ValueError("the HIP path computes in bf16 (the reference script passes torch_dtype=torch.bfloat16)")
         config = json.load(open(os.path.join(model_path, "config.json")))
@@ -213,7 +229,8 @@ class LongVITAForCausalLM:
         dev = device or (device_map if isinstance(device_map, (str, torch.device)) and device_map != "auto" else "cuda")
         check_kv_cache_dtype(kv_cache_dtype, allow_none=True)       # before the weights are read
         return cls.from_state_dict(config, checkpoint.load_hf_safetensors(model_path), device=dev, generation_config=gen,
-                                   kv_cache_dtype=kv_cache_dtype, decode_weight_dtype=decode_weight_dtype)
+                                   kv_cache_dtype=kv_cache_dtype, decode_weight_dtype=decode_weight_dtype,
+                                   prefill_weight_dtype=prefill_weight_dtype)
 
     def eval(self):
         return self

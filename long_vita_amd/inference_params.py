@@ -47,6 +47,20 @@ def check_decode_weight_dtype(name, allow_none: bool = False):
     return name
 
 
+PREFILL_WEIGHT_DTYPES = ("bf16", "mxfp8")
+
+
+def check_prefill_weight_dtype(name, allow_none: bool = False):
+    """What the multi-row passes (prefill, extend, prefix-extend) run the four linears of a decoder layer on: "bf16" (the default) or
+    "mxfp8" (both operands as OCP e4m3fn codes + one E8M0 scale byte per 32 consecutive K elements, on the block-scaled matrix
+    instruction).  Independent of decode_weight_dtype.  Anything else is a ValueError."""
+    if name is None and allow_none:
+        return None
+    if name not in PREFILL_WEIGHT_DTYPES:
+        raise ValueError(f"prefill_weight_dtype must be one of {PREFILL_WEIGHT_DTYPES}, got {name!r}")
+    return name
+
+
 class InferenceParams:
     def __init__(self, max_batch_size: int, max_sequence_length: int, kv_cache_dtype=None):
         self.max_sequence_length = max_sequence_length

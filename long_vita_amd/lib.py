@@ -297,6 +297,8 @@ PROTOTYPES = {
     "vita_gemv_rows_mx4": (_i, [_p, _l, _i, _p, _l, _p, _p, _l, _l, _l, _i, _p, _p, _l, _p]),
     "vita_decode_layer_attn_mx4": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(Mx4Layer), C.POINTER(Kv8Cache), _p]),
     "vita_decode_layer_mlp_mx4": (_i, [C.POINTER(DecodeLayerParams), C.POINTER(Mx4Layer), _p]),
+    "vita_mx8_quantize": (_i, [_p, _l, _l, _l, _p, _l, _p, _p]),
+    "vita_gemm_mx8": (_i, [_p, _l, _p, _p, _l, _p, _p, _l, _l, _l, _l, _i, _p, _p, _l, _p]),
 }
 
 _lock = threading.Lock()

@@ -1468,6 +1468,107 @@ def gemv_rows_mx4(x: torch.Tensor, codes: torch.Tensor, scales: torch.Tensor, ep
 
 
 # ------------------------------------------------------------------------------------------------
+# MXFP8 (e4m3 codes + E8M0 bytes) for the opt-in prefill GEMMs on the block-scaled matrix instruction
+# (include/vita_hip.h: vita_mx8_quantize, vita_gemm_mx8).  Not one of WEIGHT_FORMATS: that table is the decoder GEMVs'.
+# ------------------------------------------------------------------------------------------------
+MX8_BLOCK = 32                           # MXFP8: consecutive K elements of a row that share a scale byte
+
+
+def mx8_layout(N: int, K: int) -> dict:
+    """Pure layout, no allocation: codes [N, K] uint8 (one e4m3 code per byte), scales [N, K / 32] uint8 (E8M0), and their bytes next
+    to the bf16 matrix's."""
+    if K % MX8_BLOCK:
+        raise ValueError(f"mx8: K = {K} must be a multiple of {MX8_BLOCK}")
+    nbytes = N * K + N * (K // MX8_BLOCK)
+    return {"codes": (N, K), "scales": (N, K // MX8_BLOCK), "bytes": nbytes, "bytes_bf16": 2 * N * K, "ratio": nbytes / (2 * N * K)}
+
+
+def _mx8_views(codes: torch.Tensor, scales: torch.Tensor, what: str):
+    """(rows, K) of a codes / scales pair, or what is wrong with it."""
+    if codes.dim() != 2 or codes.dtype not in (torch.uint8, KV8_DTYPE) or codes.stride(1) != 1:
+        raise ValueError(f"{what}: codes [rows, K] must be uint8 (or {KV8_DTYPE}) with unit inner stride")
+    rows, K = codes.shape
+    if K % MX8_BLOCK:
+        raise RuntimeError(f"{what}: K = {K} must be a multiple of {MX8_BLOCK}")
+    if tuple(scales.shape) != (rows, K // MX8_BLOCK) or scales.dtype != torch.uint8 or not scales.is_contiguous():
+        raise ValueError(f"{what}: scales must be dense uint8 [rows, K / {MX8_BLOCK}]")
+    return rows, K
+
+
+def mx8_quantize(x: torch.Tensor, codes: Optional[torch.Tensor] = None, scales: Optional[torch.Tensor] = None):
+    """x [rows, K] bf16 (unit inner stride) -> (codes [rows, K] uint8, scales [rows, K / 32] uint8) by the MXFP8 rule of
+    csrc/mx8_rule.h on every run of 32 consecutive K elements of a row.  codes / scales: destinations to fill (codes may be a
+    padded-row view)."""
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise ValueError("mx8_quantize: x [rows, K] with unit inner stride")
+    rows, K = x.shape
+    lay = mx8_layout(rows, K)
+    if codes is None:
+        codes = torch.empty(lay["codes"], dtype=torch.uint8, device=x.device)
+    if scales is None:
+        scales = torch.empty(lay["scales"], dtype=torch.uint8, device=x.device)
+    if _mx8_views(codes, scales, "mx8_quantize") != (rows, K):
+        raise ValueError("mx8_quantize: codes and scales do not match x")
+    _L.check(_L.load().vita_mx8_quantize(_dev(x, "x", BF16), x.stride(0), rows, K, _dev(codes, "codes"), codes.stride(0),
+                                         _dev(scales, "scales", torch.uint8), _stream()), "vita_mx8_quantize")
+    return codes, scales
+
+
+_mx8_ws: dict = {}         # device index -> the codes and scales of gemm_mx8's bf16 input: one buffer, grown to the largest request
+
+
+def _mx8_workspace(rows: int, K: int, device: torch.device):
+    """(codes [rows, K], scales [rows, K / 32]) views of the device's workspace."""
+    n_codes, n_scales = rows * K, rows * (K // MX8_BLOCK)
+    off = (n_codes + 15) // 16 * 16
+    key = device.index if device.index is not None else torch.cuda.current_device()
+    ws = _mx8_ws.get(key)
+    if ws is None or ws.numel() < off + n_scales:
+        _mx8_ws.pop(key, None)                          # free the smaller one first
+        ws = _mx8_ws[key] = torch.empty(off + n_scales, dtype=torch.uint8, device=device)
+    return ws[:n_codes].view(rows, K), ws[off:off + n_scales].view(rows, K // MX8_BLOCK)
+
+
+def gemm_mx8(a, w_codes: torch.Tensor, w_scales: torch.Tensor, epilogue: int = EPI_NONE, bias: Optional[torch.Tensor] = None,
+             residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out[M, N] = epilogue(dequant(a)[M, K] @ dequant(w)[N (or 2 N), K]^T) on the block-scaled FP8 matrix instruction, fp32
+    accumulation; epilogues NONE, BIAS, RESIDUAL, SWIGLU with vita_gemm_bf16's rounding order.  a: bf16 [M, K] (unit inner stride;
+    quantised first into a per-device workspace) or a (codes, scales) pair from mx8_quantize.  K and N multiples of 128.  out may
+    alias residual.  A row's bits do not depend on M."""
+    n_rows, K = _mx8_views(w_codes, w_scales, "gemm_mx8")
+    if isinstance(a, torch.Tensor):
+        if a.dim() != 2 or a.stride(1) != 1:
+            raise ValueError("gemm_mx8: a [M, K] with unit inner stride")
+        if a.shape[1] != K:
+            raise RuntimeError(f"supplied weight's shape is {tuple(w_codes.shape)}, K = {a.shape[1]} expected")
+        M = a.shape[0]
+        device = a.device
+        a_codes, a_scales = (None, None) if M == 0 else mx8_quantize(a, *_mx8_workspace(M, K, a.device))
+    else:
+        a_codes, a_scales = a
+        M, Ka = _mx8_views(a_codes, a_scales, "gemm_mx8")
+        device = a_codes.device
+        if Ka != K:
+            raise RuntimeError(f"supplied weight's shape is {tuple(w_codes.shape)}, K = {Ka} expected")
+    N = n_rows // 2 if epilogue == EPI_SWIGLU else n_rows
+    y = torch.empty((M, N), dtype=BF16, device=device) if out is None else out
+    if y.shape != (M, N) or y.stride(1) != 1:
+        raise ValueError("out has wrong shape")
+    if M == 0:
+        return y
+    r_ptr, ldr = None, 0
+    if residual is not None:
+        if residual.shape != (M, N) or residual.stride(1) != 1:
+            raise ValueError("residual has wrong shape")
+        r_ptr, ldr = _dev(residual, "residual", BF16), residual.stride(0)
+    _L.check(_L.load().vita_gemm_mx8(_dev(a_codes, "a codes"), a_codes.stride(0), _dev(a_scales, "a scales", torch.uint8),
+                                     _dev(w_codes, "w codes"), w_codes.stride(0), _dev(w_scales, "w scales", torch.uint8),
+                                     _dev(y, "out", BF16), y.stride(0), M, N, K, epilogue, _opt(bias, "bias", BF16), r_ptr, ldr,
+                                     _stream()), "vita_gemm_mx8")
+    return y
+
+
+# ------------------------------------------------------------------------------------------------
 # beam search on a shared-prefix KV cache (M/inference/text_generation/generation.py:283-471)
 # ------------------------------------------------------------------------------------------------
 BEAM_MAX = 8

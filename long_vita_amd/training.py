@@ -58,9 +58,16 @@ class TrainStep:
         same kernels produce the same values either way (bit-identical loss and gradients); it is what 288 GB of HBM are for, and it is
         off by default because Megatron's flag means "keep the layer input only"."""
         self.m = model
+        self._check_prefill_weights()
         self.is_instruction = is_instruction_dataset
         self.recompute_num_layers = recompute_num_layers
         self.keep_attention = bool(keep_attention)
+
+    def _check_prefill_weights(self):
+        """Training differentiates the bf16 linears; the recompute block's first forward is decoder_layer, which follows the switch."""
+        dtype = getattr(self.m, "prefill_weight_dtype", "bf16")
+        if dtype != "bf16":
+            raise ValueError(f"TrainStep needs the model's prefill_weight_dtype at \"bf16\", got {dtype!r}")
 
     # ------------------------------------------------------------------------------------------
     def _layer_recompute(self, h, lp, cos, sin, mlp: bool = True):
@@ -209,6 +216,7 @@ class TrainStep:
         {"images", "indices"} (global).  `--logit-mask` semantics: logit_mask = loss_mask.bool().
         position_ids [1, S] with resets (--reset-position-ids): stage-2 packed samples — RoPE restarts and attention is
         block-diagonal (M/training/utils.py:267-270; CP = 1)."""
+        self._check_prefill_weights()
         m, c = self.m, self.m.cfg
         cp = mpu.get_context_parallel_world_size()
         seq = tokens.shape[1]
