@@ -772,20 +772,21 @@ __global__ __launch_bounds__(256) void ce_vp_stats_kernel(const T* __restrict__ 
 // stats_all [tp, rows, 4] (rank-major, as all_gather_into_tensor leaves it) -> loss [rows], row_stat [rows, 2] = {max, sumexp}
 __global__ __launch_bounds__(256) void ce_vp_finish_kernel(const float* __restrict__ stats_all, int tp, int64_t rows,
                                                            float* __restrict__ loss, float* __restrict__ row_stat) {
-  const int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (row >= rows) return;
-  float mx = -INFINITY;
-  for (int r = 0; r < tp; ++r) mx = fmaxf(mx, stats_all[((int64_t)r * rows + row) * 4]);
-  float se = 0.f, pred = 0.f, held = 0.f;
-  for (int r = 0; r < tp; ++r) {
-    const float* st = stats_all + ((int64_t)r * rows + row) * 4;
-    se += st[1] * __expf(st[0] - mx);
-    pred += st[2];
-    held += st[3];
+  // grid-stride: grid_for caps the grid at 4096 workgroups, so one row per thread left rows >= 4096 * 256 unwritten
+  for (int64_t row = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < rows; row += (int64_t)gridDim.x * blockDim.x) {
+    float mx = -INFINITY;
+    for (int r = 0; r < tp; ++r) mx = fmaxf(mx, stats_all[((int64_t)r * rows + row) * 4]);
+    float se = 0.f, pred = 0.f, held = 0.f;
+    for (int r = 0; r < tp; ++r) {
+      const float* st = stats_all + ((int64_t)r * rows + row) * 4;
+      se += st[1] * __expf(st[0] - mx);
+      pred += st[2];
+      held += st[3];
+    }
+    if (loss) loss[row] = __logf(se) - (held > 0.f ? pred - mx : 0.f);
+    row_stat[row * 2] = mx;
+    row_stat[row * 2 + 1] = se;
   }
-  if (loss) loss[row] = __logf(se) - (held > 0.f ? pred - mx : 0.f);
-  row_stat[row * 2] = mx;
-  row_stat[row * 2 + 1] = se;
 }
 
 template <typename T>
